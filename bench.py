@@ -6,11 +6,14 @@ A "step" is one pass of the hot path (reads packed 32 bases per record, 3-round 
 index and its own contiguous share of the read run (weak scaling, no data-path collective: the path shards by
 reads).  Rank 0 prints ONE JSON line.  See DESIGN.md "Measurement" for the roofline and cpu_baseline definitions.
 
-    python bench.py                       # 1 GPU, defaults
+    python bench.py                       # 1 GPU, defaults: the headline only
+    python bench.py --full                # the headline and everything below
+    python bench.py --dump-outputs DIR    # also write what the last timed step computed, DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-What the line holds besides the contract's fields:
+A plain run sets up (genome, index, engine, reads), warms up, times the K steps and prints the line: `value` (reads/s), `ms_per_step`,
+the workload and nothing that needs work of its own.  With --full the line also holds (each measured after the timed region):
   parity          a STRIDED sample of every rank's batch (every (n/20000)-th read, so the whole genome with its repeats is
                   covered) compared bit for bit with the oracle; a mismatch nulls `value` and the process exits 1
   roofline        byte model of THIS implementation (bytes the kernels request from the index-side arrays, counted on the
@@ -19,6 +22,10 @@ What the line holds besides the contract's fields:
   cpu_baseline    the real reference (oracle/_ref, kind "reference") or, without it, the oracle (CPU port), timed on this box's host
                   cores on a bounded sample
   pcie_inclusive  the host-buffer boundary call (H2D of reads, D2H of results), SURVEY 8(d)'s metric; never `value`
+  one_step_at_a_time, workloads, extension, ingest_rank0: see DESIGN.md section 5
+
+--dump-outputs writes, after the timed steps, what the last one returned for a fixed sample of its reads (dump_outputs below); the
+inputs depend on the arguments only, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -87,7 +94,17 @@ def parse_args():
                          "scatters contiguous read ranges over RCCL, every rank seeds its range, rank 0 gathers mems and seeds")
     ap.add_argument("-k", type=int, default=19); ap.add_argument("-r", type=float, default=1.5)
     ap.add_argument("-y", type=int, default=20); ap.add_argument("-c", type=int, default=500); ap.add_argument("-s", type=int, default=10)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the parity gate, roofline, traffic, CPU baseline, PCIe-inclusive, one-step-at-a-time, "
+                         "side-workload and extension measurements (off: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a fixed sample of the reads, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.ingest_rank0 and not args.full:
+        ap.error("--ingest-rank0 is one of the --full measurements")
+    return args
 
 
 def workload_args(args):
@@ -199,13 +216,49 @@ def cpu_model():
     return "unknown"
 
 
+DUMP_READS, DUMP_SEED, DUMP_BYTES = 16384, 20261016, 64 << 20
+
+
+def dump_outputs(eng, res, args, rank, world):
+    """--dump-outputs: what the last timed step returned (res: its device result).  The whole result is ~6 GB of mems and seeds, so what
+    is written is the CSR slice a caller receives for a fixed, seeded sample of the batch's reads (cs_engine_gather_reads: mem_off, mems,
+    seed_off, seeds, cut to the first sampled reads that fit 64 MB), the batch's totals, and the device-side digests of the whole result
+    (cs_engine_result_digest) as 16-bit limbs.  float64 throughout: every value is an integer below 2^53 (positions < 2^37, interval
+    bounds < 2^34, info < 2^47), so exact."""
+    rng = np.random.default_rng(DUMP_SEED)
+    ids = np.sort(rng.choice(args.reads, size=min(DUMP_READS, args.reads), replace=False)).astype(np.uint64)
+    got = eng.gather_reads(ids)
+    sal = got.seed_off is not None
+    n_m = np.diff(got.mem_off.astype(np.int64))
+    n_s = np.diff(got.seed_off.astype(np.int64)) if sal else np.zeros_like(n_m)
+    per_read = 8 * (3 + 4 * n_m + 3 * n_s)                 # id, two offsets, 4 words per mem, 3 per seed
+    k = int(np.searchsorted(np.cumsum(per_read), DUMP_BYTES - (1 << 20), side="right"))
+    m_end = int(got.mem_off[k])
+    arrays = {"read_ids": ids[:k], "mem_off": got.mem_off[:k + 1],
+              "mems": np.stack([got.mems[f][:m_end] for f in ("x0", "x1", "x2", "info")], axis=1)}
+    if sal:
+        s_end = int(got.seed_off[k])
+        arrays["seed_off"] = got.seed_off[:k + 1]
+        arrays["seeds"] = np.stack([got.seeds[f][:s_end] for f in ("rbeg", "qbeg", "len")], axis=1)
+    dg = np.array(eng.result_digest(), dtype=np.uint64)
+    arrays["digest"] = np.stack([(dg >> np.uint64(16 * i)) & np.uint64(0xFFFF) for i in range(4)], axis=1)   # [mem_off, mems, seed_off, seeds] x limb
+    arrays["totals"] = np.array([res.n_reads, res.n_mems, res.n_seeds], dtype=np.uint64)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    prefix = "rank%d." % rank if world > 1 else ""
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.size == 0 or max(int(a.max()), -int(a.min())) < 2 ** 53, name
+        np.save(os.path.join(args.dump_outputs, prefix + name + ".npy"), a.astype(np.float64))
+    log("outputs of the last timed step: %d of %d reads sampled, %s written to %s" % (k, args.reads, ", ".join(sorted(arrays)), args.dump_outputs))
+
+
 def main():
     args = parse_args()
     if args.lib:
         os.environ["CS_LIB"] = args.lib
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     traffic = None
-    if args.traffic == "live" and not args.pmc_child and world_env == 1:
+    if args.full and args.traffic == "live" and not args.pmc_child and world_env == 1:
         traffic = pmc_traffic(args)  # before this process touches the GPU: the child needs the HBM
 
     import torch
@@ -230,7 +283,11 @@ def main():
     t0 = time.time()
     L = int(args.genome_mbp * 1e6)
     prof = synth.PROFILES[args.profile]
+    # the same inputs in every run: planted repeat copies overlap, and G[idx] = copies with repeated indices keeps an arbitrary one of
+    # them unless deterministic algorithms are on (then index_put_ sorts the indices)
+    torch.use_deterministic_algorithms(True)
     G = synth.make_genome(L, seed=20261003, device=dev, **prof["genome"])
+    torch.use_deterministic_algorithms(False)
     g_host = G.cpu().numpy()
     torch.cuda.synchronize()
     t1 = time.time()
@@ -261,7 +318,9 @@ def main():
     eng = ca.Engine(ix, local, **eopts)
     t3 = time.time()
     rkw = dict(prof["reads"])
+    torch.use_deterministic_algorithms(True)
     bases, off = synth.make_reads(G, args.reads, args.read_len, seed=777 + rank, lo_frac=rank / world, hi_frac=(rank + 1) / world, **rkw)
+    torch.use_deterministic_algorithms(False)
     n_bases = bases.numel()
     torch.cuda.synchronize()
     del G
@@ -315,6 +374,29 @@ def main():
     D.barrier()
     elapsed = D.max_over_ranks(time.perf_counter() - ts)
     st_timed = eng.stats()
+    if args.dump_outputs:   # before anything else runs on the engine: its last result is the last timed step's
+        dump_outputs(eng, res, args, rank, world)
+
+    total_reads = args.reads * world * args.steps
+    value = total_reads / elapsed
+    out = {
+        "metric": "reads/sec (150bp) seeded", "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "steps_in_flight": in_flight,
+        "config": {"workload": "%s; %d x %d bp %s reads per GPU per step; -k %d -r %g -y %d -c %d%s" %
+                               (prof["describe"](args.genome_mbp), args.reads, args.read_len, "position-sorted" if rkw.get("sort", True) else "shuffled",
+                                args.k, args.r, args.y, args.c, " (mems only)" if args.no_sal else " + SAL"),
+                   "profile": args.profile, "genome_mbp": args.genome_mbp, "reads_per_gpu_per_step": args.reads, "read_len": args.read_len,
+                   "parallelism": "reads sharded over %d GPU(s), index replicated" % world},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)   # the ONE line
+        eng.close(); ix.close()
+        D.close()
+        return 0
+
     # the same steps one at a time (blocking calls): the HIP-event times of the stage mean "the stage alone on the GPU" only here, so
     # the roofline below is taken from this run; with two passes in flight the stages of two passes overlap and stretch each other
     if in_flight > 1:
@@ -325,21 +407,7 @@ def main():
         st = eng.stats()
     else:
         st, serial_ms = st_timed, 1e3 * elapsed / args.steps
-
-    total_reads = args.reads * world * args.steps
-    value = total_reads / elapsed
-    out = {
-        "metric": "reads/sec (150bp) seeded", "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-        "steps_in_flight": in_flight,
-        "one_step_at_a_time": {"ms_per_step": serial_ms, "reads_per_s": args.reads / (serial_ms * 1e-3), "note": "rank 0: the same steps as blocking cs_engine_seed_batch_device calls"},
-        "config": {"workload": "%s; %d x %d bp %s reads per GPU per step; -k %d -r %g -y %d -c %d%s" %
-                               (prof["describe"](args.genome_mbp), args.reads, args.read_len, "position-sorted" if rkw.get("sort", True) else "shuffled",
-                                args.k, args.r, args.y, args.c, " (mems only)" if args.no_sal else " + SAL"),
-                   "profile": args.profile, "genome_mbp": args.genome_mbp, "reads_per_gpu_per_step": args.reads, "read_len": args.read_len,
-                   "parallelism": "reads sharded over %d GPU(s), index replicated" % world},
-    }
+    out["one_step_at_a_time"] = {"ms_per_step": serial_ms, "reads_per_s": args.reads / (serial_ms * 1e-3), "note": "rank 0: the same steps as blocking cs_engine_seed_batch_device calls"}
 
     # ---- parity gate on EVERY rank: a strided sample of this rank's batch against the oracle (the checker, never the product)
     import _oracle
@@ -617,7 +685,7 @@ def main():
         torch.cuda.empty_cache()
         out["workloads"] = {}
         for w in side:
-            cmd = [sys.executable, os.path.abspath(__file__), "--side-child", "--profile", w, "--steps", "3", "--warmup", "1", "--traffic", "none",
+            cmd = [sys.executable, os.path.abspath(__file__), "--side-child", "--full", "--profile", w, "--steps", "3", "--warmup", "1", "--traffic", "none",
                    "--cpu-seconds", "0", "--no-host-io", "--no-extension", "--genome-mbp", str(args.genome_mbp), "--reads", str(args.reads), "--read-len", str(args.read_len),
                    "--check-reads", str(args.check_reads), "-k", str(args.k), "-r", str(args.r), "-y", str(args.y), "-c", str(args.c), "-s", str(args.s)]
             if args.lib:

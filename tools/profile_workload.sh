@@ -5,7 +5,7 @@
 tag=${1:-rXX}; prof=${2:-repeat50}
 R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp; ulimit -c 0
 O=$R/gpurun_out
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 $R/bench.py --profile $prof --steps 2 --warmup 1 --in-flight 1 --cpu-seconds 0 --no-host-io --traffic none --no-extension --side-workloads "" > $O/${tag}_bench_profiled.json 2> /tmp/prof_$tag.err || { tail -5 /tmp/prof_$tag.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 $R/bench.py --full --profile $prof --steps 2 --warmup 1 --in-flight 1 --cpu-seconds 0 --no-host-io --traffic none --no-extension --side-workloads "" > $O/${tag}_bench_profiled.json 2> /tmp/prof_$tag.err || { tail -5 /tmp/prof_$tag.err; exit 1; }
 python3 - "$tag" <<'PY'
 import csv, glob, sys, os, json
 tag = sys.argv[1]; R = os.environ["GRAFT_REPO_ROOT"]
@@ -34,7 +34,7 @@ out = [{"span_ms": (p[1] - p[0]) / 1e6, "launches": p[2], "summed_kernel_ms": p[
 json.dump({"passes": out, "last_pass_launches_name_startms_durms": launches}, open(os.path.join(R, "gpurun_out", tag + "_stage_span.json"), "w"), indent=1)
 print(json.dumps(out))
 PY
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d /tmp/sq_$tag -- python3 $R/bench.py --profile $prof --reads 4000000 --steps 1 --warmup 0 --in-flight 1 --cpu-seconds 0 --no-host-io --traffic none --check-reads 1000 --no-extension --side-workloads "" > /tmp/sq_$tag.json 2> /tmp/sq_$tag.err || { tail -5 /tmp/sq_$tag.err; exit 1; }
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d /tmp/sq_$tag -- python3 $R/bench.py --full --profile $prof --reads 4000000 --steps 1 --warmup 0 --in-flight 1 --cpu-seconds 0 --no-host-io --traffic none --check-reads 1000 --no-extension --side-workloads "" > /tmp/sq_$tag.json 2> /tmp/sq_$tag.err || { tail -5 /tmp/sq_$tag.err; exit 1; }
 python3 - "$tag" > $O/${tag}_sq_counters.txt <<'PY'
 import csv, glob, sys, collections
 tag = sys.argv[1]

@@ -8,10 +8,10 @@ out=$R/gpurun_out/${tag}_workload_profiles.jsonl
 : > $out
 for p in default repeat50 err1 err2indel shuffled repeat50err1; do
   echo "[profiles] $p" >&2
-  timeout -k 10 400 python3 $R/bench.py --steps 3 --warmup 1 --cpu-seconds 0 --no-host-io --profile $p >> $out 2>> $R/gpurun_out/${tag}_workload_profiles.err || echo "{\"profile\": \"$p\", \"failed\": true}" >> $out
+  timeout -k 10 400 python3 $R/bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --no-host-io --profile $p >> $out 2>> ${out%.jsonl}.err || echo "{\"profile\": \"$p\", \"failed\": true}" >> $out
 done
 echo "[profiles] default -r 1.0 -y 20" >&2
-timeout -k 10 400 python3 $R/bench.py --steps 3 --warmup 1 --cpu-seconds 0 --no-host-io -r 1.0 -y 20 >> $out 2>> $R/gpurun_out/${tag}_workload_profiles.err || echo "{\"profile\": \"default -r 1.0\", \"failed\": true}" >> $out
+timeout -k 10 400 python3 $R/bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --no-host-io -r 1.0 -y 20 >> $out 2>> ${out%.jsonl}.err || echo "{\"profile\": \"default -r 1.0\", \"failed\": true}" >> $out
 python3 - "$out" <<'PY'
 import json, sys
 for ln in open(sys.argv[1]):

@@ -2,7 +2,7 @@
 # tools/timeline.sh <tag> -- kernel trace of two bench passes; prints every launch of the SMEM stage of the last pass (start ms, duration ms)
 tag=${1:-tl}
 R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp; ulimit -c 0
-rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_$tag -- python3 $R/bench.py --steps 2 --warmup 1 --cpu-seconds 0 --no-host-io --traffic none ${@:2} > /dev/null 2> /tmp/tl_$tag.err
+rocprofv3 --kernel-trace --output-format csv -d /tmp/tl_$tag -- python3 $R/bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 --no-host-io --traffic none ${@:2} > /dev/null 2> /tmp/tl_$tag.err
 python3 - "$tag" <<'PY'
 import csv, glob, sys, os
 tag = sys.argv[1]; R = os.environ["GRAFT_REPO_ROOT"]
