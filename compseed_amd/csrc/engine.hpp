@@ -1,0 +1,201 @@
+// engine.hpp -- what the translation units of the seeding engine share (not part of the C ABI):
+//   engine.hip     ABI lifecycle, options, index load / residency, statistics, device memory helpers
+//   seed_pass.hip  one seeding pass on a pass context: SMEM stage, sort, SAL; the k-mer filter
+//   pipelines.hip  the host pipeline (cs_engine_submit / collect, blocking host variants) and the device pipeline
+//   inspect.hip    digest and gather of the last result, index validation, primitives, the random-line probe
+// Kernels are defined in the unit that launches them; the headers included by more than one unit hold types and __device__ functions.
+#pragma once
+#include "cs_internal.hpp"
+#include "fm_device.hpp"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <shared_mutex>
+#include <string>
+
+#include <hip/hip_runtime.h>
+
+using namespace csd;
+
+extern thread_local std::string g_err;
+inline int fail(int code, const std::string &msg) { g_err = msg; return code; }
+
+#define HIP_TRY(expr)                                                                              \
+	do {                                                                                           \
+		hipError_t e__ = (expr);                                                                   \
+		if (e__ != hipSuccess) {                                                                   \
+			(void)hipGetLastError();                                                               \
+			return fail(e__ == hipErrorOutOfMemory ? CS_ENOMEM : CS_EDEVICE,                       \
+			            std::string(#expr) + ": " + hipGetErrorString(e__));                       \
+		}                                                                                          \
+	} while (0)
+#define CS_TRY(expr) do { int rc__ = (expr); if (rc__ != CS_OK) return rc__; } while (0)
+
+inline unsigned grid_for(int64_t n, int block) { return (unsigned)std::max<int64_t>(1, (n + block - 1) / block); }
+
+// ------------------------------------------------------------------------------------------------ owning buffers and handles
+// Grow-only buffers that free their memory when destroyed; move-only.
+template <typename T> struct DevBuf {
+	T *p = nullptr; size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
+	~DevBuf() { release(); }
+	int reserve(size_t n, bool keep = false, hipStream_t s = nullptr, size_t keep_n = 0)
+	{
+		if (n <= cap) return CS_OK;
+		size_t want = std::max(n, cap + cap / 2);
+		T *q = nullptr;
+		HIP_TRY(hipMalloc((void **)&q, want * sizeof(T)));
+		if (keep && p && keep_n) {
+			hipError_t e = hipMemcpyAsync(q, p, keep_n * sizeof(T), hipMemcpyDeviceToDevice, s);
+			if (e == hipSuccess) e = hipStreamSynchronize(s);
+			if (e != hipSuccess) { (void)hipFree(q); return fail(CS_EDEVICE, hipGetErrorString(e)); }
+		}
+		if (p) (void)hipFree(p);
+		p = q; cap = want;
+		return CS_OK;
+	}
+	void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+// grow-only plain host memory (the expanded results of cs_engine_seed_batch; `keep_n` elements survive a reallocation)
+template <typename T> struct HostBuf {
+	T *p = nullptr; size_t cap = 0;
+	HostBuf() = default;
+	HostBuf(const HostBuf &) = delete;
+	HostBuf &operator=(const HostBuf &) = delete;
+	HostBuf(HostBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+	HostBuf &operator=(HostBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
+	~HostBuf() { release(); }
+	int reserve(size_t n, size_t keep_n = 0)
+	{
+		if (n <= cap) return 0;
+		size_t want = std::max(n, cap + cap / 4);
+		T *q = (T *)malloc(want * sizeof(T));
+		if (!q) return 1;
+		if (p && keep_n) memcpy(q, p, keep_n * sizeof(T));
+		free(p);
+		p = q; cap = want;
+		return 0;
+	}
+	void release() { free(p); p = nullptr; cap = 0; }
+};
+template <typename T> struct PinBuf {
+	T *p = nullptr, *dp = nullptr; size_t cap = 0; // dp: the same memory as the device addresses it (kernels may store into it)
+	PinBuf() = default;
+	PinBuf(const PinBuf &) = delete;
+	PinBuf &operator=(const PinBuf &) = delete;
+	PinBuf(PinBuf &&o) noexcept : p(o.p), dp(o.dp), cap(o.cap) { o.p = o.dp = nullptr; o.cap = 0; }
+	PinBuf &operator=(PinBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(dp, o.dp); std::swap(cap, o.cap); } return *this; }
+	~PinBuf() { release(); }
+	int reserve(size_t n, bool keep = false, size_t keep_n = 0)
+	{
+		if (n <= cap) return CS_OK;
+		size_t want = std::max(n, cap + cap / 2);
+		T *q = nullptr;
+		HIP_TRY(hipHostMalloc((void **)&q, want * sizeof(T), hipHostMallocDefault));
+		if (keep && p && keep_n) memcpy(q, p, keep_n * sizeof(T));
+		if (p) (void)hipHostFree(p);
+		p = q; cap = want; dp = nullptr;
+		void *d = nullptr;
+		if (hipHostGetDevicePointer(&d, p, 0) == hipSuccess) dp = (T *)d; else (void)hipGetLastError();
+		return CS_OK;
+	}
+	void release() { if (p) (void)hipHostFree(p); p = nullptr; dp = nullptr; cap = 0; }
+};
+// a stream or an event, destroyed with its holder; converts to the raw handle, so it is passed to the HIP calls as it is
+template <typename H, hipError_t (*Destroy)(H)> struct HipHandle {
+	H h = nullptr;
+	HipHandle() = default;
+	HipHandle(const HipHandle &) = delete;
+	HipHandle &operator=(const HipHandle &) = delete;
+	HipHandle(HipHandle &&o) noexcept : h(o.h) { o.h = nullptr; }
+	HipHandle &operator=(HipHandle &&o) noexcept { std::swap(h, o.h); return *this; }
+	~HipHandle() { if (h) (void)Destroy(h); }
+	operator H() const { return h; }
+};
+using HipStream = HipHandle<hipStream_t, hipStreamDestroy>;
+using HipEvent = HipHandle<hipEvent_t, hipEventDestroy>;
+
+// ------------------------------------------------------------------------------------------------ engine
+// What one seeding pass owns.  An engine has one or two of them: the tail of a pass (late iterations with a few thousand calls each,
+// the sort, SAL, ten host round trips) leaves most of the GPU idle, and a small part of a batch is nearly all tail; a second pass,
+// on a context of its own, fills it.
+struct PassCtx {
+	HipStream stream, stream2, stream3, stream4; // stream2: round 3 (low priority); stream3: calls without LEPs; stream4: wide sweeps
+	HipEvent ev_r3a, ev_r3b, ev_wa, ev_wb, ev_wc;
+	HipEvent ev[4];
+	DevBuf<uint8_t> d_pending; // r3text_kernel: reads with calls of rounds 1/2 still queued when it starts
+	DevBuf<uint32_t> d_cnt_snap; DevBuf<uint64_t> d_auxA, d_auxB; // re-seeding from the text
+	// inputs
+	DevBuf<uint8_t> d_seq; DevBuf<uint4> d_seqp; const uint4 *seqp_cur = nullptr; const uint64_t *off_base = nullptr; // d_seqp: pack_reads_kernel's records for the batch whose offsets start at off_base
+	// SMEM stage
+	DevBuf<OutMem> d_out, d_out2; DevBuf<uint32_t> d_cnt, d_cnt2, d_ovf; DevBuf<uint4> d_spill;
+	DevBuf<unsigned long long> d_ctr; // [0] task counter, [1] queries, [2] overflow count, [3] max len
+	DevBuf<uint8_t> d_tmp, d_tmp2;
+	PinBuf<unsigned long long> h_ctr;
+	// results (device)
+	DevBuf<uint64_t> d_mem_off, d_seed_off, d_seed_of_mem; DevBuf<OutMem> d_mems; DevBuf<uint64_t> d_salcnt; DevBuf<OutSeed> d_seeds; // d_salcnt: SA slots per mem, written by the sort that makes d_mems
+	// split (forward / cooperative backward) SMEM path
+	DevBuf<uint64_t> d_fqA, d_fqB, d_fqR; DevBuf<uint4> d_sst2; DevBuf<BTask> d_bq; DevBuf<uint4> d_lep; DevBuf<OvfRec> d_ovfrec;
+	DevBuf<uint32_t> d_okey, d_oidx, d_okey2, d_oidx2; DevBuf<uint64_t> d_okey64, d_okey64b; DevBuf<unsigned long long> d_sctr; PinBuf<unsigned long long> h_sctr;
+	cs_stats_t st{};
+	DevBuf<unsigned long long> d_evc; uint64_t stream_bytes = 0; // byte model: event counters [N_KID][N_EV] on the device, stream part on the host
+	struct { bool valid = false; int64_t n_reads = 0; uint64_t n_mems = 0, n_seeds = 0; int want_sal = 0; } last; // the result held in d_mems / d_seeds
+};
+
+constexpr int PIPE_DEPTH = 4; // batches in flight in the host pipeline (cs_engine_submit): one pinned result slot each
+struct cs_engine {
+	int device = 0;
+	int n_cu = 256;
+	cs_engine_options_t opt{};
+	int smem_mode = 1;          // 1 = split kernels (default), 0 = fused one-lane-per-read kernel (CS_SMEM_MODE=fused)
+	int occ_win = 5; // ... of bwd_win_kernel
+	int occ_fwd = 4, occ_bwd = 4; // resident 256-thread blocks per CU of fwd_kernel / bwd_kernel
+	size_t lep_arena_bytes = (size_t)32 << 30;
+	uint32_t cap = 64;          // mems per read kept by the first pass
+	size_t max_raw_bytes = (size_t)24 << 30;
+	DevIndex ix{};
+	DevBuf<uint4> d_bwt; DevBuf<uint64_t> d_sa;
+	DevBuf<uint32_t> d_fsa32; DevBuf<uint64_t> d_fsa64; // full suffix array (one of the two)
+	DevBuf<uint32_t> d_text2, d_isa32; DevBuf<uint64_t> d_isa64; // text mode: 2-bit text + inverse suffix array
+	DevBuf<uint8_t> d_lcp, d_rep; // re-seeding from the text: capped LCP by row, repeat length by position
+	DevBuf<uint4> d_jump; int jump_k = 0; // round-3 jump table
+	// k-mer filter of the text for the min_seed_len in use: passes hold filter_rw shared; rebuilding it for another min_seed_len
+	// (run_pass) takes it exclusively
+	DevBuf<uint64_t> d_bloom; int bloom_k = 0; uint32_t bloom_bits = 0;
+	std::shared_mutex filter_rw;
+	int bloom_tried_k = 0;                         // last min_seed_len the filter was (re)built or found not to fit for
+	std::unique_ptr<PassCtx> ctx[2];               // the second one is made on the first call that can use two passes at a time
+	PassCtx *last_ctx = nullptr;                   // which context holds the last whole-batch result (`last` lives in that one)
+	// host variants (seed_host_pipelined): copy streams, three input slots, two pack slots, pinned packed results, expanded results
+	HipStream s_up, s_down; HipEvent hp_ev_pk[2], hp_ev_dn[4], hp_ev_done[PIPE_DEPTH];
+	PinBuf<uint4> hp_stage[3]; // records made by the host (host_pack.cpp), staged for the upload into hp_in[slot]
+	DevBuf<uint8_t> hp_in[3], hp_pk_mems[2]; DevBuf<uint64_t> hp_inoff[3], hp_pk_moff[2], hp_pk_soff[2]; DevBuf<uint32_t> hp_pk_rlo[2]; DevBuf<uint8_t> hp_pk_rhi[2]; // seeds: low words and fifth bytes of rbeg
+	PinBuf<uint64_t> hp_moff[PIPE_DEPTH], hp_soff[PIPE_DEPTH]; PinBuf<uint8_t> hp_mems[PIPE_DEPTH]; PinBuf<uint32_t> hp_rlo[PIPE_DEPTH]; PinBuf<uint8_t> hp_rhi[PIPE_DEPTH]; // pinned result slots (slot = batch % PIPE_DEPTH)
+	struct HostPipe *hp = nullptr;
+	HostBuf<cs_intv_t> x_mems; HostBuf<cs_seed_t> x_seeds;
+	struct DevPipe *dp = nullptr;                  // cs_engine_submit_device / cs_engine_collect_device
+	// cs_engine_gather_reads
+	DevBuf<uint64_t> d_sel, d_sel_moff, d_sel_soff; DevBuf<OutMem> d_sel_mems; DevBuf<OutSeed> d_sel_seeds;
+	PinBuf<uint64_t> h_mem_off, h_seed_off; PinBuf<OutMem> h_mems; PinBuf<OutSeed> h_seeds;
+};
+
+inline int n_pass_ctx(const cs_engine *e) { return e->ctx[1] ? 2 : 1; }
+inline void invalidate_last(cs_engine *e) { for (auto &c : e->ctx) if (c) c->last.valid = false; e->last_ctx = nullptr; }
+
+// seed_pass.hip
+int add_pass_ctx(cs_engine *e);   // makes the engine's next pass context (the first at engine creation)
+int seed_pass_init(cs_engine *e); // occupancy of the split kernels, the k-mer filter for the default min_seed_len
+// One seeding pass on context c; every caller runs its passes through here.  d_recs: the reads as pack_reads_kernel's records when
+// the host made them (d_bases is then null), else null.
+int run_pass(cs_engine *e, PassCtx *c, const cs_params_t *par, int64_t n_reads, const uint8_t *d_bases, const uint64_t *d_off,
+             uint64_t n_bases, uint64_t *nm, uint64_t *ns, const uint4 *d_recs);
+// pipelines.hip
+void pipe_stop(cs_engine *e);
+void dev_pipe_stop(cs_engine *e);
+bool pipe_busy(const cs_engine *e);

@@ -105,26 +105,26 @@ struct Intv64 { uint64_t x0, x1, x2; };           // the primitive entry points 
 
 __device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (uint64_t)hi << 32 | lo; }
 
-// file layout -> device layout, in place, one thread per 128-row block of the file (run once per engine)
-__global__ void relayout_kernel(uint4 *bwt, uint64_t n_blocks, unsigned long long *overflow)
+struct OutMem { uint64_t x0, x1, x2, info; };   // == cs_intv_t / bwtintv_t
+struct OutSeed { int64_t rbeg; int32_t qbeg, len; }; // == cs_seed_t
+struct BTask { uint32_t r; uint16_t x, mi_kind, n, ret; uint32_t cls; };  // 16 bytes, stored at the forward task's slot;
+                                                                           // cls = size class 0..3, 0xffffffff = no call
+struct OvfRec { OutMem m; uint32_t r, pad; };                              // a mem beyond a read's first `cap`
+
+// a bi-interval as a 16-byte LEP entry (seed_kernels.hpp, smem_split.hpp) and as a jump-table entry (smem_split.hpp)
+__device__ __forceinline__ uint4 pack_lep(const Intv &v, uint32_t end)
 {
-	uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (b >= n_blocks) return;
-	uint4 q0 = bwt[b * 4], q1 = bwt[b * 4 + 1], q2 = bwt[b * 4 + 2], q3 = bwt[b * 4 + 3];
-	const uint32_t w[8] = {q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
-	uint64_t h[4] = {u64_of(q0.x, q0.y), u64_of(q0.z, q0.w), u64_of(q1.x, q1.y), u64_of(q1.z, q1.w)};
-	uint32_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0}, first64[4] = {0, 0, 0, 0};
-	for (int i = 0; i < 128; ++i) {
-		uint32_t code = (w[i >> 4] >> ((15 - (i & 15)) << 1)) & 3u; // bwt_B0, bwt.h:80
-		lo[i >> 5] |= (code & 1u) << (i & 31);
-		hi[i >> 5] |= (code >> 1) << (i & 31);
-		if (i < 64) ++first64[code];
-	}
-	for (int c = 0; c < 4; ++c) if ((h[c] + first64[c]) >> 32) atomicAdd(overflow, 1ull);
-	bwt[b * 4]     = make_uint4((uint32_t)h[0], (uint32_t)h[1], (uint32_t)h[2], (uint32_t)h[3]);
-	bwt[b * 4 + 1] = make_uint4(lo[0], lo[1], hi[0], hi[1]);
-	bwt[b * 4 + 2] = make_uint4((uint32_t)(h[0] + first64[0]), (uint32_t)(h[1] + first64[1]), (uint32_t)(h[2] + first64[2]), (uint32_t)(h[3] + first64[3]));
-	bwt[b * 4 + 3] = make_uint4(lo[2], lo[3], hi[2], hi[3]);
+	uint4 e;
+	e.x = (uint32_t)v.x0; e.y = (uint32_t)v.x1; e.z = (uint32_t)v.x2;
+	e.w = (uint32_t)(v.x0 >> 32) | (uint32_t)(v.x1 >> 32) << 5 | end << 16; // (bits 10..14 held the top of a 37-bit size; sizes are 32-bit)
+	return e;
+}
+__device__ __forceinline__ void unpack_lep(const uint4 &e, Intv &v, uint32_t &end)
+{
+	v.x0 = (uint64_t)(e.w & 31u) << 32 | e.x;
+	v.x1 = (uint64_t)((e.w >> 5) & 31u) << 32 | e.y;
+	v.x2 = e.z;
+	end = e.w >> 16;
 }
 
 struct Block { uint4 cnt, pl; }; // counts A,C,G,T | lo0, lo1, hi0, hi1
@@ -304,31 +304,6 @@ __device__ __forceinline__ uint64_t sa_direct(const DevIndex &ix, uint64_t k)
 
 __device__ __forceinline__ uint64_t isa_direct(const DevIndex &ix, uint64_t pos) { return ix.isa32 ? (uint64_t)ix.isa32[pos] : ix.isa64[pos]; }
 
-// one-time preparation of the text-mode arrays from the full suffix array: T[SA[r] - 1] is the BWT character of row r
-template <typename T>
-__global__ void text_isa_fill_kernel(const DevIndex ix, const T *fsa, uint8_t *tbytes, T *isa)
-{
-	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= ix.seq_len; r += (uint64_t)gridDim.x * blockDim.x) {
-		uint64_t s = (uint64_t)fsa[r];
-		isa[s] = (T)r;
-		if (r == ix.primary) continue; // the row of the whole text: its BWT character is the sentinel
-		uint64_t row = r - (r > ix.primary);
-		Block b = load_block(ix, row >> OCC_SHIFT);
-		uint32_t p = (uint32_t)row & OCC_MASK, w = p >> 5, bit = p & 31;
-		uint32_t lo = w == 0 ? b.pl.x : b.pl.y, hi = w == 0 ? b.pl.z : b.pl.w;
-		tbytes[s - 1] = (uint8_t)(((lo >> bit) & 1u) | (((hi >> bit) & 1u) << 1));
-	}
-}
-__global__ void text_pack_kernel(const uint8_t *tbytes, uint64_t n, uint32_t *text2)
-{
-	uint64_t nw = (n + 15) >> 4;
-	for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < nw; w += (uint64_t)gridDim.x * blockDim.x) {
-		uint32_t v = 0;
-		for (int j = 0; j < 16; ++j) { uint64_t p = w * 16 + j; if (p < n) v |= (uint32_t)(tbytes[p] & 3) << (2 * j); }
-		text2[w] = v;
-	}
-}
-
 // 32 text bases from position pos on (2 bits each, base j in bits 2j..2j+1); the text buffer is padded
 __device__ __forceinline__ uint64_t text_win(const DevIndex &ix, uint64_t pos)
 {
@@ -349,20 +324,6 @@ __device__ __forceinline__ uint32_t text_lcp(const DevIndex &ix, uint64_t a, uin
 		if (m < 32) break;
 	}
 	return l < lim ? l : lim;
-}
-template <typename T>
-__global__ void lcp_fill_kernel(const DevIndex ix, const T *fsa, uint8_t *lcp)
-{
-	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= ix.seq_len + 1; r += (uint64_t)gridDim.x * blockDim.x)
-		lcp[r] = (r == 0 || r > ix.seq_len) ? 0 : (uint8_t)text_lcp(ix, (uint64_t)fsa[r - 1], (uint64_t)fsa[r], 255u);
-}
-template <typename T>
-__global__ void rep_fill_kernel(const DevIndex ix, const T *fsa, const uint8_t *lcp, uint8_t *rep)
-{
-	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= ix.seq_len; r += (uint64_t)gridDim.x * blockDim.x) {
-		uint8_t a = lcp[r], b = lcp[r + 1];
-		rep[(uint64_t)fsa[r]] = a > b ? a : b; // row 0 (the empty suffix) writes rep[seq_len] = 0
-	}
 }
 
 // bwt_sa (bwt.c:86-96)

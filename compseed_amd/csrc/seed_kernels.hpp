@@ -25,8 +25,6 @@
 
 namespace csd {
 
-struct OutMem { uint64_t x0, x1, x2, info; };   // == cs_intv_t / bwtintv_t
-
 struct SeedArgs {
 	DevIndex ix;
 	const uint8_t  *seq;        // nt4 codes of the sub-batch, 8-byte padded at the end
@@ -51,21 +49,6 @@ enum : int {
 	ST_R2_NEXT, ST_R3_START, ST_R3_CHECK, ST_FINISH, ST_EXIT,
 	ST_FWD_WAIT, ST_BWD_WAIT, ST_R3_WAIT
 };
-
-__device__ __forceinline__ uint4 pack_lep(const Intv &v, uint32_t end)
-{
-	uint4 e;
-	e.x = (uint32_t)v.x0; e.y = (uint32_t)v.x1; e.z = (uint32_t)v.x2;
-	e.w = (uint32_t)(v.x0 >> 32) | (uint32_t)(v.x1 >> 32) << 5 | end << 16; // (bits 10..14 held the top of a 37-bit size; sizes are 32-bit)
-	return e;
-}
-__device__ __forceinline__ void unpack_lep(const uint4 &e, Intv &v, uint32_t &end)
-{
-	v.x0 = (uint64_t)(e.w & 31u) << 32 | e.x;
-	v.x1 = (uint64_t)((e.w >> 5) & 31u) << 32 | e.y;
-	v.x2 = e.z;
-	end = e.w >> 16;
-}
 
 template <int BLOCK, int LEP_LDS, bool COUNT>
 __global__ __launch_bounds__(BLOCK, (LEP_LDS <= 10 ? 4 : LEP_LDS <= 13 ? 3 : 2)) void smem_kernel(const SeedArgs A)
@@ -275,8 +258,6 @@ __global__ void sal_count_kernel(const OutMem *mems, uint64_t n_mems, uint32_t m
 	cnt[m] = x2 < max_occ ? x2 : max_occ;
 }
 
-struct OutSeed { int64_t rbeg; int32_t qbeg, len; }; // == cs_seed_t
-
 // GATHER: the slot is looked up in the HBM-resident full suffix array right here (one pass over the seeds instead of two).
 // A lane per mem, but a mem with more than SAL_LIGHT slots (a repeat: up to max_occ = 500 of them) is expanded by the whole wave, 64 slots
 // at a time with coalesced stores -- one lane looping over 500 slots while 63 wait was what SAL cost on repeat-rich genomes.
@@ -331,67 +312,11 @@ __global__ void sal_gather_kernel(const DevIndex ix, OutSeed *seeds, uint64_t n_
 	seeds[s].rbeg = (int64_t)sa_direct(ix, (uint64_t)seeds[s].rbeg);
 }
 
-// Materialise SA[row] for every row from the 1-in-sa_intv samples: lane t starts at sampled row t*sa_intv, whose value is
-// known, and follows bwt_invPsi (one text position back per step, bwt.c:53-59) writing SA = value - steps until it
-// reaches the next sampled row.  Every row lies on exactly one such chain, so all seq_len+1 rows get written once.
-template <typename T>
-__global__ void sa_fill_kernel(const DevIndex ix, T *full)
-{
-	uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= ix.n_sa) return;
-	uint64_t k = t << ix.sa_shift;
-	uint64_t s = (t == 0) ? ix.seq_len : ix.sa[t]; // row 0 is the "$" suffix at text position seq_len
-	full[k] = (T)s;
-	for (;;) {
-		k = inv_psi(ix, k);
-		if ((k & ix.sa_mask) == 0) break;
-		--s;
-		full[k] = (T)s;
-	}
-}
-
 __global__ void seed_off_kernel(const uint64_t *mem_off, const uint64_t *seed_of_mem, int64_t n_reads, uint64_t *seed_off)
 {
 	int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r > n_reads) return;
 	seed_off[r] = seed_of_mem[mem_off[r]];
-}
-
-// ------------------------------------------------------------------------------------------------------------ primitive test entries
-__global__ void occ4_kernel(const DevIndex ix, const uint64_t *k, uint64_t *cnt, int64_t n)
-{
-	int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= n) return;
-	uint64_t c[4]; occ4(ix, k[t], c);
-	cnt[4 * t] = c[0]; cnt[4 * t + 1] = c[1]; cnt[4 * t + 2] = c[2]; cnt[4 * t + 3] = c[3];
-}
-__global__ void extend_kernel(const DevIndex ix, const OutMem *ik, const uint8_t *is_back, OutMem *ok, int64_t n)
-{
-	int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= n) return;
-	Intv64 v64 = {ik[t].x0, ik[t].x1, ik[t].x2}, o[4];
-	extend4(ix, v64, is_back[t] != 0, o);
-	const bool small = ik[t].x2 < (1ull << 32);            // the single-child forms serve the search: sizes below 2^32
-	Intv v = {ik[t].x0, ik[t].x1, (uint32_t)ik[t].x2};
-	for (int c = 0; c < 4; ++c) {
-		OutMem m = {o[c].x0, o[c].x1, o[c].x2, 0};
-		ok[4 * t + c] = m;
-		// the single-child paths used by the search must agree with the four-child one
-		NoCtr W;
-		Intv o1 = extend1_rt(ix, v, is_back[t] != 0, c, W);
-		Intv o2 = is_back[t] ? extend1<true>(ix, v, c, W) : extend1<false>(ix, v, c, W);
-		if (small && v.x0 != 0 && v.x1 != 0 && (o2.x0 != o[c].x0 || o2.x1 != o[c].x1 || o2.x2 != o[c].x2)) ok[4 * t + c].info = 2;
-		if (small && (o1.x0 != o[c].x0 || o1.x1 != o[c].x1 || o1.x2 != o[c].x2)) ok[4 * t + c].info = 1;
-	}
-}
-__global__ void sa_kernel(const DevIndex ix, const uint64_t *k, uint64_t *sa, int64_t n)
-{
-	int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= n) return;
-	uint64_t walked = sa_lookup(ix, k[t]);
-	// when the full suffix array is resident it must agree with the walk on every row (mismatch => poison the answer)
-	if ((ix.fsa32 || ix.fsa64) && sa_direct(ix, k[t]) != walked) walked = 0xdeadbeefdeadbeefull;
-	sa[t] = walked;
 }
 
 } // namespace csd

@@ -41,10 +41,6 @@ __device__ __host__ __forceinline__ uint64_t ftask_pack(uint32_t r, uint32_t x, 
 	return (uint64_t)r | (uint64_t)x << 32 | (uint64_t)min_intv << 48 | (uint64_t)kind << 62;
 }
 
-struct BTask { uint32_t r; uint16_t x, mi_kind, n, ret; uint32_t cls; };  // 16 bytes, stored at the forward task's slot;
-                                                                           // cls = size class 0..3, 0xffffffff = no call
-struct OvfRec { OutMem m; uint32_t r, pad; };                              // a mem beyond a read's first `cap`
-
 struct SplitArgs {
 	DevIndex ix;
 	const uint8_t  *seq;
@@ -154,25 +150,6 @@ __device__ __forceinline__ bool sst_get(const uint4 *sst, uint4 *sst2, int len, 
 __device__ __forceinline__ void sst_put(uint4 *sst, uint4 *sst2, int len, uint32_t code, const Intv &v)
 {
 	if (len <= SST_K) sst[sst_index(len, code)] = pack_lep(v, 0); else sst2[sst2_index(len, code)] = pack_lep(v, 0);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Round-3 jump table.  bwt_seed_strategy1 (bwt.c:358-379) extends forward from a start x and looks at the interval only
-// once i - x >= min_seed_len, so the first min_seed_len bases of every segment are pure pointer chasing whose
-// intermediate intervals nobody reads -- and at those depths the interval is still wide, so every step costs TWO random
-// records.  The bi-interval of every k-mer (k = jump_k <= min_seed_len) is therefore precomputed once per engine into a
-// table in HBM (4^15 x 16 B = 17 GB by default: this is what 288 GB are for) and a segment starts with ONE lookup instead of k - 1
-// extensions.  A k-mer that does not occur has size 0 and every later extension keeps it at 0, exactly as in the
-// reference, so the emitted seeds are unchanged; the skipped steps are counted as queries answered by the cache.
-__global__ void jump_fill_kernel(const DevIndex ix, int k, uint4 *table)
-{
-	uint64_t n = 1ull << (2 * k);
-	for (uint64_t m = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; m < n; m += (uint64_t)gridDim.x * blockDim.x) {
-		Intv v = set_intv(ix, (int)((m >> (2 * (k - 1))) & 3));
-		NoCtr W;
-		for (int j = k - 2; j >= 0; --j) v = extend1<false>(ix, v, 3 - (int)((m >> (2 * j)) & 3), W);
-		table[m] = pack_lep(v, 0);
-	}
 }
 
 // The reads a second time, packed: one 16-byte record per 32 bases -- .x/.y the bases, 2 bits each, base j in bits 2j..2j+1 (the
@@ -1762,44 +1739,6 @@ __device__ __forceinline__ const OutMem &mem_at(const OutMem *src, uint32_t cap,
 {
 	return a < cap ? src[a] : ovf[ovf_idx[olo + (a - cap)]].m;
 }
-__global__ void sort_compact2_kernel(const OutMem *raw, const uint32_t *cnt, uint32_t cap, const OvfRec *ovf, const uint32_t *ovf_key,
-                                     const uint32_t *ovf_idx, uint64_t n_ovf, const uint64_t *mem_off, int64_t n_reads, OutMem *mems, int skip_small,
-                                     uint64_t *salcnt, uint32_t max_occ)
-{
-	int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (r >= n_reads) return;
-	uint32_t n = cnt[r];
-	if (skip_small && n <= 64 && n <= cap) return; // done by sort_compact16_kernel
-	const OutMem *src = raw + (size_t)r * cap;
-	OutMem *dst = mems + mem_off[r]; uint64_t *dsc = salcnt + mem_off[r]; // (the SA slots each mem will ask for: comp_seed.cpp:2313-2325)
-	if (n <= 16 && n <= cap) { // keys in registers, ranks by 16 x 16 compares, no re-reads
-		uint64_t k[16];
-#pragma unroll
-		for (int a = 0; a < 16; ++a) k[a] = (uint32_t)a < n ? src[a].info : ~0ull;
-#pragma unroll
-		for (int a = 0; a < 16; ++a) {
-			if ((uint32_t)a < n) {
-				uint32_t rank = 0;
-#pragma unroll
-				for (int b = 0; b < 16; ++b) rank += (k[b] < k[a]) || (k[b] == k[a] && b < a); // padding keys are never smaller
-				dst[rank] = src[a]; dsc[rank] = src[a].x2 < max_occ ? src[a].x2 : max_occ;
-			}
-		}
-		return;
-	}
-	uint64_t olo = 0;
-	if (n > cap) { // lower bound of r among the sorted overflow keys
-		uint64_t lo = 0, hi = n_ovf;
-		while (lo < hi) { uint64_t mid = (lo + hi) >> 1; if (ovf_key[mid] < (uint32_t)r) lo = mid + 1; else hi = mid; }
-		olo = lo;
-	}
-	for (uint32_t a = 0; a < n; ++a) {
-		OutMem ma = mem_at(src, cap, ovf, ovf_idx, olo, a);
-		uint32_t rank = 0;
-		for (uint32_t b = 0; b < n; ++b) { uint64_t kb = mem_at(src, cap, ovf, ovf_idx, olo, b).info; rank += (kb < ma.info) || (kb == ma.info && b < a); }
-		dst[rank] = ma; dsc[rank] = ma.x2 < max_occ ? ma.x2 : max_occ;
-	}
-}
 // The reads sort_compact16_kernel leaves out (more than 64 mems, or mems beyond `cap`: tandem arrays, repeats): one WAVE per
 // read.  A wave owns 64 consecutive reads, finds the heavy ones by ballot and rank-sorts each with all 64 lanes: lane j
 // owns mems j, j+64, ...; the keys of 64 mems at a time sit in registers and travel by shuffle.  (One lane per read made
@@ -1845,7 +1784,7 @@ __global__ __launch_bounds__(256) void sort_compact_wave_kernel(const OutMem *ra
 // Fast form of the same for the bulk: 16 lanes per read (4 reads per wave).  Up to 16 mems: lane a owns mem a; 17..64 mems
 // (repeat-rich reads): lane a owns mems a, a+16, a+32, a+48.  Each mem is read once (coalesced: 16 lanes x 32 B contiguous),
 // keys travel by shuffle, and every lane writes its mems at their ranks.  Reads with more than 64 mems, or whose mems
-// spilled beyond `cap`, are left to sort_compact2_kernel (launched over the same range with skip_upto = 64).
+// spilled beyond `cap`, are left to sort_compact_wave_kernel.
 __global__ __launch_bounds__(256) void sort_compact16_kernel(const OutMem *raw, const uint32_t *cnt, uint32_t cap, const uint64_t *mem_off,
                                                              int64_t n_reads, OutMem *mems, uint64_t *salcnt, uint32_t max_occ)
 {
