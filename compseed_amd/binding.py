@@ -13,6 +13,7 @@ SEED_DT = np.dtype([("rbeg", "<i8"), ("qbeg", "<i4"), ("len", "<i4")])          
 SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", "cs_index_view", "cs_index_free", "cs_index_build",
            "cs_index_build_flags", "cs_index_save", "cs_refseq_from_fasta", "cs_refseq_codes", "cs_refseq_save", "cs_refseq_free", "cs_index_build_fasta", "cs_reader_open", "cs_reader_next", "cs_reader_close",
            "cs_chainer_create", "cs_chainer_destroy", "cs_chain_params_default", "cs_chain_batch", "cs_flt_params_default", "cs_chain_filter",
+           "cs_chainer_create_device", "cs_chain_batch_device", "cs_chain_batch_gpu", "cs_chainer_stats",
            "cs_device_count", "cs_engine_options_default", "cs_engine_create", "cs_engine_create_opts", "cs_engine_destroy", "cs_engine_seed_batch",
            "cs_engine_seed_batch_device", "cs_engine_submit_device", "cs_engine_collect_device", "cs_engine_seed_batch_packed", "cs_engine_submit", "cs_engine_collect_packed", "cs_unpack_mem", "cs_mem_seed_count", "cs_host_alloc", "cs_host_free", "cs_pack_reads",
            "cs_engine_result_digest", "cs_engine_gather_reads", "cs_engine_traffic_model", "cs_engine_stats", "cs_engine_reset_stats", "cs_engine_occ4",
@@ -177,6 +178,13 @@ class IndexCheck(C.Structure):
                                           "text_violations")] + [("text_checked", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ChainStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "seeds", "chains", "tree_reads", "launches")] + [("kernel_ms", C.c_double)]
+
+
+CHAIN_TREE_ONLY = 1   # CS_CHAIN_TREE_ONLY: every read through the B-tree path of the device chainer (A/B switch, same results)
+
+
 class ExtStats(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("cells", C.c_uint64), ("rows", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
 
@@ -295,6 +303,10 @@ def load_library():
     L.cs_chain_params_default.argtypes = [C.POINTER(ChainParams)]
     L.cs_chain_params_default.restype = None
     L.cs_chain_batch.argtypes = [vp, C.POINTER(ChainParams), C.POINTER(CResult), vp, C.c_int, C.POINTER(CChainResult)]
+    L.cs_chainer_create_device.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
+    L.cs_chain_batch_device.argtypes = [vp, C.POINTER(ChainParams), C.POINTER(CResult), vp, C.c_uint32, C.POINTER(CChainResult)]
+    L.cs_chain_batch_gpu.argtypes = [vp, C.POINTER(ChainParams), C.POINTER(CResult), vp, C.c_uint32, C.POINTER(CChainResult)]
+    L.cs_chainer_stats.argtypes = [vp, C.POINTER(ChainStats)]
     L.cs_flt_params_default.argtypes = [C.POINTER(FltParams)]
     L.cs_flt_params_default.restype = None
     L.cs_chain_filter.argtypes = [vp, C.POINTER(FltParams), C.POINTER(CChainResult), vp, vp, C.c_int, C.POINTER(CChainResult), C.POINTER(vp)]
@@ -488,23 +500,63 @@ class Reader:
 
 
 class Chainer:
-    """mem_chain over a batch's seeds (cs_chainer_t); needs <prefix>.ann"""
+    """mem_chain over a batch's seeds (cs_chainer_t); needs <prefix>.ann.  With a device (cs_chainer_create_device) the chainer also
+    chains on that GPU: chain_gpu() from host arrays, chain_device() from an on-device Result."""
 
-    def __init__(self, prefix):
+    def __init__(self, prefix, device=None):
         self._h = C.c_void_p()
-        _check(load_library().cs_chainer_create(os.fsencode(prefix), C.byref(self._h)))
+        self.device = device
+        if device is None:
+            _check(load_library().cs_chainer_create(os.fsencode(prefix), C.byref(self._h)))
+        else:
+            _check(load_library().cs_chainer_create_device(os.fsencode(prefix), int(device), C.byref(self._h)))
 
-    def chain(self, mem_off, mems, seed_off, seeds, read_offsets, params=None, threads=4, copy=True):
-        """host CSR seeds (numpy arrays as Result holds them) -> dict(chain_off, chains (CHAIN_DT), cseed_off, cseeds (SEED_DT)), copies"""
-        params = params or ChainParams()
+    @staticmethod
+    def _host_in(mem_off, mems, seed_off, seeds, read_offsets):
         mem_off = np.ascontiguousarray(mem_off, dtype=np.uint64); seed_off = np.ascontiguousarray(seed_off, dtype=np.uint64)
         mems = np.ascontiguousarray(mems, dtype=INTV_DT); seeds = np.ascontiguousarray(seeds, dtype=SEED_DT)
         ro = np.ascontiguousarray(read_offsets, dtype=np.uint64)
         res = CResult(mem_off.size - 1, mems.size, seeds.size, mem_off.ctypes.data, mems.ctypes.data, seed_off.ctypes.data, seeds.ctypes.data)
-        out = CChainResult()
-        _check(load_library().cs_chain_batch(self._h, C.byref(params), C.byref(res), ro.ctypes.data, int(threads), C.byref(out)))
+        return res, ro, (mem_off, mems, seed_off, seeds)
+
+    @staticmethod
+    def _host_out(out, copy):
         return dict(chain_off=_view(out.chain_off, "<u8", int(out.n_reads) + 1, copy), chains=_view(out.chains, CHAIN_DT, int(out.n_chains), copy),
                     cseed_off=_view(out.cseed_off, "<u8", int(out.n_chains) + 1, copy), cseeds=_view(out.cseeds, SEED_DT, int(out.n_seeds), copy))   # copy=False: views of the chainer's arrays, valid until its next chain()
+
+    def chain(self, mem_off, mems, seed_off, seeds, read_offsets, params=None, threads=4, copy=True):
+        """host CSR seeds (numpy arrays as Result holds them) -> dict(chain_off, chains (CHAIN_DT), cseed_off, cseeds (SEED_DT)), copies"""
+        params = params or ChainParams()
+        res, ro, _keep = self._host_in(mem_off, mems, seed_off, seeds, read_offsets)
+        out = CChainResult()
+        _check(load_library().cs_chain_batch(self._h, C.byref(params), C.byref(res), ro.ctypes.data, int(threads), C.byref(out)))
+        return self._host_out(out, copy)
+
+    def chain_gpu(self, mem_off, mems, seed_off, seeds, read_offsets, params=None, flags=0, copy=True):
+        """cs_chain_batch_gpu: chain()'s arguments and result, the work done on the chainer's GPU (flags: CHAIN_TREE_ONLY)"""
+        params = params or ChainParams()
+        res, ro, _keep = self._host_in(mem_off, mems, seed_off, seeds, read_offsets)
+        out = CChainResult()
+        _check(load_library().cs_chain_batch_gpu(self._h, C.byref(params), C.byref(res), ro.ctypes.data, int(flags), C.byref(out)))
+        return self._host_out(out, copy)
+
+    def chain_device(self, result, d_read_offsets, params=None, flags=0):
+        """cs_chain_batch_device: an on-device Result (Engine.seed_batch_device / collect_device) and the batch's offsets in device memory ->
+        dict(n_reads, n_chains, n_seeds, chain_off, chains, cseed_off, cseeds): host counts and device pointers owned by the chainer, valid
+        until its next chain call (download_chains() turns them into chain()'s dict)"""
+        params = params or ChainParams()
+        p = result.ptr
+        res = CResult(result.n_reads, result.n_mems, result.n_seeds, p["mem_off"], p["mems"], p["seed_off"], p["seeds"])
+        out = CChainResult()
+        _check(load_library().cs_chain_batch_device(self._h, C.byref(params), C.byref(res), C.c_void_p(d_read_offsets), int(flags), C.byref(out)))
+        return dict(n_reads=int(out.n_reads), n_chains=int(out.n_chains), n_seeds=int(out.n_seeds), chain_off=out.chain_off, chains=out.chains,
+                    cseed_off=out.cseed_off, cseeds=out.cseeds)
+
+    def stats(self):
+        """cs_chainer_stats: counters of the device calls over the chainer's life"""
+        st = ChainStats()
+        _check(load_library().cs_chainer_stats(self._h, C.byref(st)))
+        return {n: (float(getattr(st, n)) if n == "kernel_ms" else int(getattr(st, n))) for n, _ in ChainStats._fields_}
 
     def filter(self, chain_off, chains, cseed_off, cseeds, bases, read_offsets, params=None, threads=4, copy=True):
         """cs_chain_filter (mem_chain_flt + mem_flt_chained_seeds): chains as chain() returns them -> the same dict for the surviving
@@ -533,6 +585,14 @@ class Chainer:
             self.close()
         except Exception:
             pass
+
+
+def download_chains(engine, d):
+    """Chainer.chain_device's result -> chain()'s dict of host arrays, through an Engine on the same GPU"""
+    def get(ptr, dt, n):
+        return engine.download(ptr, dt, n) if n else np.zeros(0, dtype=dt)
+    return dict(chain_off=get(d["chain_off"], np.uint64, d["n_reads"] + 1), chains=get(d["chains"], CHAIN_DT, d["n_chains"]),
+                cseed_off=get(d["cseed_off"], np.uint64, d["n_chains"] + 1), cseeds=get(d["cseeds"], SEED_DT, d["n_seeds"]))
 
 
 def build_index_from_fasta(fasta, prefix, device=0):

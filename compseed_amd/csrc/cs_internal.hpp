@@ -26,8 +26,13 @@ inline uint8_t cs_base_code_(uint8_t c)
 	switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; case '-': return 5; default: return 4; }
 }
 
+// the device side of a chainer (chain_gpu.hip: cs_chain_batch_device / cs_chain_batch_gpu)
+struct cs_chainer_gpu;
+void cs_chainer_gpu_release_(cs_chainer_gpu *g);
+
 // the chainer (chain.cpp: cs_chain_batch; chain_filter.cpp: cs_chain_filter)
 struct cs_chainer {
+	cs_chainer_gpu *gpu = nullptr;                                                                                                       // cs_chainer_create_device only
 	cs_refseq_view ref; std::string prefix;
 	std::vector<cs_chain_t> chains; std::vector<uint64_t> chain_off, cseed_off; std::vector<cs_seed_t> cseeds;                          // cs_chain_batch's result
 	std::vector<uint8_t> pac;                                                                                                            // loaded when cs_chain_filter first needs it

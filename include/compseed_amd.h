@@ -305,6 +305,25 @@ void cs_chainer_destroy(cs_chainer_t *c);
 void cs_chain_params_default(cs_chain_params_t *p);
 int  cs_chain_batch(cs_chainer_t *c, const cs_chain_params_t *par, const cs_result_t *seeds, const uint64_t *read_offsets, int n_threads,
                     cs_chain_result_t *out);
+/* The same pass on the GPU, bit-identical to cs_chain_batch (which stays the specification).  cs_chainer_create_device gives a chainer that
+ * still does everything a host chainer does and also holds device state on `device`: the contig offsets and ALT flags, uploaded once, and a
+ * stream and buffers of its own (CS_EDEVICE without a GPU).  cs_chain_batch_device: `d_seeds` is a result as the engine's device variants
+ * return it (device pointers on the chainer's GPU, host counts) and `d_read_offsets` the batch's offsets in device memory; inputs must be
+ * COMPLETE when the call is made, as for cs_engine_seed_batch_device, and the results are complete when it returns.  The output CSR arrays
+ * are device pointers owned by the chainer, valid until its next chain call; the counts are host values.  A result of
+ * cs_engine_collect_device is to be chained before the next cs_engine_submit_device.  cs_chain_batch_gpu: the same work from host arrays to
+ * host arrays (owned by the chainer, as cs_chain_batch's), byte for byte cs_chain_batch's result.  Both return CS_EINVAL for a result
+ * without seeds (want_sal = 0) and for a chainer made by cs_chainer_create; n_reads == 0 gives an empty result.  cs_chainer_stats: counters
+ * of the device calls over the chainer's life (zero for a host chainer). */
+#define CS_CHAIN_TREE_ONLY 1u   /* A/B switch: every read through the exact B-tree path instead of the sorted-array fast path; same results */
+typedef struct { uint64_t reads, seeds, chains, tree_reads, launches; double kernel_ms; } cs_chain_stats_t;   /* tree_reads: reads that went
+                                                                                                                   * the B-tree path; kernel_ms: HIP-event time of the kernels */
+int  cs_chainer_create_device(const char *prefix, int device, cs_chainer_t **out);
+int  cs_chain_batch_device(cs_chainer_t *c, const cs_chain_params_t *par, const cs_result_t *d_seeds, const uint64_t *d_read_offsets, uint32_t flags,
+                           cs_chain_result_t *d_out);
+int  cs_chain_batch_gpu(cs_chainer_t *c, const cs_chain_params_t *par, const cs_result_t *seeds, const uint64_t *read_offsets, uint32_t flags,
+                        cs_chain_result_t *out);
+int  cs_chainer_stats(const cs_chainer_t *c, cs_chain_stats_t *st);
 
 /* ---- the chain filters between chaining and extension (comp_seed.cpp:2364-2367), host code: mem_chain_flt (comp_seed.cpp:297-360: chains
  *      by descending weight -- klib's introsort, whose order among equal weights is reproduced --, chains shadowed on the read by a much

@@ -1,6 +1,8 @@
 """tools/align_bench.py -- the stages behind seeding at a size where their speed shows: N reads of 150 bases sampled from the golden
 reference (tests/golden/g1, 220 kbp: every read has a true locus, many have repeats) with substitutions and short indels, through
-GPU seeding -> cs_chain_batch -> cs_chain_filter -> cs_extend_chains -> cs_dedup_regions; wall time and reads/s per stage.
+GPU seeding -> cs_chain_batch -> cs_chain_filter -> cs_extend_chains -> cs_dedup_regions; wall time and reads/s per stage.  Beside the host
+chain row: the device chainer on the same reads, cs_chain_batch_gpu (host arrays) and cs_chain_batch_device (on a second, device-resident
+seeding of the batch), both checked equal to the host chains over the whole batch.
 usage: align_bench.py [reads] [--synth-mbp M]"""
 import gzip, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,7 +59,12 @@ def run(n=200000, synth_mbp=0.0):
         reads[rc] = comp[reads[rc]][:, ::-1]
         bases = np.ascontiguousarray(reads.reshape(-1)); off = (np.arange(n + 1, dtype=np.uint64) * np.uint64(L))
     ix = ca.Index.load(PREFIX); eng = ca.Engine(ix, 0); ch = ca.Chainer(PREFIX); al = ca.Aligner(PREFIX, 0)
+    chd = ca.Chainer(PREFIX, device=0)   # the device chainer (cs_chain_batch_device / cs_chain_batch_gpu)
+    d_b, d_o = eng.alloc(bases.nbytes), eng.alloc(off.nbytes)
+    eng.upload(d_b, bases); eng.upload(d_o, off); eng.sync()
     out = {"reads": n, "reference": ("synthetic %g Mbp" % synth_mbp) if synth_mbp > 0 else "tests/golden/g1 (220 kbp, tandem arrays)"}
+    def same(a, b):
+        return all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in ("chain_off", "chains", "cseed_off", "cseeds"))
     for rep in range(2):   # the second round is the measured one (buffers sized)
         t0 = time.perf_counter(); res = eng.seed_batch(bases, off, ca.Params(), copy=False); t1 = time.perf_counter()
         c = ch.chain(res.mem_off, res.mems, res.seed_off, res.seeds, off, ca.ChainParams(), threads=16, copy=False); t2 = time.perf_counter()
@@ -66,8 +73,18 @@ def run(n=200000, synth_mbp=0.0):
         g = al.extend_chains(f["chain_off"], f["chains"], f["cseed_off"], f["cseeds"], bases, off, cseed_score=f["cseed_score"], copy=False); t4 = time.perf_counter()
         st1 = al.stats()
         d = al.dedup_regions(g["reg_off"], g["regs"], bases, off, copy=False); t5 = time.perf_counter()
+        # the chain pass on the GPU: host arrays in and out (PCIe both ways), then from the engine's device result (seeded once more)
+        t6 = time.perf_counter(); cg = chd.chain_gpu(res.mem_off, res.mems, res.seed_off, res.seeds, off, ca.ChainParams(), copy=False); t7 = time.perf_counter()
+        assert same(cg, c), "cs_chain_batch_gpu differs from cs_chain_batch"
+        rd = eng.seed_batch_device(d_b, d_o, n, bases.size, ca.Params())
+        sd0 = chd.stats(); t8 = time.perf_counter(); dd = chd.chain_device(rd, d_o, ca.ChainParams()); t9 = time.perf_counter(); sd1 = chd.stats()
+        assert same(ca.download_chains(eng, dd), c), "cs_chain_batch_device differs from cs_chain_batch"
     for name, a, b in (("seed (host call)", t0, t1), ("chain", t1, t2), ("chain_filter", t2, t3), ("extend_chains", t3, t4), ("dedup_regions", t4, t5)):
         out[name] = {"ms": 1e3 * (b - a), "reads_per_s": n / (b - a)}
+    kms = sd1["kernel_ms"] - sd0["kernel_ms"]
+    out["chain_device"] = {"ms": 1e3 * (t9 - t8), "reads_per_s": n / (t9 - t8), "kernel_ms": kms, "kernel_reads_per_s": n / (kms * 1e-3) if kms > 0 else None,
+                           "tree_reads": sd1["tree_reads"] - sd0["tree_reads"], "launches": sd1["launches"] - sd0["launches"], "equal_to_host_chains": True}
+    out["chain_gpu"] = {"ms": 1e3 * (t7 - t6), "reads_per_s": n / (t7 - t6), "equal_to_host_chains": True, "note": "host arrays in and out: PCIe-bound"}
     out["counts"] = {"seeds": int(res.n_seeds), "chains": int(c["chains"].size), "chains_after_filter": int(f["chains"].size), "regions": int(g["regs"].size),
                      "regions_after_dedup": int(d["regs"].size), "extensions": int(st1["pairs"] - st0["pairs"]), "ext_launches": int(st1["launches"] - st0["launches"])}
     per_read = np.diff(np.asarray(g["reg_off"]).astype(np.int64))
@@ -81,7 +98,8 @@ def run(n=200000, synth_mbp=0.0):
     out["behind_seeding_reads_per_s"] = n / (t_all * 1e-3)
     if tmpdir:
         shutil.rmtree(tmpdir, ignore_errors=True)
-    for x in (al, ch, eng, ix):
+    eng.free(d_b); eng.free(d_o)
+    for x in (al, chd, ch, eng, ix):
         x.close()
     return out
 
