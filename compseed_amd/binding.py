@@ -20,7 +20,7 @@ SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", 
            "cs_engine_extend", "cs_engine_sa", "cs_engine_probe_random_lines", "cs_device_alloc", "cs_device_free", "cs_device_upload",
            "cs_device_download", "cs_device_sync", "cs_packed_seed_rbeg", "cs_engine_check_index",
            "cs_ext_params_default", "cs_extender_create", "cs_extender_destroy", "cs_extend_batch", "cs_extend_batch_device", "cs_extender_stats",
-           "cs_extender_upload", "cs_extend_batch_resident", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats"]
+           "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats"]
 
 
 class CSError(RuntimeError):
@@ -61,7 +61,7 @@ class EngineOptions(C.Structure):
                 ("jump_k", C.c_int32), ("kmer_filter", C.c_int32), ("fused", C.c_int32), ("mem_cap", C.c_int32),
                 ("lep_arena_mb", C.c_int64), ("max_raw_mb", C.c_int64), ("r3_text_iter", C.c_int32),
                 ("pipeline_reads", C.c_int32), ("expand_threads", C.c_int32),
-                ("count_sal_merged", C.c_int32), ("verbose", C.c_int32), ("host_pack_threads", C.c_int32), ("passes_in_flight", C.c_int32), ("reserved", C.c_int32 * 3)]
+                ("count_sal_merged", C.c_int32), ("verbose", C.c_int32), ("host_pack_threads", C.c_int32), ("passes_in_flight", C.c_int32), ("sa40", C.c_int32), ("reserved", C.c_int32 * 2)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -218,6 +218,12 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Memory(C.Structure):
+    """cs_memory_t: device bytes the engine holds, by group (cs_engine_memory)"""
+    _fields_ = [(n, C.c_uint64) for n in ("occ_bwt", "sampled_sa", "full_sa", "isa", "text", "lcp_rep", "jump_table", "kmer_filter")] + \
+               [("pass_ctx", C.c_uint64 * 2), ("total", C.c_uint64), ("sa_entry_bits", C.c_int32), ("n_pass_ctx", C.c_int32)]
+
+
 KERNELS = ["fwd0_kernel", "fwd_kernel", "bwd_win_kernel", "bwd_win0_kernel", "bwd_wide_kernel", "bwd_all_kernel", "r2text_kernel",
            "r3text_kernel", "smem_kernel"]
 EVENTS = ["occ_record", "jump_entry", "filter_word", "sa_entry", "isa_entry", "text_word", "rep_load", "lcp_byte", "lep_entry", "mem_record"]
@@ -329,6 +335,7 @@ def load_library():
     L.cs_host_free.argtypes = [vp]
     L.cs_engine_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cs_engine_reset_stats.argtypes = [vp]
+    L.cs_engine_memory.argtypes = [vp, C.POINTER(Memory)]
     L.cs_engine_reset_stats.restype = None
     L.cs_engine_occ4.argtypes = [vp, i64, vp, vp]
     L.cs_engine_extend.argtypes = [vp, i64, vp, vp, vp]
@@ -660,7 +667,7 @@ class Engine:
     """One GPU, one resident index (cs_engine_t)."""
 
     def __init__(self, index, device=0, **options):
-        """options: fields of cs_engine_options_t (full_sa, sa64, text_mode, text_arrays, jump_k, kmer_filter, fused, mem_cap,
+        """options: fields of cs_engine_options_t (full_sa, sa64, sa40, text_mode, text_arrays, jump_k, kmer_filter, fused, mem_cap,
         lep_arena_mb, max_raw_mb, r3_text_iter, count_sal_merged, verbose)"""
         self._L = load_library()
         self._h = C.c_void_p()
@@ -792,6 +799,15 @@ class Engine:
 
     def reset_stats(self):
         self._L.cs_engine_reset_stats(self._h)
+
+    def memory(self):
+        """cs_engine_memory: device bytes held, by group: {"occ_bwt", "sampled_sa", "full_sa", "isa", "text", "lcp_rep", "jump_table",
+        "kmer_filter", "pass_ctx": [ctx0, ctx1], "total", "sa_entry_bits": 32 | 40 | 64 | 0, "n_pass_ctx"}; host-only, legal while batches are in flight"""
+        m = Memory()
+        _check(self._L.cs_engine_memory(self._h, C.byref(m)))
+        d = {n: int(getattr(m, n)) for n, _ in Memory._fields_ if n != "pass_ctx"}
+        d["pass_ctx"] = [int(x) for x in m.pass_ctx]
+        return d
 
     # ---- primitives (parity tests of the building blocks)
     def occ4(self, k):

@@ -24,7 +24,7 @@ extern "C" void cs_engine_options_default(cs_engine_options_t *o)
 {
 	if (!o) return;
 	memset(o, 0, sizeof *o);
-	o->full_sa = 1; o->sa64 = 0; o->text_mode = 1; o->text_arrays = 1; o->jump_k = 15; o->kmer_filter = 1; o->fused = 0;
+	o->full_sa = 1; o->sa64 = 0; o->sa40 = 0; o->text_mode = 1; o->text_arrays = 1; o->jump_k = 15; o->kmer_filter = 1; o->fused = 0;
 	o->mem_cap = 64; o->lep_arena_mb = 16384; o->max_raw_mb = 24576; o->r3_text_iter = 5; o->count_sal_merged = 0; o->verbose = 0;
 	o->pipeline_reads = 5000000; o->expand_threads = 16; o->host_pack_threads = 8; o->passes_in_flight = 2;
 }
@@ -122,12 +122,13 @@ __global__ void relayout_kernel(uint4 *bwt, uint64_t n_blocks, unsigned long lon
 }
 
 // one-time preparation of the text-mode arrays from the full suffix array: T[SA[r] - 1] is the BWT character of row r
-template <typename T>
-__global__ void text_isa_fill_kernel(const DevIndex ix, const T *fsa, uint8_t *tbytes, T *isa)
+// (the suffix array and its inverse come as Plain<u32>, Plain<u64> or Pack40, fm_device.hpp: get / put by entry)
+template <typename A>
+__global__ void text_isa_fill_kernel(const DevIndex ix, const A fsa, uint8_t *tbytes, const A isa)
 {
 	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= ix.seq_len; r += (uint64_t)gridDim.x * blockDim.x) {
-		uint64_t s = (uint64_t)fsa[r];
-		isa[s] = (T)r;
+		uint64_t s = fsa.get(r);
+		isa.put(s, r);
 		if (r == ix.primary) continue; // the row of the whole text: its BWT character is the sentinel
 		uint64_t row = r - (r > ix.primary);
 		Block b = load_block(ix, row >> OCC_SHIFT);
@@ -146,37 +147,37 @@ __global__ void text_pack_kernel(const uint8_t *tbytes, uint64_t n, uint32_t *te
 	}
 }
 
-template <typename T>
-__global__ void lcp_fill_kernel(const DevIndex ix, const T *fsa, uint8_t *lcp)
+template <typename A>
+__global__ void lcp_fill_kernel(const DevIndex ix, const A fsa, uint8_t *lcp)
 {
 	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= ix.seq_len + 1; r += (uint64_t)gridDim.x * blockDim.x)
-		lcp[r] = (r == 0 || r > ix.seq_len) ? 0 : (uint8_t)text_lcp(ix, (uint64_t)fsa[r - 1], (uint64_t)fsa[r], 255u);
+		lcp[r] = (r == 0 || r > ix.seq_len) ? 0 : (uint8_t)text_lcp(ix, fsa.get(r - 1), fsa.get(r), 255u);
 }
-template <typename T>
-__global__ void rep_fill_kernel(const DevIndex ix, const T *fsa, const uint8_t *lcp, uint8_t *rep)
+template <typename A>
+__global__ void rep_fill_kernel(const DevIndex ix, const A fsa, const uint8_t *lcp, uint8_t *rep)
 {
 	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= ix.seq_len; r += (uint64_t)gridDim.x * blockDim.x) {
 		uint8_t a = lcp[r], b = lcp[r + 1];
-		rep[(uint64_t)fsa[r]] = a > b ? a : b; // row 0 (the empty suffix) writes rep[seq_len] = 0
+		rep[fsa.get(r)] = a > b ? a : b; // row 0 (the empty suffix) writes rep[seq_len] = 0
 	}
 }
 
 // Materialise SA[row] for every row from the 1-in-sa_intv samples: lane t starts at sampled row t*sa_intv, whose value is
 // known, and follows bwt_invPsi (one text position back per step, bwt.c:53-59) writing SA = value - steps until it
 // reaches the next sampled row.  Every row lies on exactly one such chain, so all seq_len+1 rows get written once.
-template <typename T>
-__global__ void sa_fill_kernel(const DevIndex ix, T *full)
+template <typename A>
+__global__ void sa_fill_kernel(const DevIndex ix, const A full)
 {
 	uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= ix.n_sa) return;
 	uint64_t k = t << ix.sa_shift;
 	uint64_t s = (t == 0) ? ix.seq_len : ix.sa[t]; // row 0 is the "$" suffix at text position seq_len
-	full[k] = (T)s;
+	full.put(k, s);
 	for (;;) {
 		k = inv_psi(ix, k);
 		if ((k & ix.sa_mask) == 0) break;
 		--s;
-		full[k] = (T)s;
+		full.put(k, s);
 	}
 }
 
@@ -236,6 +237,7 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 
 	if (v->seq_len == 0 || v->seq_len != v->L2[4] || v->L2[0] != 0) return fail(CS_EINVAL, "index view: L2 / seq_len inconsistent");
 	if (v->seq_len >> 37) return fail(CS_ERANGE, "index longer than 2^37 symbols does not fit the packed LEP entries");
+	if (opt.sa40 && (v->seq_len + 1) >> 40) return fail(CS_ERANGE, "sa40: 2^40 rows or more do not fit 40-bit suffix-array entries");
 	if (v->primary > v->seq_len) return fail(CS_EINVAL, "index view: primary out of range");
 	uint64_t n_blocks = (v->seq_len + 127) >> 7;
 	// the file holds one extra count record after the last block (bwt_bwtupdate_core, index_main.c:152-174)
@@ -269,24 +271,31 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 	ix.sa_shift = (uint32_t)__builtin_ctzll(v->sa_intv);
 
 	if (verbose) { fprintf(stderr, "[cs_engine] index uploaded and re-laid out\n"); fflush(stderr); }
-	// full suffix array in HBM (4 B/row below 2^32 rows, else 8 B/row): 50 GB for hg19 of the 288 GB on board
-	ix.fsa32 = nullptr; ix.fsa64 = nullptr;
+	// full suffix array in HBM (4 B/row below 2^32 rows, else 8 B/row: 50 GB for hg19 of the 288 GB on board; 40-bit entries, 5.33 B/row,
+	// with engine option sa40: 33 GB)
+	ix.fsa32 = nullptr; ix.fsa64 = nullptr; ix.fsa40 = nullptr;
+	const uint64_t rows = v->seq_len + 1;
+	const bool pack40 = opt.sa40 != 0;
+	const bool small = !pack40 && rows < 0xffffffffull && !opt.sa64; // sa64: 8-byte entries on a small index (tests of the hg19-scale instantiation)
+	const size_t sa_bytes = pack40 ? pack40_groups(rows) * sizeof(uint4) : (size_t)rows * (small ? 4 : 8); // of the full SA, and of its inverse
 	if (opt.full_sa) {
-		uint64_t rows = v->seq_len + 1;
 		size_t free_b = 0, total_b = 0;
 		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-		bool small = rows < 0xffffffffull && !opt.sa64; // sa64: 8-byte entries on a small index (tests of the hg19-scale instantiation)
-		size_t need = (size_t)rows * (small ? 4 : 8);
-		if (need + ((size_t)8 << 30) < free_b) {
+		if (sa_bytes + ((size_t)8 << 30) < free_b) {
 			unsigned grid = (unsigned)((v->n_sa + 255) / 256);
-			if (small) {
+			if (pack40) {
+				CS_TRY(e->d_fsa40.reserve(pack40_groups(rows) + 4));
+				hipLaunchKernelGGL(sa_fill_kernel<Pack40>, dim3(grid), dim3(256), 0, c.stream, ix, Pack40{e->d_fsa40.p});
+				HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(c.stream));
+				ix.fsa40 = e->d_fsa40.p;
+			} else if (small) {
 				CS_TRY(e->d_fsa32.reserve((size_t)rows + 16));
-				hipLaunchKernelGGL(sa_fill_kernel<uint32_t>, dim3(grid), dim3(256), 0, c.stream, ix, e->d_fsa32.p);
+				hipLaunchKernelGGL(sa_fill_kernel<Plain<uint32_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint32_t>{e->d_fsa32.p});
 				HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(c.stream));
 				ix.fsa32 = e->d_fsa32.p;
 			} else {
 				CS_TRY(e->d_fsa64.reserve((size_t)rows + 16));
-				hipLaunchKernelGGL(sa_fill_kernel<uint64_t>, dim3(grid), dim3(256), 0, c.stream, ix, e->d_fsa64.p);
+				hipLaunchKernelGGL(sa_fill_kernel<Plain<uint64_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint64_t>{e->d_fsa64.p});
 				HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(c.stream));
 				ix.fsa64 = e->d_fsa64.p;
 			}
@@ -294,27 +303,29 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 	}
 
 	// text mode (smem_split.hpp): the 2-bit text and the inverse suffix array, derived from the full suffix array
-	ix.text2 = nullptr; ix.isa32 = nullptr; ix.isa64 = nullptr;
+	ix.text2 = nullptr; ix.isa32 = nullptr; ix.isa64 = nullptr; ix.isa40 = nullptr;
 	{
 		size_t free_b = 0, total_b = 0;
 		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-		uint64_t rows = v->seq_len + 1;
-		size_t need = (size_t)rows * (ix.fsa32 ? 4 : 8) + (size_t)v->seq_len + (size_t)v->seq_len / 4 + ((size_t)24 << 30);
-		if (opt.text_mode && (ix.fsa32 || ix.fsa64) && need < free_b) {
+		size_t need = sa_bytes + (size_t)v->seq_len + (size_t)v->seq_len / 4 + ((size_t)24 << 30);
+		if (opt.text_mode && has_full_sa(ix) && need < free_b) {
 			DevBuf<uint8_t> tbytes;
 			CS_TRY(tbytes.reserve((size_t)v->seq_len + 64));
 			CS_TRY(e->d_text2.reserve((size_t)((v->seq_len + 15) >> 4) + 16));
 			unsigned grid = (unsigned)std::min<uint64_t>((rows + 255) / 256, 1u << 22);
-			if (ix.fsa32) {
+			if (ix.fsa40) {
+				CS_TRY(e->d_isa40.reserve(pack40_groups(rows) + 4));
+				hipLaunchKernelGGL(text_isa_fill_kernel<Pack40>, dim3(grid), dim3(256), 0, c.stream, ix, Pack40{e->d_fsa40.p}, tbytes.p, Pack40{e->d_isa40.p});
+			} else if (ix.fsa32) {
 				CS_TRY(e->d_isa32.reserve((size_t)rows + 16));
-				hipLaunchKernelGGL(text_isa_fill_kernel<uint32_t>, dim3(grid), dim3(256), 0, c.stream, ix, ix.fsa32, tbytes.p, e->d_isa32.p);
+				hipLaunchKernelGGL(text_isa_fill_kernel<Plain<uint32_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint32_t>{e->d_fsa32.p}, tbytes.p, Plain<uint32_t>{e->d_isa32.p});
 			} else {
 				CS_TRY(e->d_isa64.reserve((size_t)rows + 16));
-				hipLaunchKernelGGL(text_isa_fill_kernel<uint64_t>, dim3(grid), dim3(256), 0, c.stream, ix, ix.fsa64, tbytes.p, e->d_isa64.p);
+				hipLaunchKernelGGL(text_isa_fill_kernel<Plain<uint64_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint64_t>{e->d_fsa64.p}, tbytes.p, Plain<uint64_t>{e->d_isa64.p});
 			}
 			hipLaunchKernelGGL(text_pack_kernel, dim3(grid), dim3(256), 0, c.stream, tbytes.p, v->seq_len, e->d_text2.p);
 			HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(c.stream));
-			ix.text2 = e->d_text2.p; ix.isa32 = e->d_isa32.p; ix.isa64 = e->d_isa64.p;
+			ix.text2 = e->d_text2.p; ix.isa32 = e->d_isa32.p; ix.isa64 = e->d_isa64.p; ix.isa40 = e->d_isa40.p;
 		}
 		if (verbose) { fprintf(stderr, "[cs_engine] text mode: %s\n", ix.text2 ? "on" : "off"); fflush(stderr); }
 	}
@@ -325,15 +336,17 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
 		size_t need = (size_t)v->seq_len * 2 + ((size_t)24 << 30);
 		if (opt.text_arrays && ix.text2 && need < free_b) {
-			uint64_t rows = v->seq_len + 1;
 			CS_TRY(e->d_lcp.reserve((size_t)rows + 64)); CS_TRY(e->d_rep.reserve((size_t)rows + 64));
 			unsigned grid = (unsigned)std::min<uint64_t>((rows + 256) / 256, 1u << 22);
-			if (ix.fsa32) {
-				hipLaunchKernelGGL(lcp_fill_kernel<uint32_t>, dim3(grid), dim3(256), 0, c.stream, ix, ix.fsa32, e->d_lcp.p);
-				hipLaunchKernelGGL(rep_fill_kernel<uint32_t>, dim3(grid), dim3(256), 0, c.stream, ix, ix.fsa32, (const uint8_t *)e->d_lcp.p, e->d_rep.p);
+			if (ix.fsa40) {
+				hipLaunchKernelGGL(lcp_fill_kernel<Pack40>, dim3(grid), dim3(256), 0, c.stream, ix, Pack40{e->d_fsa40.p}, e->d_lcp.p);
+				hipLaunchKernelGGL(rep_fill_kernel<Pack40>, dim3(grid), dim3(256), 0, c.stream, ix, Pack40{e->d_fsa40.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p);
+			} else if (ix.fsa32) {
+				hipLaunchKernelGGL(lcp_fill_kernel<Plain<uint32_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint32_t>{e->d_fsa32.p}, e->d_lcp.p);
+				hipLaunchKernelGGL(rep_fill_kernel<Plain<uint32_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint32_t>{e->d_fsa32.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p);
 			} else {
-				hipLaunchKernelGGL(lcp_fill_kernel<uint64_t>, dim3(grid), dim3(256), 0, c.stream, ix, ix.fsa64, e->d_lcp.p);
-				hipLaunchKernelGGL(rep_fill_kernel<uint64_t>, dim3(grid), dim3(256), 0, c.stream, ix, ix.fsa64, (const uint8_t *)e->d_lcp.p, e->d_rep.p);
+				hipLaunchKernelGGL(lcp_fill_kernel<Plain<uint64_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint64_t>{e->d_fsa64.p}, e->d_lcp.p);
+				hipLaunchKernelGGL(rep_fill_kernel<Plain<uint64_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint64_t>{e->d_fsa64.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p);
 			}
 			HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(c.stream));
 			ix.lcp = e->d_lcp.p; ix.rep = e->d_rep.p;
@@ -356,7 +369,7 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 		}
 	}
 	CS_TRY(seed_pass_init(e));
-	if (verbose) { fprintf(stderr, "[cs_engine] full suffix array: %s\n", ix.fsa32 ? "4-byte" : ix.fsa64 ? "8-byte" : "off"); fflush(stderr); }
+	if (verbose) { fprintf(stderr, "[cs_engine] full suffix array: %s\n", ix.fsa32 ? "4-byte" : ix.fsa64 ? "8-byte" : ix.fsa40 ? "5-byte" : "off"); fflush(stderr); }
 	return CS_OK;
 }
 
@@ -404,6 +417,26 @@ extern "C" int cs_engine_stats(const cs_engine_t *e, cs_stats_t *st)
 	}
 	return CS_OK;
 }
+extern "C" int cs_engine_memory(const cs_engine_t *e, cs_memory_t *out)
+{
+	if (!e || !out) return fail(CS_EINVAL, "null argument");
+	memset(out, 0, sizeof *out);
+	auto bytes = [](const auto &b) { return (uint64_t)b.cap * sizeof(*b.p); };
+	// the index-side buffers do not change once the engine exists; the rest comes from counters the passes publish
+	out->occ_bwt = bytes(e->d_bwt); out->sampled_sa = bytes(e->d_sa);
+	out->full_sa = bytes(e->d_fsa32) + bytes(e->d_fsa64) + bytes(e->d_fsa40);
+	out->isa = bytes(e->d_isa32) + bytes(e->d_isa64) + bytes(e->d_isa40);
+	out->text = bytes(e->d_text2); out->lcp_rep = bytes(e->d_lcp) + bytes(e->d_rep); out->jump_table = bytes(e->d_jump);
+	out->kmer_filter = e->bloom_bytes.load(std::memory_order_relaxed);
+	out->total = out->occ_bwt + out->sampled_sa + out->full_sa + out->isa + out->text + out->lcp_rep + out->jump_table + out->kmer_filter;
+	for (int i = 0; i < 2; ++i) {
+		out->pass_ctx[i] = e->ctx_bytes[i].load(std::memory_order_relaxed);
+		out->total += out->pass_ctx[i];
+		if (out->pass_ctx[i]) out->n_pass_ctx = i + 1;
+	}
+	out->sa_entry_bits = e->ix.fsa32 ? 32 : e->ix.fsa64 ? 64 : e->ix.fsa40 ? 40 : 0;
+	return CS_OK;
+}
 extern "C" void cs_engine_reset_stats(cs_engine_t *e)
 {
 	if (!e || pipe_busy(e)) return; // (the seeding thread owns the counters while batches are in flight)
@@ -431,7 +464,7 @@ extern "C" int cs_engine_traffic_model(cs_engine_t *e, cs_traffic_t *out)
 		for (int a = 0; a < N_KID; ++a) for (int b = 0; b < N_EV; ++b) out->events[a][b] += ev[(size_t)a * N_EV + b];
 		stream_bytes += c->stream_bytes;
 	}
-	const uint64_t sa_b = e->ix.fsa64 ? 8 : 4;
+	const uint64_t sa_b = e->ix.fsa64 ? 8 : e->ix.fsa40 ? 5 : 4;
 	const uint64_t eb[N_EV] = {32, 16, 8, sa_b, sa_b, 4, 8, 1, 16, 32};
 	for (int i = 0; i < N_EV; ++i) out->event_bytes[i] = eb[i];
 	out->stream_bytes = stream_bytes;

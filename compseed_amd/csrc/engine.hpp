@@ -9,6 +9,7 @@
 #include "fm_device.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -146,6 +147,17 @@ struct PassCtx {
 	cs_stats_t st{};
 	DevBuf<unsigned long long> d_evc; uint64_t stream_bytes = 0; // byte model: event counters [N_KID][N_EV] on the device, stream part on the host
 	struct { bool valid = false; int64_t n_reads = 0; uint64_t n_mems = 0, n_seeds = 0; int want_sal = 0; } last; // the result held in d_mems / d_seeds
+	int id = 0; // index in cs_engine::ctx
+	// device bytes of every buffer above, as reserved (cs_engine_memory)
+	uint64_t device_bytes() const
+	{
+		uint64_t b = 0;
+		auto add = [&b](const auto &...buf) { ((b += (uint64_t)buf.cap * sizeof(*buf.p)), ...); };
+		add(d_pending, d_cnt_snap, d_auxA, d_auxB, d_seq, d_seqp, d_out, d_out2, d_cnt, d_cnt2, d_ovf, d_spill, d_ctr, d_tmp, d_tmp2);
+		add(d_mem_off, d_seed_off, d_seed_of_mem, d_mems, d_salcnt, d_seeds, d_fqA, d_fqB, d_fqR, d_sst2, d_bq, d_lep, d_ovfrec);
+		add(d_okey, d_oidx, d_okey2, d_oidx2, d_okey64, d_okey64b, d_sctr, d_evc);
+		return b;
+	}
 };
 
 constexpr int PIPE_DEPTH = 4; // batches in flight in the host pipeline (cs_engine_submit): one pinned result slot each
@@ -161,8 +173,8 @@ struct cs_engine {
 	size_t max_raw_bytes = (size_t)24 << 30;
 	DevIndex ix{};
 	DevBuf<uint4> d_bwt; DevBuf<uint64_t> d_sa;
-	DevBuf<uint32_t> d_fsa32; DevBuf<uint64_t> d_fsa64; // full suffix array (one of the two)
-	DevBuf<uint32_t> d_text2, d_isa32; DevBuf<uint64_t> d_isa64; // text mode: 2-bit text + inverse suffix array
+	DevBuf<uint32_t> d_fsa32; DevBuf<uint64_t> d_fsa64; DevBuf<uint4> d_fsa40; // full suffix array (one of the three; d_fsa40: engine option sa40, fm_device.hpp Pack40)
+	DevBuf<uint32_t> d_text2, d_isa32; DevBuf<uint64_t> d_isa64; DevBuf<uint4> d_isa40; // text mode: 2-bit text + inverse suffix array
 	DevBuf<uint8_t> d_lcp, d_rep; // re-seeding from the text: capped LCP by row, repeat length by position
 	DevBuf<uint4> d_jump; int jump_k = 0; // round-3 jump table
 	// k-mer filter of the text for the min_seed_len in use: passes hold filter_rw shared; rebuilding it for another min_seed_len
@@ -172,6 +184,9 @@ struct cs_engine {
 	int bloom_tried_k = 0;                         // last min_seed_len the filter was (re)built or found not to fit for
 	std::unique_ptr<PassCtx> ctx[2];               // the second one is made on the first call that can use two passes at a time
 	PassCtx *last_ctx = nullptr;                   // which context holds the last whole-batch result (`last` lives in that one)
+	// cs_engine_memory reads these and nothing a running pass writes: bytes of each pass context as of the end of its last pass (0: no
+	// such context), and of the k-mer filter
+	std::atomic<uint64_t> ctx_bytes[2] = {{0}, {0}}, bloom_bytes{0};
 	// host variants (seed_host_pipelined): copy streams, three input slots, two pack slots, pinned packed results, expanded results
 	HipStream s_up, s_down; HipEvent hp_ev_pk[2], hp_ev_dn[4], hp_ev_done[PIPE_DEPTH];
 	PinBuf<uint4> hp_stage[3]; // records made by the host (host_pack.cpp), staged for the upload into hp_in[slot]
@@ -186,6 +201,7 @@ struct cs_engine {
 };
 
 inline int n_pass_ctx(const cs_engine *e) { return e->ctx[1] ? 2 : 1; }
+inline void note_ctx_bytes(cs_engine *e, const PassCtx *c) { e->ctx_bytes[c->id].store(c->device_bytes(), std::memory_order_relaxed); }
 inline void invalidate_last(cs_engine *e) { for (auto &c : e->ctx) if (c) c->last.valid = false; e->last_ctx = nullptr; }
 
 // seed_pass.hip

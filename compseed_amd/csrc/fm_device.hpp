@@ -30,8 +30,9 @@ struct DevIndex {
 	uint64_t primary, seq_len, n_sa, n_blocks; // n_blocks = 128-row blocks of the file layout
 	uint64_t L2[5];
 	uint32_t sa_mask, sa_shift;
-	// full suffix array materialised in HBM at engine creation (one entry per BWT row, 4 or 8 bytes): SAL becomes ONE
-	// gather instead of a walk of up to sa_intv-1 dependent Occ reads.  Null when disabled / out of memory.
+	// full suffix array materialised in HBM at engine creation (one entry per BWT row: 4 or 8 bytes, or 40 bits packed three to a
+	// 16-byte group, Pack40 below): SAL becomes ONE gather instead of a walk of up to sa_intv-1 dependent Occ reads.  At most one of
+	// the three is set; all null when disabled / out of memory.
 	const uint32_t *fsa32;
 	const uint64_t *fsa64;
 	// "text mode" for unique matches (smem_split.hpp): the text itself, 2 bits per base (16 bases per word, base j in bits
@@ -44,6 +45,45 @@ struct DevIndex {
 	// substring starting at text position p that occurs at least twice (capped at 255).  Null when disabled.
 	const uint8_t *lcp;
 	const uint8_t *rep;
+	// engine option sa40: the full suffix array and the inverse suffix array as 40-bit entries (Pack40); fsa32 / fsa64 / isa32 /
+	// isa64 are then null
+	const uint4 *fsa40;
+	const uint4 *isa40;
+};
+__host__ __device__ inline bool has_full_sa(const DevIndex &ix) { return ix.fsa32 || ix.fsa64 || ix.fsa40; }
+
+// ---- how the fill kernels and the accessors below see a suffix-array / inverse-SA buffer: get(k) / put(k, v) over plain 4- or
+// 8-byte entries, or over 40-bit entries.  The packed form holds THREE entries per aligned 16-byte group: their low words at bytes
+// 0, 4, 8, their fifth bytes at 12, 13, 14, byte 15 unused (5.33 bytes per entry).  Entry k lives in group k / 3, so an entry never
+// straddles a 64-byte line and a lookup is one aligned 16-byte load; put() is one dword store and one byte store that no other
+// entry shares, so threads that write neighbouring entries at the same time (isa[sa[r]] = r) need no atomics.
+template <typename T> struct Plain {
+	T *p;
+	__device__ __forceinline__ uint64_t get(uint64_t k) const { return (uint64_t)p[k]; }
+	__device__ __forceinline__ void put(uint64_t k, uint64_t v) const { p[k] = (T)v; }
+};
+constexpr size_t pack40_groups(uint64_t n) { return (size_t)((n + 2) / 3); } // 16-byte groups that hold n entries
+__device__ __forceinline__ uint64_t load40(const uint4 *p, uint64_t k)
+{
+	const uint64_t g = k / 3;
+	const uint32_t j = (uint32_t)k - (uint32_t)g * 3u;
+	uint4 q = p[g];
+	// all four words pass through an empty asm: otherwise the compiler narrows the load to the words a lane uses and fetches them
+	// behind divergent branches on j (three memory instructions and two branches instead of one global_load_dwordx4)
+	asm("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));
+	const uint32_t lo = j == 0 ? q.x : j == 1 ? q.y : q.z;
+	return (uint64_t)((q.w >> (j << 3)) & 0xffu) << 32 | lo;
+}
+struct Pack40 {
+	uint4 *p;
+	__device__ __forceinline__ uint64_t get(uint64_t k) const { return load40(p, k); }
+	__device__ __forceinline__ void put(uint64_t k, uint64_t v) const
+	{
+		const uint64_t g = k / 3;
+		const uint32_t j = (uint32_t)k - (uint32_t)g * 3u;
+		reinterpret_cast<uint32_t *>(p + g)[j] = (uint32_t)v;
+		reinterpret_cast<uint8_t *>(p + g)[12 + j] = (uint8_t)(v >> 32);
+	}
 };
 
 // ---- byte model of the kernels (bench.py's roofline): every read of an index-side array is an EVENT, counted per lane in a
@@ -299,10 +339,10 @@ __device__ __forceinline__ uint64_t inv_psi(const DevIndex &ix, uint64_t k)
 __device__ __forceinline__ uint64_t sa_direct(const DevIndex &ix, uint64_t k)
 {
 	if (k == 0) return ~0ull; // sa[0] = -1 (bwt.c:83)
-	return ix.fsa32 ? (uint64_t)ix.fsa32[k] : ix.fsa64[k];
+	return ix.fsa32 ? (uint64_t)ix.fsa32[k] : ix.fsa64 ? ix.fsa64[k] : load40(ix.fsa40, k);
 }
 
-__device__ __forceinline__ uint64_t isa_direct(const DevIndex &ix, uint64_t pos) { return ix.isa32 ? (uint64_t)ix.isa32[pos] : ix.isa64[pos]; }
+__device__ __forceinline__ uint64_t isa_direct(const DevIndex &ix, uint64_t pos) { return ix.isa32 ? (uint64_t)ix.isa32[pos] : ix.isa64 ? ix.isa64[pos] : load40(ix.isa40, pos); }
 
 // 32 text bases from position pos on (2 bits each, base j in bits 2j..2j+1); the text buffer is padded
 __device__ __forceinline__ uint64_t text_win(const DevIndex &ix, uint64_t pos)

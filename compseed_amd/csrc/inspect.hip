@@ -163,7 +163,7 @@ extern "C" int cs_engine_check_index(cs_engine_t *e, const uint8_t *d_fwd_nt4, u
 {
 	if (!e || !out) return fail(CS_EINVAL, "cs_engine_check_index: null argument");
 	if (pipe_busy(e)) return fail(CS_EINVAL, "cs_engine_check_index: submitted batches are in flight, collect them first");
-	if (!e->ix.text2 || !(e->ix.fsa32 || e->ix.fsa64)) return fail(CS_EINVAL, "cs_engine_check_index: needs the full suffix array and the text arrays (engine options full_sa, text_mode)");
+	if (!e->ix.text2 || !has_full_sa(e->ix)) return fail(CS_EINVAL, "cs_engine_check_index: needs the full suffix array and the text arrays (engine options full_sa, text_mode)");
 	if (d_fwd_nt4 && 2 * l_pac != e->ix.seq_len) return fail(CS_EINVAL, "cs_engine_check_index: l_pac is not half of the index length");
 	HIP_TRY(hipSetDevice(e->device));
 	PassCtx *c = e->ctx[0].get();
@@ -215,7 +215,7 @@ __global__ void sa_kernel(const DevIndex ix, const uint64_t *k, uint64_t *sa, in
 	if (t >= n) return;
 	uint64_t walked = sa_lookup(ix, k[t]);
 	// when the full suffix array is resident it must agree with the walk on every row (mismatch => poison the answer)
-	if ((ix.fsa32 || ix.fsa64) && sa_direct(ix, k[t]) != walked) walked = 0xdeadbeefdeadbeefull;
+	if (has_full_sa(ix) && sa_direct(ix, k[t]) != walked) walked = 0xdeadbeefdeadbeefull;
 	sa[t] = walked;
 }
 

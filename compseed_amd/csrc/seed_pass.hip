@@ -44,6 +44,8 @@ int add_pass_ctx(cs_engine *e)
 	CS_TRY(c->d_evc.reserve((size_t)N_KID * N_EV));
 	HIP_TRY(hipMemsetAsync(c->d_evc.p, 0, (size_t)N_KID * N_EV * sizeof(unsigned long long), c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->id = ci;
+	note_ctx_bytes(e, c.get());
 	e->ctx[ci] = std::move(c);
 	if (ci && e->opt.verbose) { fprintf(stderr, "[cs_engine] second pass context created\n"); fflush(stderr); }
 	return CS_OK;
@@ -199,6 +201,7 @@ static int build_kmer_filter(cs_engine *e, int k, hipStream_t s)
 	hipLaunchKernelGGL(kmer_filter_fill_kernel, dim3((unsigned)(e->n_cu * 32)), dim3(256), 0, s, e->ix, k, e->d_bloom.p, bits);
 	HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(s));
 	e->bloom_k = k; e->bloom_bits = bits; e->bloom_tried_k = k;
+	e->bloom_bytes.store((uint64_t)e->d_bloom.cap * sizeof(uint64_t), std::memory_order_relaxed);
 	return CS_OK;
 }
 
@@ -560,7 +563,7 @@ static int seed_device_impl(const cs_engine *e, PassCtx *c, const cs_params_t *p
 		HIP_TRY(hipStreamSynchronize(s));
 		uint64_t total_seeds = c->h_ctr.p[0];
 		CS_TRY(c->d_seeds.reserve((size_t)total_seeds + 16));
-		const bool fused_gather = !e->opt.count_sal_merged && (e->ix.fsa32 || e->ix.fsa64); // (the merged-call statistic needs the slots)
+		const bool fused_gather = !e->opt.count_sal_merged && has_full_sa(e->ix); // (the merged-call statistic needs the slots)
 		if (total_mems) {
 			if (fused_gather) hipLaunchKernelGGL(sal_expand_kernel<true>, dim3(grid_for((int64_t)total_mems, 256)), dim3(256), 0, s, e->ix, c->d_mems.p, total_mems,
 			                                     (uint32_t)par->max_occ, som.p, c->d_seeds.p);
@@ -587,7 +590,7 @@ static int seed_device_impl(const cs_engine *e, PassCtx *c, const cs_params_t *p
 			sal_calls = c->h_ctr.p[5];
 		}
 		if (total_seeds && !fused_gather) {
-			if (e->ix.fsa32 || e->ix.fsa64)
+			if (has_full_sa(e->ix))
 				hipLaunchKernelGGL(sal_gather_kernel, dim3(grid_for((int64_t)total_seeds, 256)), dim3(256), 0, s, e->ix, c->d_seeds.p, total_seeds);
 			else
 				hipLaunchKernelGGL(sal_walk_kernel, dim3(grid_for((int64_t)total_seeds, 256)), dim3(256), 0, s, e->ix, c->d_seeds.p, total_seeds);
@@ -621,7 +624,11 @@ int run_pass(cs_engine *e, PassCtx *c, const cs_params_t *par, int64_t n_reads, 
 	for (;;) {
 		{
 			std::shared_lock<std::shared_mutex> sl(e->filter_rw);
-			if (!wants_build()) return seed_device_impl(e, c, par, n_reads, d_bases, d_off, n_bases, nm, ns, d_recs);
+			if (!wants_build()) {
+				const int rc = seed_device_impl(e, c, par, n_reads, d_bases, d_off, n_bases, nm, ns, d_recs);
+				note_ctx_bytes(e, c); // what the pass made its buffers grow to
+				return rc;
+			}
 		}
 		std::unique_lock<std::shared_mutex> ul(e->filter_rw);
 		if (wants_build()) { e->bloom_tried_k = k; CS_TRY(build_kmer_filter(e, k, c->stream)); }

@@ -102,7 +102,10 @@ typedef struct {
 	int32_t passes_in_flight; /* [2] seeding passes the engine runs at the same time (parts of a blocking call, batches of a stream, device
 	                           *     batches of cs_engine_submit_device): the thin tail of one pass is filled by the next.  2 costs a second
 	                           *     set of working buffers (allocated on first use); 1 = one pass at a time                          */
-	int32_t reserved[3];      /* must be 0 */
+	int32_t sa40;             /* [0] 1: the full suffix array and the inverse suffix array as 40-bit entries, three to a 16-byte group
+	                           *     (5.33 instead of 8 bytes per row: 33 GB less at hg19 scale), whatever the index size; sa64 is then
+	                           *     ignored.  Needs full_sa; an index of 2^40 rows or more gives CS_ERANGE                          */
+	int32_t reserved[2];      /* must be 0 */
 } cs_engine_options_t;
 
 /* CSR result of one batch.  Read r owns mems[mem_off[r] .. mem_off[r+1]) sorted by info (comp_seed.cpp:2301) and
@@ -430,7 +433,7 @@ int  cs_engine_gather_reads(cs_engine_t *e, int64_t n_sel, const uint64_t *read_
  *      the kernels ask for -- a lower bound of what has to come out of HBM/L2 for them -- not the bytes of the reference's
  *      algorithm (most of whose bwt_extend calls are answered without the FM index here).  Accumulated like cs_stats_t. */
 #define CS_N_KERNELS 9   /* fwd0, fwd, bwd_win, bwd_win0, bwd_wide, bwd_all, r2text, r3text, fused (smem_kernel) */
-#define CS_N_EVENTS 10   /* Occ record 32 B, jump entry 16 B, filter word 8 B, SA entry, inverse-SA entry (4 or 8 B), text word 4 B,
+#define CS_N_EVENTS 10   /* Occ record 32 B, jump entry 16 B, filter word 8 B, SA entry, inverse-SA entry (4 or 8 B; 5 under sa40), text word 4 B,
                             rep[] load 8 B, lcp[] byte, LEP entry 16 B (read or written), mem record read back 32 B */
 typedef struct {
 	uint64_t events[CS_N_KERNELS][CS_N_EVENTS];
@@ -454,6 +457,30 @@ int  cs_engine_check_index(cs_engine_t *e, const uint8_t *d_fwd_nt4, uint64_t l_
 
 int  cs_engine_stats(const cs_engine_t *e, cs_stats_t *st);
 void cs_engine_reset_stats(cs_engine_t *e);
+
+/* ---- what the engine holds in device memory, in bytes, by group: the sizes its buffers were reserved with (padding included), not
+ *      differences of free memory.  The index-side arrays are fixed once the engine exists (an array that did not fit, or was switched
+ *      off, reports 0); kmer_filter changes when a call with another min_seed_len rebuilds the filter; pass_ctx[i] is the working set of
+ *      pass context i (streams' buffers: reads, queues, LEP arena, raw mems, results) as of the end of its last pass -- it grows with the
+ *      largest batch seen -- and 0 for a context that does not exist (the second one is made on first use).  total is the sum of the
+ *      groups.  Not counted: the staging buffers of the host variants and of cs_engine_gather_reads, which are a few bytes per read of a
+ *      sub-batch.  sa_entry_bits: the entry width of the full suffix array / inverse suffix array, 32, 40 or 64; 0 without a full suffix
+ *      array.  Host-only: no device call is made, and it is legal while submitted batches are in flight. */
+typedef struct {
+	uint64_t occ_bwt;        /* Occ/BWT records                          */
+	uint64_t sampled_sa;
+	uint64_t full_sa;
+	uint64_t isa;            /* inverse suffix array                     */
+	uint64_t text;           /* 2-bit text                               */
+	uint64_t lcp_rep;        /* lcp[] + rep[]                            */
+	uint64_t jump_table;
+	uint64_t kmer_filter;
+	uint64_t pass_ctx[2];
+	uint64_t total;
+	int32_t  sa_entry_bits;
+	int32_t  n_pass_ctx;     /* pass contexts allocated: 1 or 2          */
+} cs_memory_t;
+int  cs_engine_memory(const cs_engine_t *e, cs_memory_t *out);
 
 /* ---- batched primitives on the device index, for parity tests of the building blocks (host pointers):
  *      bwt_occ4 (bwt.c:169), bwt_extend (bwt.c:262; ok is n x 4 intervals, info untouched = 0), bwt_sa (bwt.c:86) */
