@@ -302,7 +302,7 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 		}
 	}
 
-	// text mode (smem_split.hpp): the 2-bit text and the inverse suffix array, derived from the full suffix array
+	// text mode (smem_common.hpp, text_step): the 2-bit text and the inverse suffix array, derived from the full suffix array
 	ix.text2 = nullptr; ix.isa32 = nullptr; ix.isa64 = nullptr; ix.isa40 = nullptr;
 	{
 		size_t free_b = 0, total_b = 0;
@@ -329,7 +329,7 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 		}
 		if (verbose) { fprintf(stderr, "[cs_engine] text mode: %s\n", ix.text2 ? "on" : "off"); fflush(stderr); }
 	}
-	// re-seeding from the text (smem_split.hpp, r2text_kernel): capped LCP array and repeat-length array, 1 byte per row each
+	// re-seeding from the text (smem_text.hpp, r2text_kernel): capped LCP array and repeat-length array, 1 byte per row each
 	ix.lcp = nullptr; ix.rep = nullptr;
 	{
 		size_t free_b = 0, total_b = 0;
@@ -356,7 +356,7 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 			fprintf(stderr, "[cs_engine] re-seeding from the text: %s; device memory free %.1f of %.1f GB\n", ix.rep ? "on" : "off", free_b / 1e9, total_b / 1e9); fflush(stderr);
 		}
 	}
-	// round-3 jump table (smem_split.hpp): every 15-mer, 17 GB (13: 1 GB, measured 2 % slower); CS_JUMP_K = 0 disables
+	// round-3 jump table (smem_fwd.hpp): every 15-mer, 17 GB (13: 1 GB, measured 2 % slower); CS_JUMP_K = 0 disables
 	{
 		const int jk = opt.jump_k;
 		size_t free_b = 0, total_b = 0;

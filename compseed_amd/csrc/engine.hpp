@@ -1,6 +1,7 @@
 // engine.hpp -- what the translation units of the seeding engine share (not part of the C ABI):
 //   engine.hip     ABI lifecycle, options, index load / residency, statistics, device memory helpers
-//   seed_pass.hip  one seeding pass on a pass context: SMEM stage, sort, SAL; the k-mer filter
+//   seed_pass.hip  one seeding pass on a pass context: SMEM stage, sort, SAL; the k-mer filter.  The only unit that includes the
+//                  kernels of the default SMEM path, smem_common.hpp and smem_{reads,fwd,bwd,text,sort}.hpp
 //   pipelines.hip  the host pipeline (cs_engine_submit / collect, blocking host variants) and the device pipeline
 //   inspect.hip    digest and gather of the last result, index validation, primitives, the random-line probe
 // Kernels are defined in the unit that launches them; the headers included by more than one unit hold types and __device__ functions.
@@ -123,6 +124,37 @@ using HipStream = HipHandle<hipStream_t, hipStreamDestroy>;
 using HipEvent = HipHandle<hipEvent_t, hipEventDestroy>;
 
 // ------------------------------------------------------------------------------------------------ engine
+// The words of PassCtx::d_sctr / h_sctr, the counters of the split SMEM stage.  seed_pass.hip hands the kernels pointers to them
+// (SplitArgs and kernel arguments) and reads the whole block back after every iteration.
+enum : int {
+	SC_TASK = 0,           // task dispenser of the forward kernels
+	SC_NEXT_N = 1,         // length of the next forward queue, no-op slots included
+	SC_BWD_CLS = 2,        // 2..5: slot counters of the backward kernels' size classes
+	SC_BWD_WIDE = 5,       // ... the last of them: calls with more than 64 LEPs (bwd_wide_kernel)
+	SC_OVF_MEMS = 6,       // mems beyond a read's first `cap` (overflow records)
+	SC_ERR = 7,            // sticky: a queue or the overflow records ran full
+	SC_QUERIES = 8,        // bwt_extend queries
+	SC_SST_HITS = 9,       // ... of which the on-device SST answered
+	SC_R3_TASK = 10,       // task dispenser of round 3 on the index (its own stream)
+	SC_R2_TEXT = 11,       // re-seeding calls answered from the text (r2text_kernel, fwd0_kernel's quick test)
+	SC_R2_INDEX = 12,      // re-seeding calls left to the index
+	SC_BTASKS = 13,        // backward calls created by the last forward launch
+	SC_TEXT_SWEEPS = 14,   // backward sweeps answered from the text
+	SC_R3_TEXT_SEEDS = 15, // round-3 seeds made by r3text_kernel
+	SC_DENSE_N = 16,       // length of the next forward queue as r2text_kernel has compacted it
+	SC_WORDS = 32
+};
+// The words of PassCtx::d_ctr / h_ctr as seed_pass.hip uses them (inspect.hip takes d_ctr as scratch of its own)
+enum : int {
+	CTR_TASK = 0,          // task dispenser of the fused kernel
+	CTR_FETCHED = 0,       // h_ctr only: where a single fetched word (a running total) lands
+	CTR_QUERIES = 1,       // bwt_extend queries of the fused kernel
+	CTR_OVERFLOW = 2,      // reads with more than `cap` mems (fused path)
+	CTR_MAX_LEN = 3,       // longest read of the batch
+	CTR_BAD_OFFSETS = 4,   // offsets that do not tile [0, n_bases)
+	CTR_SAL_DISTINCT = 5,  // distinct SA slots per 512-read batch (engine option count_sal_merged)
+	CTR_WORDS = 8
+};
 // What one seeding pass owns.  An engine has one or two of them: the tail of a pass (late iterations with a few thousand calls each,
 // the sort, SAL, ten host round trips) leaves most of the GPU idle, and a small part of a batch is nearly all tail; a second pass,
 // on a context of its own, fills it.
@@ -131,12 +163,12 @@ struct PassCtx {
 	HipEvent ev_r3a, ev_r3b, ev_wa, ev_wb, ev_wc;
 	HipEvent ev[4];
 	DevBuf<uint8_t> d_pending; // r3text_kernel: reads with calls of rounds 1/2 still queued when it starts
-	DevBuf<uint32_t> d_cnt_snap; DevBuf<uint64_t> d_auxA, d_auxB; // re-seeding from the text
+	DevBuf<uint32_t> d_cnt_snap; DevBuf<uint64_t> d_aux; // re-seeding from the text: r3text_kernel's snapshot of the mem counts; side words of d_fqB's re-seeding calls
 	// inputs
 	DevBuf<uint8_t> d_seq; DevBuf<uint4> d_seqp; const uint4 *seqp_cur = nullptr; const uint64_t *off_base = nullptr; // d_seqp: pack_reads_kernel's records for the batch whose offsets start at off_base
 	// SMEM stage
 	DevBuf<OutMem> d_out, d_out2; DevBuf<uint32_t> d_cnt, d_cnt2, d_ovf; DevBuf<uint4> d_spill;
-	DevBuf<unsigned long long> d_ctr; // [0] task counter, [1] queries, [2] overflow count, [3] max len
+	DevBuf<unsigned long long> d_ctr; // CTR_WORDS words: the CTR_* enum above for seed_pass.hip, anonymous scratch for inspect.hip
 	DevBuf<uint8_t> d_tmp, d_tmp2;
 	PinBuf<unsigned long long> h_ctr;
 	// results (device)
@@ -153,7 +185,7 @@ struct PassCtx {
 	{
 		uint64_t b = 0;
 		auto add = [&b](const auto &...buf) { ((b += (uint64_t)buf.cap * sizeof(*buf.p)), ...); };
-		add(d_pending, d_cnt_snap, d_auxA, d_auxB, d_seq, d_seqp, d_out, d_out2, d_cnt, d_cnt2, d_ovf, d_spill, d_ctr, d_tmp, d_tmp2);
+		add(d_pending, d_cnt_snap, d_aux, d_seq, d_seqp, d_out, d_out2, d_cnt, d_cnt2, d_ovf, d_spill, d_ctr, d_tmp, d_tmp2);
 		add(d_mem_off, d_seed_off, d_seed_of_mem, d_mems, d_salcnt, d_seeds, d_fqA, d_fqB, d_fqR, d_sst2, d_bq, d_lep, d_ovfrec);
 		add(d_okey, d_oidx, d_okey2, d_oidx2, d_okey64, d_okey64b, d_sctr, d_evc);
 		return b;
@@ -165,7 +197,7 @@ struct cs_engine {
 	int device = 0;
 	int n_cu = 256;
 	cs_engine_options_t opt{};
-	int smem_mode = 1;          // 1 = split kernels (default), 0 = fused one-lane-per-read kernel (CS_SMEM_MODE=fused)
+	int smem_mode = 1;          // 1 = split kernels (default), 0 = fused one-lane-per-read kernel (engine option `fused`)
 	int occ_win = 5; // ... of bwd_win_kernel
 	int occ_fwd = 4, occ_bwd = 4; // resident 256-thread blocks per CU of fwd_kernel / bwd_kernel
 	size_t lep_arena_bytes = (size_t)32 << 30;

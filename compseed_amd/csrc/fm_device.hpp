@@ -35,12 +35,12 @@ struct DevIndex {
 	// the three is set; all null when disabled / out of memory.
 	const uint32_t *fsa32;
 	const uint64_t *fsa64;
-	// "text mode" for unique matches (smem_split.hpp): the text itself, 2 bits per base (16 bases per word, base j in bits
+	// "text mode" for unique matches (smem_common.hpp, text_step): the text itself, 2 bits per base (16 bases per word, base j in bits
 	// 2j..2j+1), and the inverse suffix array.  Null when disabled / out of memory.
 	const uint32_t *text2;
 	const uint32_t *isa32;
 	const uint64_t *isa64;
-	// Re-seeding from the text (smem_split.hpp, r2text_kernel): lcp[r] = min(255, LCP(suffix of row r-1, suffix of row r))
+	// Re-seeding from the text (smem_text.hpp, r2text_kernel): lcp[r] = min(255, LCP(suffix of row r-1, suffix of row r))
 	// for rows 1..seq_len (lcp[0] = lcp[seq_len+1] = 0), and rep[p] = max(lcp[ISA[p]], lcp[ISA[p]+1]) = length of the longest
 	// substring starting at text position p that occurs at least twice (capped at 255).  Null when disabled.
 	const uint8_t *lcp;
@@ -151,7 +151,7 @@ struct BTask { uint32_t r; uint16_t x, mi_kind, n, ret; uint32_t cls; };  // 16 
                                                                            // cls = size class 0..3, 0xffffffff = no call
 struct OvfRec { OutMem m; uint32_t r, pad; };                              // a mem beyond a read's first `cap`
 
-// a bi-interval as a 16-byte LEP entry (seed_kernels.hpp, smem_split.hpp) and as a jump-table entry (smem_split.hpp)
+// a bi-interval as a 16-byte LEP entry (seed_kernels.hpp, smem_fwd.hpp) and as a jump-table entry (smem_fwd.hpp, smem_bwd.hpp)
 __device__ __forceinline__ uint4 pack_lep(const Intv &v, uint32_t end)
 {
 	uint4 e;

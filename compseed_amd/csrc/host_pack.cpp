@@ -1,4 +1,4 @@
-// The reads as the seeding kernels want them -- 16-byte records of 32 bases (smem_split.hpp, pack_reads_kernel) -- made on the host, so
+// The reads as the seeding kernels want them -- 16-byte records of 32 bases (smem_reads.hpp, pack_reads_kernel) -- made on the host, so
 // that a batch crosses PCIe as 0.6 bytes per base instead of one.  The records are bit-identical to pack_reads_kernel<true>'s:
 // .x/.y the bases, 2 bits each, base j in bits 2j..2j+1; .z one bit per base that is ambiguous or behind the end of the read; .w 0;
 // record k of read r at (off[r] >> 5) + r + k with off counted from the part's first base; letters through nst_nt4_table's rule

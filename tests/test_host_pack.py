@@ -1,5 +1,5 @@
 """cs_pack_reads (host_pack.cpp): the records the host variants upload, against a numpy restatement of the record format
-(smem_split.hpp pack_reads_kernel; the GPU test test_host_packed_reads_equal_device_packed compares the two on the device)."""
+(smem_reads.hpp pack_reads_kernel; the GPU test test_host_packed_reads_equal_device_packed compares the two on the device)."""
 import numpy as np
 import pytest
 
