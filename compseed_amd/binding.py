@@ -14,6 +14,7 @@ SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", 
            "cs_index_build_flags", "cs_index_save", "cs_refseq_from_fasta", "cs_refseq_codes", "cs_refseq_save", "cs_refseq_free", "cs_index_build_fasta", "cs_reader_open", "cs_reader_next", "cs_reader_close",
            "cs_chainer_create", "cs_chainer_destroy", "cs_chain_params_default", "cs_chain_batch", "cs_flt_params_default", "cs_chain_filter",
            "cs_chainer_create_device", "cs_chain_batch_device", "cs_chain_batch_gpu", "cs_chainer_stats",
+           "cs_chain_filter_device", "cs_chain_filter_gpu", "cs_chain_filter_stats",
            "cs_device_count", "cs_engine_options_default", "cs_engine_create", "cs_engine_create_opts", "cs_engine_destroy", "cs_engine_seed_batch",
            "cs_engine_seed_batch_device", "cs_engine_submit_device", "cs_engine_collect_device", "cs_engine_seed_batch_packed", "cs_engine_submit", "cs_engine_collect_packed", "cs_unpack_mem", "cs_mem_seed_count", "cs_host_alloc", "cs_host_free", "cs_pack_reads",
            "cs_engine_result_digest", "cs_engine_gather_reads", "cs_engine_traffic_model", "cs_engine_stats", "cs_engine_reset_stats", "cs_engine_occ4",
@@ -182,6 +183,11 @@ class ChainStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("reads", "seeds", "chains", "tree_reads", "launches")] + [("kernel_ms", C.c_double)]
 
 
+class FltStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "chains_in", "chains_out", "seeds_in", "seeds_out", "wave_reads", "spill_reads", "sw_seeds", "launches")] + [("kernel_ms", C.c_double)]
+
+
+FLT_WAVE_ONLY = 1     # CS_FLT_WAVE_ONLY: every read through the wave-per-read path of the device chain filter (A/B switch, same results)
 CHAIN_TREE_ONLY = 1   # CS_CHAIN_TREE_ONLY: every read through the B-tree path of the device chainer (A/B switch, same results)
 
 
@@ -316,6 +322,9 @@ def load_library():
     L.cs_flt_params_default.argtypes = [C.POINTER(FltParams)]
     L.cs_flt_params_default.restype = None
     L.cs_chain_filter.argtypes = [vp, C.POINTER(FltParams), C.POINTER(CChainResult), vp, vp, C.c_int, C.POINTER(CChainResult), C.POINTER(vp)]
+    L.cs_chain_filter_device.argtypes = [vp, C.POINTER(FltParams), C.POINTER(CChainResult), vp, vp, C.c_uint32, C.POINTER(CChainResult), C.POINTER(vp)]
+    L.cs_chain_filter_gpu.argtypes = [vp, C.POINTER(FltParams), C.POINTER(CChainResult), vp, vp, C.c_uint32, C.POINTER(CChainResult), C.POINTER(vp)]
+    L.cs_chain_filter_stats.argtypes = [vp, C.POINTER(FltStats)]
     L.cs_device_count.argtypes = [C.POINTER(C.c_int)]
     L.cs_engine_create.argtypes = [C.POINTER(IndexView), C.c_int, C.POINTER(vp)]
     L.cs_engine_destroy.argtypes = [vp]
@@ -582,6 +591,41 @@ class Chainer:
                     cseed_off=_view(out.cseed_off, "<u8", int(out.n_chains) + 1, copy), cseeds=_view(out.cseeds, SEED_DT, int(out.n_seeds), copy),
                     cseed_score=_view(sc.value, "<i4", int(out.n_seeds), copy))
 
+    def filter_gpu(self, chain_off, chains, cseed_off, cseeds, bases, read_offsets, params=None, flags=0, copy=True):
+        """cs_chain_filter_gpu: filter()'s arguments and result, the work done on the chainer's GPU (flags: FLT_WAVE_ONLY)"""
+        params = params or FltParams()
+        chain_off = np.ascontiguousarray(chain_off, dtype=np.uint64); cseed_off = np.ascontiguousarray(cseed_off, dtype=np.uint64)
+        chains = np.ascontiguousarray(chains, dtype=CHAIN_DT); cseeds = np.ascontiguousarray(cseeds, dtype=SEED_DT)
+        ro = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+        bases = None if bases is None else np.ascontiguousarray(bases, dtype=np.uint8)
+        cin = CChainResult(chain_off.size - 1, chains.size, cseeds.size, chain_off.ctypes.data, chains.ctypes.data if chains.size else None, cseed_off.ctypes.data,
+                           cseeds.ctypes.data if cseeds.size else None)
+        out = CChainResult(); sc = C.c_void_p()
+        _check(load_library().cs_chain_filter_gpu(self._h, C.byref(params), C.byref(cin), bases.ctypes.data if bases is not None and bases.size else None, ro.ctypes.data,
+                                                  int(flags), C.byref(out), C.byref(sc)))
+        return dict(chain_off=_view(out.chain_off, "<u8", int(out.n_reads) + 1, copy), chains=_view(out.chains, CHAIN_DT, int(out.n_chains), copy),
+                    cseed_off=_view(out.cseed_off, "<u8", int(out.n_chains) + 1, copy), cseeds=_view(out.cseeds, SEED_DT, int(out.n_seeds), copy),
+                    cseed_score=_view(sc.value, "<i4", int(out.n_seeds), copy))
+
+    def filter_device(self, d_chains, d_bases, d_read_offsets, params=None, flags=0):
+        """cs_chain_filter_device: chain_device()'s dict, the batch's reads and offsets in device memory (d_bases may be None / 0 when no read is
+        long enough for the seed test) -> the same dict form for the surviving chains plus cseed_score, the device pointer of their seeds'
+        scores; device arrays owned by the chainer, valid until its next filter_device / filter_gpu (download_chains() brings them over)"""
+        params = params or FltParams()
+        d = d_chains
+        cin = CChainResult(d["n_reads"], d["n_chains"], d["n_seeds"], d["chain_off"], d["chains"], d["cseed_off"], d["cseeds"])
+        out = CChainResult(); sc = C.c_void_p()
+        _check(load_library().cs_chain_filter_device(self._h, C.byref(params), C.byref(cin), C.c_void_p(d_bases or None), C.c_void_p(d_read_offsets or None), int(flags),
+                                                     C.byref(out), C.byref(sc)))
+        return dict(n_reads=int(out.n_reads), n_chains=int(out.n_chains), n_seeds=int(out.n_seeds), chain_off=out.chain_off, chains=out.chains,
+                    cseed_off=out.cseed_off, cseeds=out.cseeds, cseed_score=sc.value)
+
+    def filter_stats(self):
+        """cs_chain_filter_stats: counters of filter_device / filter_gpu over the chainer's life"""
+        st = FltStats()
+        _check(load_library().cs_chain_filter_stats(self._h, C.byref(st)))
+        return {n: (float(getattr(st, n)) if n == "kernel_ms" else int(getattr(st, n))) for n, _ in FltStats._fields_}
+
     def close(self):
         if self._h:
             load_library().cs_chainer_destroy(self._h)
@@ -595,11 +639,15 @@ class Chainer:
 
 
 def download_chains(engine, d):
-    """Chainer.chain_device's result -> chain()'s dict of host arrays, through an Engine on the same GPU"""
+    """Chainer.chain_device's result -> chain()'s dict of host arrays, through an Engine on the same GPU; Chainer.filter_device's result
+    (a dict with cseed_score) -> filter()'s dict"""
     def get(ptr, dt, n):
         return engine.download(ptr, dt, n) if n else np.zeros(0, dtype=dt)
-    return dict(chain_off=get(d["chain_off"], np.uint64, d["n_reads"] + 1), chains=get(d["chains"], CHAIN_DT, d["n_chains"]),
-                cseed_off=get(d["cseed_off"], np.uint64, d["n_chains"] + 1), cseeds=get(d["cseeds"], SEED_DT, d["n_seeds"]))
+    out = dict(chain_off=get(d["chain_off"], np.uint64, d["n_reads"] + 1), chains=get(d["chains"], CHAIN_DT, d["n_chains"]),
+               cseed_off=get(d["cseed_off"], np.uint64, d["n_chains"] + 1), cseeds=get(d["cseeds"], SEED_DT, d["n_seeds"]))
+    if "cseed_score" in d:
+        out["cseed_score"] = get(d["cseed_score"], np.int32, d["n_seeds"])
+    return out
 
 
 def build_index_from_fasta(fasta, prefix, device=0):

@@ -235,7 +235,7 @@ extern "C" int cs_chainer_create(const char *prefix, cs_chainer_t **out)
 	*out = c;
 	return CS_OK;
 }
-extern "C" void cs_chainer_destroy(cs_chainer_t *c) { if (c && c->gpu) cs_chainer_gpu_release_(c->gpu); delete c; }
+extern "C" void cs_chainer_destroy(cs_chainer_t *c) { if (c && c->flt) cs_chainer_flt_gpu_release_(c->flt); if (c && c->gpu) cs_chainer_gpu_release_(c->gpu); delete c; }
 
 extern "C" void cs_chain_params_default(cs_chain_params_t *p)
 {

@@ -397,6 +397,8 @@ void cs_chainer_gpu_release_(cs_chainer_gpu *g)
 	delete g;
 }
 
+int cs_chainer_gpu_device_(const cs_chainer_gpu *g) { return g->device; }
+
 namespace {
 int gpu_init(cs_chainer *c, int device)
 {

@@ -29,10 +29,15 @@ inline uint8_t cs_base_code_(uint8_t c)
 // the device side of a chainer (chain_gpu.hip: cs_chain_batch_device / cs_chain_batch_gpu)
 struct cs_chainer_gpu;
 void cs_chainer_gpu_release_(cs_chainer_gpu *g);
+int cs_chainer_gpu_device_(const cs_chainer_gpu *g);
+// the device side of the chain filters (chain_filter_gpu.hip: cs_chain_filter_device / cs_chain_filter_gpu), made by the first such call
+struct cs_chainer_flt_gpu;
+void cs_chainer_flt_gpu_release_(cs_chainer_flt_gpu *g);
 
 // the chainer (chain.cpp: cs_chain_batch; chain_filter.cpp: cs_chain_filter)
 struct cs_chainer {
 	cs_chainer_gpu *gpu = nullptr;                                                                                                       // cs_chainer_create_device only
+	cs_chainer_flt_gpu *flt = nullptr;                                                                                                   // ... and after its first device filter call
 	cs_refseq_view ref; std::string prefix;
 	std::vector<cs_chain_t> chains; std::vector<uint64_t> chain_off, cseed_off; std::vector<cs_seed_t> cseeds;                          // cs_chain_batch's result
 	std::vector<uint8_t> pac;                                                                                                            // loaded when cs_chain_filter first needs it

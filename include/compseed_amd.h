@@ -328,7 +328,7 @@ int  cs_chain_batch_gpu(cs_chainer_t *c, const cs_chain_params_t *par, const cs_
                         cs_chain_result_t *out);
 int  cs_chainer_stats(const cs_chainer_t *c, cs_chain_stats_t *st);
 
-/* ---- the chain filters between chaining and extension (comp_seed.cpp:2364-2367), host code: mem_chain_flt (comp_seed.cpp:297-360: chains
+/* ---- the chain filters between chaining and extension (comp_seed.cpp:2364-2367), as host code and (below) as kernels: mem_chain_flt (comp_seed.cpp:297-360: chains
  *      by descending weight -- klib's introsort, whose order among equal weights is reproduced --, chains shadowed on the read by a much
  *      heavier one dropped, the first shadowed chain of each kept one retained) and mem_flt_chained_seeds (comp_seed.cpp:393-412: for reads
  *      of ~700 bases and more, short seeds whose neighbourhood does not reach a local alignment score of 5.5 ln(read length) are dropped and
@@ -341,6 +341,31 @@ typedef struct { int32_t min_chain_weight, max_chain_extend, max_chain_gap, min_
 void cs_flt_params_default(cs_flt_params_t *p);
 int  cs_chain_filter(cs_chainer_t *c, const cs_flt_params_t *par, const cs_chain_result_t *in, const uint8_t *bases, const uint64_t *read_offsets,
                      int n_threads, cs_chain_result_t *out, const int32_t **cseed_score);
+/* The same two filters on the GPU (chain_filter_gpu.hip), byte for byte cs_chain_filter's result; cs_chain_filter stays the specification.
+ * Both calls need a chainer from cs_chainer_create_device (CS_EINVAL otherwise).  cs_chain_filter_device: `d_in` is a chain result as
+ * cs_chain_batch_device returns it (device pointers on the chainer's GPU, host counts), complete when the call is made; `d_bases` /
+ * `d_read_offsets` are the batch's reads in device memory (ASCII or codes, n_reads + 1 offsets).  `d_bases` may be NULL only if no read with
+ * chains is long enough for the seed test (found by a kernel; <prefix>.pac is loaded and uploaded only then, once per chainer).  Results are
+ * complete when the call returns: `d_out` and `*d_cseed_score` are device arrays of the chainer's filter state, buffers of their own -- the
+ * chainer's cs_chain_batch_device output, this call's usual input, is left as it is -- and stay valid until the chainer's next
+ * cs_chain_filter_device / cs_chain_filter_gpu.  cs_chain_filter_gpu: the same work from host arrays to host arrays (owned by the chainer,
+ * valid as long).  Passing a call's own previous output as input gives CS_EINVAL, unknown flag bits too; the parameter checks are
+ * cs_chain_filter's; n_reads == 0 gives an empty result.  Inconsistent input (a chain without seeds, offsets that are not a CSR, a chain's
+ * n_seeds that is not what cseed_off says) is found by the first kernels, which do not follow it, and reported as CS_EINVAL; a read of
+ * 65,536 bases or more gives CS_ERANGE.  cs_chain_filter_stats: counters of both calls over the chainer's life (zero for a host chainer). */
+#define CS_FLT_WAVE_ONLY 1u   /* A/B switch: every read through the wave-per-read path; same results */
+typedef struct { uint64_t reads, chains_in, chains_out, seeds_in, seeds_out,
+                 wave_reads,    /* reads that took the wave-per-read path            */
+                 spill_reads,   /* ... of those, reads whose lists did not fit the LDS */
+                 sw_seeds,      /* seeds scored by the local alignment (long reads)  */
+                 launches; double kernel_ms; } cs_flt_stats_t;
+int  cs_chain_filter_device(cs_chainer_t *c, const cs_flt_params_t *par, const cs_chain_result_t *d_in,
+                            const uint8_t *d_bases, const uint64_t *d_read_offsets, uint32_t flags,
+                            cs_chain_result_t *d_out, const int32_t **d_cseed_score);
+int  cs_chain_filter_gpu(cs_chainer_t *c, const cs_flt_params_t *par, const cs_chain_result_t *in,
+                         const uint8_t *bases, const uint64_t *read_offsets, uint32_t flags,
+                         cs_chain_result_t *out, const int32_t **cseed_score);
+int  cs_chain_filter_stats(const cs_chainer_t *c, cs_flt_stats_t *st);
 
 /* ---- seed extension: the banded Smith-Waterman extensions of mem_chain2aln_across_reads_V2 (mapping/comp_seed.cpp:1319), i.e.
  *      what the reference hands to BandedPairWiseSW::getScores8 / getScores16 / scalarBandedSWAWrapper (mapping/bandedSWA.h:117-167; call sites

@@ -2,7 +2,8 @@
 reference (tests/golden/g1, 220 kbp: every read has a true locus, many have repeats) with substitutions and short indels, through
 GPU seeding -> cs_chain_batch -> cs_chain_filter -> cs_extend_chains -> cs_dedup_regions; wall time and reads/s per stage.  Beside the host
 chain row: the device chainer on the same reads, cs_chain_batch_gpu (host arrays) and cs_chain_batch_device (on a second, device-resident
-seeding of the batch), both checked equal to the host chains over the whole batch.
+seeding of the batch), both checked equal to the host chains over the whole batch.  Beside the host chain_filter row: the device filter,
+cs_chain_filter_device (fed by the device chain call's result) and cs_chain_filter_gpu (host arrays), both checked equal to the host filter.
 usage: align_bench.py [reads] [--synth-mbp M]"""
 import gzip, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,8 +64,9 @@ def run(n=200000, synth_mbp=0.0):
     d_b, d_o = eng.alloc(bases.nbytes), eng.alloc(off.nbytes)
     eng.upload(d_b, bases); eng.upload(d_o, off); eng.sync()
     out = {"reads": n, "reference": ("synthetic %g Mbp" % synth_mbp) if synth_mbp > 0 else "tests/golden/g1 (220 kbp, tandem arrays)"}
-    def same(a, b):
-        return all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in ("chain_off", "chains", "cseed_off", "cseeds"))
+    def same(a, b, keys=("chain_off", "chains", "cseed_off", "cseeds")):
+        return all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in keys)
+    FK = ("chain_off", "chains", "cseed_off", "cseeds", "cseed_score")
     for rep in range(2):   # the second round is the measured one (buffers sized)
         t0 = time.perf_counter(); res = eng.seed_batch(bases, off, ca.Params(), copy=False); t1 = time.perf_counter()
         c = ch.chain(res.mem_off, res.mems, res.seed_off, res.seeds, off, ca.ChainParams(), threads=16, copy=False); t2 = time.perf_counter()
@@ -79,12 +81,22 @@ def run(n=200000, synth_mbp=0.0):
         rd = eng.seed_batch_device(d_b, d_o, n, bases.size, ca.Params())
         sd0 = chd.stats(); t8 = time.perf_counter(); dd = chd.chain_device(rd, d_o, ca.ChainParams()); t9 = time.perf_counter(); sd1 = chd.stats()
         assert same(ca.download_chains(eng, dd), c), "cs_chain_batch_device differs from cs_chain_batch"
+        # the chain filter on the GPU: from the device chain call's result, then host arrays in and out
+        fs0 = chd.filter_stats(); t10 = time.perf_counter(); fd = chd.filter_device(dd, d_b, d_o); t11 = time.perf_counter(); fs1 = chd.filter_stats()
+        assert same(ca.download_chains(eng, fd), f, FK), "cs_chain_filter_device differs from cs_chain_filter"
+        t12 = time.perf_counter(); fg = chd.filter_gpu(c["chain_off"], c["chains"], c["cseed_off"], c["cseeds"], bases, off, copy=False); t13 = time.perf_counter()
+        assert same(fg, f, FK), "cs_chain_filter_gpu differs from cs_chain_filter"
     for name, a, b in (("seed (host call)", t0, t1), ("chain", t1, t2), ("chain_filter", t2, t3), ("extend_chains", t3, t4), ("dedup_regions", t4, t5)):
         out[name] = {"ms": 1e3 * (b - a), "reads_per_s": n / (b - a)}
     kms = sd1["kernel_ms"] - sd0["kernel_ms"]
     out["chain_device"] = {"ms": 1e3 * (t9 - t8), "reads_per_s": n / (t9 - t8), "kernel_ms": kms, "kernel_reads_per_s": n / (kms * 1e-3) if kms > 0 else None,
                            "tree_reads": sd1["tree_reads"] - sd0["tree_reads"], "launches": sd1["launches"] - sd0["launches"], "equal_to_host_chains": True}
     out["chain_gpu"] = {"ms": 1e3 * (t7 - t6), "reads_per_s": n / (t7 - t6), "equal_to_host_chains": True, "note": "host arrays in and out: PCIe-bound"}
+    kms = fs1["kernel_ms"] - fs0["kernel_ms"]
+    out["chain_filter (device)"] = {"ms": 1e3 * (t11 - t10), "reads_per_s": n / (t11 - t10), "kernel_ms": kms, "wave_reads": fs1["wave_reads"] - fs0["wave_reads"],
+                                    "spill_reads": fs1["spill_reads"] - fs0["spill_reads"], "sw_seeds": fs1["sw_seeds"] - fs0["sw_seeds"], "launches": fs1["launches"] - fs0["launches"],
+                                    "equal_to_host_filter": True}
+    out["chain_filter (gpu, host arrays)"] = {"ms": 1e3 * (t13 - t12), "reads_per_s": n / (t13 - t12), "equal_to_host_filter": True, "note": "host arrays in and out: PCIe-bound"}
     out["counts"] = {"seeds": int(res.n_seeds), "chains": int(c["chains"].size), "chains_after_filter": int(f["chains"].size), "regions": int(g["regs"].size),
                      "regions_after_dedup": int(d["regs"].size), "extensions": int(st1["pairs"] - st0["pairs"]), "ext_launches": int(st1["launches"] - st0["launches"])}
     per_read = np.diff(np.asarray(g["reg_off"]).astype(np.int64))

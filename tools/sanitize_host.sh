@@ -9,7 +9,7 @@ make -C $S -j4 all > /dev/null
 for f in refseq reader chain chain_filter align dedup host_pack; do
 	/opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off -Wno-option-ignored -DCS_FLT_SELFCHECK -c -o $O/$f.o $S/$f.cpp &
 done; wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -fsanitize=address,undefined -shared-libasan -Wno-option-ignored -o $O/libcompseed_amd_asan.so $S/build/engine.o $S/build/seed_pass.o $S/build/pipelines.o $S/build/inspect.o $S/build/index_build.o $S/build/extend.o $S/build/align_gpu.o $S/build/chain_gpu.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -fsanitize=address,undefined -shared-libasan -Wno-option-ignored -o $O/libcompseed_amd_asan.so $S/build/engine.o $S/build/seed_pass.o $S/build/pipelines.o $S/build/inspect.o $S/build/index_build.o $S/build/extend.o $S/build/align_gpu.o $S/build/chain_gpu.o $S/build/chain_filter_gpu.o \
 	$O/refseq.o $O/reader.o $O/chain.o $O/chain_filter.o $O/align.o $O/dedup.o $O/host_pack.o -lz
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so)
 cd $R
