@@ -21,7 +21,7 @@ SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", 
            "cs_engine_extend", "cs_engine_sa", "cs_engine_probe_random_lines", "cs_device_alloc", "cs_device_free", "cs_device_upload",
            "cs_device_download", "cs_device_sync", "cs_packed_seed_rbeg", "cs_engine_check_index",
            "cs_ext_params_default", "cs_extender_create", "cs_extender_destroy", "cs_extend_batch", "cs_extend_batch_device", "cs_extender_stats",
-           "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats"]
+           "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_extend_chains_device", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats"]
 
 
 class CSError(RuntimeError):
@@ -189,6 +189,7 @@ class FltStats(C.Structure):
 
 FLT_WAVE_ONLY = 1     # CS_FLT_WAVE_ONLY: every read through the wave-per-read path of the device chain filter (A/B switch, same results)
 CHAIN_TREE_ONLY = 1   # CS_CHAIN_TREE_ONLY: every read through the B-tree path of the device chainer (A/B switch, same results)
+ALN_DEV_COMPACT = 1   # CS_ALN_DEV_COMPACT: cs_extend_chains_device leaves the purged regions (qe <= qb) behind on the device
 
 
 class ExtStats(C.Structure):
@@ -372,6 +373,7 @@ def load_library():
     L.cs_aligner_destroy.argtypes = [vp]
     L.cs_aligner_destroy.restype = None
     L.cs_extend_chains.argtypes = [vp, C.POINTER(CChainResult), vp, vp, vp, C.POINTER(CAlnResult)]
+    L.cs_extend_chains_device.argtypes = [vp, C.POINTER(CChainResult), vp, vp, vp, C.c_uint32, C.POINTER(CAlnResult)]
     L.cs_aligner_stats.argtypes = [vp, C.POINTER(AlnStats)]
     L.cs_dedup_params_default.argtypes = [C.POINTER(DedupParams)]
     L.cs_dedup_params_default.restype = None
@@ -648,6 +650,13 @@ def download_chains(engine, d):
     if "cseed_score" in d:
         out["cseed_score"] = get(d["cseed_score"], np.int32, d["n_seeds"])
     return out
+
+
+def download_regions(engine, d):
+    """Aligner.extend_chains_device's result -> extend_chains()'s dict of host arrays (reg_off uint64, regs ALNREG_DT), through an Engine on
+    the same GPU"""
+    return dict(reg_off=engine.download(d["reg_off"], np.uint64, d["n_reads"] + 1),
+                regs=engine.download(d["regs"], ALNREG_DT, d["n_regs"]) if d["n_regs"] else np.zeros(0, dtype=ALNREG_DT))
 
 
 def build_index_from_fasta(fasta, prefix, device=0):
@@ -963,6 +972,20 @@ class Aligner:
         out = CAlnResult()
         _check(self.L.cs_extend_chains(self.h, C.byref(cr), sc.ctypes.data if sc is not None and sc.size else None, bases.ctypes.data if bases.size else None, ro.ctypes.data, C.byref(out)))
         return dict(reg_off=_view(out.reg_off, "<u8", int(out.n_reads) + 1, copy), regs=_view(out.regs, ALNREG_DT, int(out.n_regs), copy))
+
+    def extend_chains_device(self, d_chains, d_bases, d_read_offsets, d_cseed_score=None, flags=0):
+        """cs_extend_chains_device: Chainer.filter_device's / chain_device's dict and the batch's reads and offsets in device memory
+        (d_cseed_score defaults to the dict's own cseed_score, if it has one) -> dict(n_reads, n_regs, reg_off, regs): host counts and
+        device pointers owned by the aligner, valid until its next extend_chains / extend_chains_device (download_regions() brings them
+        over); flags: ALN_DEV_COMPACT"""
+        d = d_chains
+        if d_cseed_score is None:
+            d_cseed_score = d.get("cseed_score")
+        cin = CChainResult(d["n_reads"], d["n_chains"], d["n_seeds"], d["chain_off"], d["chains"], d["cseed_off"], d["cseeds"])
+        out = CAlnResult()
+        _check(self.L.cs_extend_chains_device(self.h, C.byref(cin), C.c_void_p(d_cseed_score or None), C.c_void_p(d_bases or None), C.c_void_p(d_read_offsets or None),
+                                              int(flags), C.byref(out)))
+        return dict(n_reads=int(out.n_reads), n_regs=int(out.n_regs), reg_off=out.reg_off, regs=out.regs)
 
     def dedup_regions(self, reg_off, regs, bases, read_offsets, params=None, copy=True):
         """cs_dedup_regions (purged regions dropped, mem_sort_dedup_patch): regions as extend_chains returns them -> dict(reg_off, regs, n_comp), copies"""

@@ -1,5 +1,5 @@
 // align.cpp -- the aligner object behind chaining (SURVEY 8f row 4 as a whole): cs_aligner_create / destroy / stats, the argument checks
-// of cs_extend_chains (whose work -- mem_chain2aln_across_reads_V2, mapping/comp_seed.cpp:1319-2237 -- runs on the GPU: align_gpu.hip around
+// of cs_extend_chains and cs_extend_chains_device (whose work -- mem_chain2aln_across_reads_V2, mapping/comp_seed.cpp:1319-2237 -- runs on the GPU: align_gpu.hip around
 // extend.hip) and cs_dedup_regions (dedup.cpp).  Sequences are laid out so that NO per-pair copy is made: the query buffer holds every
 // read once forward and once reversed, the target buffer every chain's reference window once forward and once reversed, and a pair is
 // four numbers.  Results are the reference's regions field by field (tests/golden/aln1, flt1, ddp1; tests/test_gpu_align.py).
@@ -82,6 +82,21 @@ extern "C" int cs_extend_chains(cs_aligner_t *A, const cs_chain_result_t *chains
 	if (rc != CS_OK) return rc;
 	out->n_reads = chains->n_reads; out->n_regs = A->regs.size(); out->reg_off = A->reg_off.data(); out->regs = A->regs.data();
 	return CS_OK;
+}
+
+// the same stage over device-resident chains: only what the host can know is checked here, the arrays are checked by kernels (align_gpu.hip)
+extern "C" int cs_extend_chains_device(cs_aligner_t *A, const cs_chain_result_t *d_chains, const int32_t *d_cseed_score, const uint8_t *d_bases,
+                                       const uint64_t *d_read_offsets, uint32_t flags, cs_aln_result_t *d_out)
+{
+	if (!A || !d_chains || !d_out) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: null argument");
+	if (flags & ~CS_ALN_DEV_COMPACT) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: unknown flags");
+	if (d_chains->n_reads < 0 || (d_chains->n_reads > 0 && (!d_read_offsets || !d_chains->chain_off)) || (d_chains->n_chains > 0 && (!d_chains->chains || !d_chains->cseed_off)) ||
+	    (d_chains->n_seeds > 0 && (!d_chains->cseeds || !d_bases)))
+		return cs_fail_(CS_EINVAL, "cs_extend_chains_device: bad argument");
+	if (!A->ext) return cs_fail_(CS_EDEVICE, "cs_extend_chains_device: this aligner was created without a device (device -1): the extension runs on the GPU only");
+	if (A->par.pen_clip5 != A->par.pen_clip3) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: pen_clip5 != pen_clip3 is not supported yet (one extender, one end bonus)");
+	if (d_chains->n_seeds >= 0x7fffffffull || d_chains->n_chains >= 0xffffffffull) return cs_fail_(CS_ERANGE, "cs_extend_chains_device: more than 2^31 regions in one call");
+	return cs_extend_chains_device_gpu_(&A->gpu, A->device, A->ext, A->ref, A->pac, A->par, d_chains, d_cseed_score, d_bases, d_read_offsets, flags, d_out, A->st);
 }
 
 extern "C" int cs_dedup_regions(cs_aligner_t *A, const cs_dedup_params_t *par, const cs_aln_result_t *regs, const uint8_t *bases, const uint64_t *read_offsets,

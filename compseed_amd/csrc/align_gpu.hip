@@ -435,6 +435,55 @@ __global__ __launch_bounds__(PB) void purge_big_kernel(const Args A, uint8_t *pf
 	}
 	if (lane == 0 && my) atomicAdd(A.ctr + 4, my);
 }
+
+// ---- cs_extend_chains_device.  The caller's arrays are device memory that no host loop has seen, so what cs_extend_chains' host loops
+// refuse is counted by two kernels that follow no offset themselves -- a lane reads its own two entries of an offset array and compares
+// them with each other and with the host counts --, the host waits for the counter, and only then do reg_off_kernel and the kernels above
+// index one array by another (the way chain_filter_gpu.hip goes about it).  Beyond the host's conditions: read_off starts at 0 and does
+// not decrease (query_kernel's search and read lengths rest on it), a read with chains is shorter than MAX_READ_LEN, and both offset arrays
+// run from 0 to their count -- a chain no read owns has no chain_read entry, a seed no chain owns no region, and the kernels above read both.
+constexpr uint64_t MAX_READ_LEN = 65536;
+struct DevIn { const uint64_t *chain_off, *cseed_off, *read_off; const cs_chain_t *chains; int64_t n_reads; uint64_t n_chains, n_seeds; };
+__global__ void check_reads_kernel(const DevIn D, unsigned long long *bad)
+{
+	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < D.n_reads; r += (int64_t)gridDim.x * blockDim.x) {
+		const uint64_t c0 = D.chain_off[r], c1 = D.chain_off[r + 1], b0 = D.read_off[r], b1 = D.read_off[r + 1];
+		if (c1 < c0 || c1 > D.n_chains || b1 < b0 || (r == 0 && (b0 != 0 || c0 != 0)) || (r == D.n_reads - 1 && c1 != D.n_chains) || (c1 > c0 && b1 - b0 >= MAX_READ_LEN)) atomicAdd(bad, 1ull);
+	}
+}
+__global__ void check_chains_kernel(const DevIn D, unsigned long long *bad)
+{
+	for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < D.n_chains; c += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t s0 = D.cseed_off[c], s1 = D.cseed_off[c + 1];
+		if (s1 < s0 || s1 > D.n_seeds || (int64_t)(s1 - s0) != (int64_t)D.chains[c].n_seeds || (c == 0 && s0 != 0) || (c == D.n_chains - 1 && s1 != D.n_seeds)) atomicAdd(bad, 1ull);
+	}
+}
+__global__ void reg_off_kernel(const DevIn D, uint64_t *reg_off) // a read's regions start where its first chain's seeds start; entry n_reads: the total
+{
+	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= D.n_reads; r += (int64_t)gridDim.x * blockDim.x) reg_off[r] = D.cseed_off[D.chain_off[r]];
+}
+// CS_ALN_DEV_COMPACT: the regions the purge marked (qe <= qb: what comp_seed.cpp:2387-2393 drops) stay behind.  live[g], an exclusive scan
+// over n_seeds + 1 flags (the last one 0: the total), then the live regions move as 8-byte words, a word per lane -- 7 words a region, so
+// a wave reads 512 contiguous bytes and writes runs of them -- into a buffer of their own, and reg_off[r] becomes scan[reg_off[r]].
+constexpr int REG_WORDS = (int)(sizeof(cs_alnreg_t) / 8);
+static_assert(sizeof(cs_alnreg_t) == 56 && REG_WORDS * 8 == (int)sizeof(cs_alnreg_t), "cs_alnreg_t is seven 8-byte words");
+__global__ void live_kernel(const cs_alnreg_t *regs, uint64_t n, uint32_t *live)
+{
+	for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= n; g += (uint64_t)gridDim.x * blockDim.x) live[g] = g < n && regs[g].qe > regs[g].qb ? 1u : 0u;
+}
+__global__ void scatter_kernel(const uint64_t *in, uint64_t n, const uint32_t *live, const uint32_t *scan, uint64_t *out)
+{
+	const uint64_t n_words = n * REG_WORDS;
+	for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_words; t += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t g = t / REG_WORDS;
+		if (live[g]) out[(uint64_t)scan[g] * REG_WORDS + (t - g * REG_WORDS)] = in[t];
+	}
+}
+__global__ void reg_off_live_kernel(uint64_t *reg_off, int64_t n_reads, const uint32_t *scan, uint64_t n, unsigned long long *n_live) // in place: a lane reads and writes its own entry
+{
+	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n_reads; r += (int64_t)gridDim.x * blockDim.x) reg_off[r] = scan[reg_off[r]];
+	if (blockIdx.x == 0 && threadIdx.x == 0) *n_live = scan[n];
+}
 } // namespace csa
 
 namespace {
@@ -450,7 +499,9 @@ int ensure(Buf &b, size_t bytes)
 	return CS_OK;
 }
 enum { B_CHAIN_OFF, B_CSEED_OFF, B_READ_OFF, B_CHAINS, B_CSEEDS, B_SCORE, B_BASES, B_PAC, B_CTG_OFF, B_CTG_LEN, B_CHAIN_READ, B_W0, B_WLEN2, B_TB0, B_QBUF, B_TBUF, B_ORD, B_REGS,
-       B_REG_CI, B_LP, B_RP, B_RETRY, B_RES, B_CTR, B_SCAN, B_PFLAG, B_BIG, B_BIG_READS, B_COUNT };
+       B_REG_CI, B_LP, B_RP, B_RETRY, B_RES, B_CTR, B_SCAN, B_PFLAG, B_BIG, B_BIG_READS,
+       B_O_REG_OFF, B_O_REGS, B_LIVE, B_LSCAN,   // cs_extend_chains_device: reg_off, the compacted regions, the live flags and their scan
+       B_COUNT };
 } // namespace
 
 struct cs_aligner_gpu { int device = 0, n_cu = 256; hipStream_t s = nullptr; Buf b[B_COUNT]; bool pac_up = false; unsigned long long *h_ctr = nullptr; };
@@ -466,54 +517,62 @@ void cs_aligner_gpu_release_(cs_aligner_gpu *g)
 	delete g;
 }
 
-int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, const cs_refseq_view &R, const std::vector<uint8_t> &pac, const cs_aln_params_t &o,
-                          const cs_chain_result_t *chains, const int32_t *cseed_score, const uint8_t *bases, const uint64_t *read_offsets,
-                          std::vector<uint64_t> &reg_off, std::vector<cs_alnreg_t> &regs, cs_aln_stats_t &st)
+namespace {
+// -DCS_ALIGN_TIMING: the laps of a call on stderr (each one waits for the stream)
+struct Lap {
+#ifdef CS_ALIGN_TIMING
+	hipStream_t s; const char *who; std::chrono::steady_clock::time_point t_last;
+	Lap(hipStream_t s_, const char *who_) : s(s_), who(who_), t_last(std::chrono::steady_clock::now()) {}
+	void operator()(const char *what) { (void)hipStreamSynchronize(s); const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[%s] %-28s %8.1f ms\n", who, what, std::chrono::duration<double, std::milli>(t - t_last).count()); t_last = t; }
+#else
+	Lap(hipStream_t, const char *) {}
+	void operator()(const char *) {}
+#endif
+};
+dim3 grid_for(const cs_aligner_gpu &G, int64_t items, int per_block = 256) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)G.n_cu * 16))); }
+
+// the aligner's device state, made by its first call; the packed reference and the contig table go up once
+int gpu_state_(cs_aligner_gpu **gp, int device)
 {
 	HIP_TRYA(hipSetDevice(device));
-	if (!*gp) {
-		cs_aligner_gpu *g = new cs_aligner_gpu(); g->device = device; *gp = g;
-		hipDeviceProp_t prop;
-		if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) g->n_cu = prop.multiProcessorCount;
-		HIP_TRYA(hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking));
-		HIP_TRYA(hipHostMalloc((void **)&g->h_ctr, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-	}
-	cs_aligner_gpu &G = **gp;
+	if (*gp) return CS_OK;
+	cs_aligner_gpu *g = new cs_aligner_gpu(); g->device = device; *gp = g;
+	hipDeviceProp_t prop;
+	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) g->n_cu = prop.multiProcessorCount;
+	HIP_TRYA(hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking));
+	HIP_TRYA(hipHostMalloc((void **)&g->h_ctr, 8 * sizeof(unsigned long long), hipHostMallocDefault));
+	return CS_OK;
+}
+int up_(cs_aligner_gpu &G, int which, const void *src, size_t bytes)
+{
+	if (int rc = ensure(G.b[which], bytes + 64)) return rc;
+	if (bytes) HIP_TRYA(hipMemcpyAsync(G.b[which].p, src, bytes, hipMemcpyHostToDevice, G.s));
+	return CS_OK;
+}
+int ref_up_(cs_aligner_gpu &G, const cs_refseq_view &R, const std::vector<uint8_t> &pac)
+{
+	if (G.pac_up) return CS_OK;
+	std::vector<int64_t> co(R.offset.begin(), R.offset.end()); std::vector<int32_t> cl(R.len.begin(), R.len.end());
+	if (int rc = up_(G, B_PAC, pac.data(), pac.size())) return rc;
+	if (int rc = up_(G, B_CTG_OFF, co.data(), co.size() * 8)) return rc;
+	if (int rc = up_(G, B_CTG_LEN, cl.data(), cl.size() * 4)) return rc;
+	HIP_TRYA(hipStreamSynchronize(G.s));          // (co / cl are locals)
+	G.pac_up = true;
+	return CS_OK;
+}
+
+// a batch in device memory: the aligner's own uploads (cs_extend_chains) or the caller's arrays (cs_extend_chains_device)
+struct DevBatch { const uint64_t *chain_off, *cseed_off, *read_off; const cs_chain_t *chains; const cs_seed_t *cseeds; const int32_t *score; const uint8_t *bases;
+                  int64_t n, nc, ns; uint64_t n_bases; };
+
+// The stage itself, device pointers in: windows, regions, both sides' extensions, seed coverage, purge.  On return the regions lie in
+// B_REGS in the reference's order (the purge kernels may still be running on the stream) and ctr[4] counts the purged ones; the offsets
+// were found consistent by the caller (host loops or checking kernels), ns > 0 and the reference is up.
+int extend_core_(cs_aligner_gpu &G, cs_extender_t *ext, const cs_refseq_view &R, const cs_aln_params_t &o, const DevBatch &in, cs_aln_stats_t &st, Lap &lap, const char *who)
+{
 	hipStream_t s = G.s;
-#ifdef CS_ALIGN_TIMING
-	auto t_last = std::chrono::steady_clock::now();
-	auto lap = [&](const char *what) { (void)hipStreamSynchronize(s); const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[cs_extend_chains] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count()); t_last = t; };
-#else
-	auto lap = [](const char *) {};
-#endif
-	const int64_t n = chains->n_reads, nc = (int64_t)chains->n_chains, ns = (int64_t)chains->n_seeds;
-	reg_off.assign((size_t)n + 1, 0);                              // (regs keeps its size from call to call: growing a vector by 200 MB of zeroes took 6 ms per million reads)
-	for (int64_t r = 0; r < n; ++r) reg_off[(size_t)r + 1] = chains->cseed_off[chains->chain_off[r + 1]];
-	st.reads += (uint64_t)n;
-	if (ns == 0) { regs.clear(); return CS_OK; }
-	if (ns >= 0x7fffffffll || nc >= 0xffffffffll) return cs_fail_(CS_ERANGE, "cs_extend_chains: more than 2^31 regions in one call");
-	const uint64_t n_bases = read_offsets[n];
-	auto up = [&](int which, const void *src, size_t bytes) -> int {
-		if (int rc = ensure(G.b[which], bytes + 64)) return rc;
-		if (bytes) HIP_TRYA(hipMemcpyAsync(G.b[which].p, src, bytes, hipMemcpyHostToDevice, s));
-		return CS_OK;
-	};
-	if (int rc = up(B_CHAIN_OFF, chains->chain_off, ((size_t)n + 1) * 8)) return rc;
-	if (int rc = up(B_CSEED_OFF, chains->cseed_off, ((size_t)nc + 1) * 8)) return rc;
-	if (int rc = up(B_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
-	if (int rc = up(B_CHAINS, chains->chains, (size_t)nc * sizeof(cs_chain_t))) return rc;
-	if (int rc = up(B_CSEEDS, chains->cseeds, (size_t)ns * sizeof(cs_seed_t))) return rc;
-	if (cseed_score) { if (int rc = up(B_SCORE, cseed_score, (size_t)ns * 4)) return rc; }
-	if (int rc = up(B_BASES, bases, (size_t)n_bases)) return rc;
-	if (!G.pac_up) {
-		std::vector<int64_t> co(R.offset.begin(), R.offset.end()); std::vector<int32_t> cl(R.len.begin(), R.len.end());
-		if (int rc = up(B_PAC, pac.data(), pac.size())) return rc;
-		if (int rc = up(B_CTG_OFF, co.data(), co.size() * 8)) return rc;
-		if (int rc = up(B_CTG_LEN, cl.data(), cl.size() * 4)) return rc;
-		HIP_TRYA(hipStreamSynchronize(s));          // (co / cl are locals)
-		G.pac_up = true;
-	}
-	lap("uploads");
+	const int64_t n = in.n, nc = in.nc, ns = in.ns;
+	const uint64_t n_bases = in.n_bases;
 	for (int which : {B_CHAIN_READ, B_BIG}) if (int rc = ensure(G.b[which], (size_t)nc * 4 + 64)) return rc;
 	if (int rc = ensure(G.b[B_BIG_READS], (size_t)n * 4 + 64)) return rc;
 	for (int which : {B_W0, B_WLEN2, B_TB0}) if (int rc = ensure(G.b[which], ((size_t)nc + 1) * 8 + 64)) return rc;
@@ -526,9 +585,9 @@ int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, c
 	HIP_TRYA(hipMemsetAsync(G.b[B_CTR].p, 0, 8 * sizeof(unsigned long long), s));
 
 	csa::Args A;
-	A.chain_off = (const uint64_t *)G.b[B_CHAIN_OFF].p; A.cseed_off = (const uint64_t *)G.b[B_CSEED_OFF].p; A.read_off = (const uint64_t *)G.b[B_READ_OFF].p;
-	A.chains = (const cs_chain_t *)G.b[B_CHAINS].p; A.cseeds = (const cs_seed_t *)G.b[B_CSEEDS].p; A.score = cseed_score ? (const int32_t *)G.b[B_SCORE].p : nullptr;
-	A.bases = (const uint8_t *)G.b[B_BASES].p; A.n_reads = n; A.n_chains = nc; A.n_seeds = ns; A.l_pac = R.l_pac; A.n_bases = n_bases;
+	A.chain_off = in.chain_off; A.cseed_off = in.cseed_off; A.read_off = in.read_off;
+	A.chains = in.chains; A.cseeds = in.cseeds; A.score = in.score;
+	A.bases = in.bases; A.n_reads = n; A.n_chains = nc; A.n_seeds = ns; A.l_pac = R.l_pac; A.n_bases = n_bases;
 	A.pac = (const uint8_t *)G.b[B_PAC].p; A.ctg_off = (const int64_t *)G.b[B_CTG_OFF].p; A.ctg_len = (const int32_t *)G.b[B_CTG_LEN].p; A.n_ctg = (int32_t)R.offset.size();
 	A.o = o;
 	A.chain_read = (uint32_t *)G.b[B_CHAIN_READ].p; A.w0 = (int64_t *)G.b[B_W0].p; A.wlen2 = (uint64_t *)G.b[B_WLEN2].p; A.tb0 = (uint64_t *)G.b[B_TB0].p;
@@ -537,7 +596,7 @@ int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, c
 	A.big = (uint32_t *)G.b[B_BIG].p; A.big_reads = (uint32_t *)G.b[B_BIG_READS].p;
 	A.small_chain = (o.flags & CS_ALN_NO_LIGHT_PATHS) ? 0 : csa::SMALL_CHAIN; A.light_max = (o.flags & CS_ALN_NO_LIGHT_PATHS) ? 1 : 64;
 	A.purge_cap = (o.flags & CS_ALN_PURGE_FROM_HBM) ? 0 : csa::PURGE_CAP;
-	auto grid = [&](int64_t items, int per_block = 256) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)G.n_cu * 16))); };
+	auto grid = [&](int64_t items, int per_block = 256) { return grid_for(G, items, per_block); };
 
 	lap("buffers");
 	hipLaunchKernelGGL(csa::chain_read_kernel, grid(n), dim3(256), 0, s, A);
@@ -554,7 +613,7 @@ int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, c
 	HIP_TRYA(hipMemcpyAsync(G.h_ctr, A.tb0 + nc, 8, hipMemcpyDeviceToHost, s));
 	HIP_TRYA(hipMemcpyAsync(G.h_ctr + 1, A.ctr + 3, 8, hipMemcpyDeviceToHost, s));
 	HIP_TRYA(hipStreamSynchronize(s));
-	if (G.h_ctr[1]) return cs_fail_(CS_EINVAL, "cs_extend_chains: a chain's first seed lies outside the reference");
+	if (G.h_ctr[1]) return cs_fail_(CS_EINVAL, std::string(who) + ": a chain's first seed lies outside the reference");
 	lap("queries, windows, scan");
 	const uint64_t t_bytes = G.h_ctr[0];
 	if (int rc = ensure(G.b[B_TBUF], (size_t)t_bytes + 64)) return rc;
@@ -602,12 +661,106 @@ int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, c
 	hipLaunchKernelGGL(csa::purge_big_kernel, dim3((unsigned)G.n_cu), dim3(csa::PB), 0, s, A, (uint8_t *)G.b[B_PFLAG].p);
 	HIP_TRYA(hipGetLastError());
 	lap("purge");
+	return CS_OK;
+}
+} // namespace
+
+// cs_extend_chains: host arrays (checked by align.cpp's loops) up, the core, every region down
+int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, const cs_refseq_view &R, const std::vector<uint8_t> &pac, const cs_aln_params_t &o,
+                          const cs_chain_result_t *chains, const int32_t *cseed_score, const uint8_t *bases, const uint64_t *read_offsets,
+                          std::vector<uint64_t> &reg_off, std::vector<cs_alnreg_t> &regs, cs_aln_stats_t &st)
+{
+	if (int rc = gpu_state_(gp, device)) return rc;
+	cs_aligner_gpu &G = **gp;
+	hipStream_t s = G.s;
+	Lap lap(s, "cs_extend_chains");
+	const int64_t n = chains->n_reads, nc = (int64_t)chains->n_chains, ns = (int64_t)chains->n_seeds;
+	reg_off.assign((size_t)n + 1, 0);                              // (regs keeps its size from call to call: growing a vector by 200 MB of zeroes took 6 ms per million reads)
+	for (int64_t r = 0; r < n; ++r) reg_off[(size_t)r + 1] = chains->cseed_off[chains->chain_off[r + 1]];
+	st.reads += (uint64_t)n;
+	if (ns == 0) { regs.clear(); return CS_OK; }
+	if (ns >= 0x7fffffffll || nc >= 0xffffffffll) return cs_fail_(CS_ERANGE, "cs_extend_chains: more than 2^31 regions in one call");
+	const uint64_t n_bases = read_offsets[n];
+	if (int rc = up_(G, B_CHAIN_OFF, chains->chain_off, ((size_t)n + 1) * 8)) return rc;
+	if (int rc = up_(G, B_CSEED_OFF, chains->cseed_off, ((size_t)nc + 1) * 8)) return rc;
+	if (int rc = up_(G, B_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
+	if (int rc = up_(G, B_CHAINS, chains->chains, (size_t)nc * sizeof(cs_chain_t))) return rc;
+	if (int rc = up_(G, B_CSEEDS, chains->cseeds, (size_t)ns * sizeof(cs_seed_t))) return rc;
+	if (cseed_score) { if (int rc = up_(G, B_SCORE, cseed_score, (size_t)ns * 4)) return rc; }
+	if (int rc = up_(G, B_BASES, bases, (size_t)n_bases)) return rc;
+	if (int rc = ref_up_(G, R, pac)) return rc;
+	lap("uploads");
+	const DevBatch in = {(const uint64_t *)G.b[B_CHAIN_OFF].p, (const uint64_t *)G.b[B_CSEED_OFF].p, (const uint64_t *)G.b[B_READ_OFF].p, (const cs_chain_t *)G.b[B_CHAINS].p,
+	                     (const cs_seed_t *)G.b[B_CSEEDS].p, cseed_score ? (const int32_t *)G.b[B_SCORE].p : nullptr, (const uint8_t *)G.b[B_BASES].p, n, nc, ns, n_bases};
+	if (int rc = extend_core_(G, ext, R, o, in, st, lap, "cs_extend_chains")) return rc;
 	regs.resize((size_t)ns);
 	lap("host resize");
-	HIP_TRYA(hipMemcpyAsync(regs.data(), A.regs, (size_t)ns * sizeof(cs_alnreg_t), hipMemcpyDeviceToHost, s));
-	HIP_TRYA(hipMemcpyAsync(G.h_ctr, A.ctr + 4, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRYA(hipMemcpyAsync(regs.data(), G.b[B_REGS].p, (size_t)ns * sizeof(cs_alnreg_t), hipMemcpyDeviceToHost, s));
+	HIP_TRYA(hipMemcpyAsync(G.h_ctr, (unsigned long long *)G.b[B_CTR].p + 4, 8, hipMemcpyDeviceToHost, s));
 	HIP_TRYA(hipStreamSynchronize(s));
 	lap("download");
 	st.purged += G.h_ctr[0]; st.regions += (uint64_t)ns;
+	return CS_OK;
+}
+
+// cs_extend_chains_device: the caller's device arrays, checked by kernels; the core; reg_off and (CS_ALN_DEV_COMPACT) the live regions
+// made on the device.  Host round trips of its own: the checks' counter with n_bases, and at the end the purge counter with n_regs.
+int cs_extend_chains_device_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, const cs_refseq_view &R, const std::vector<uint8_t> &pac, const cs_aln_params_t &o,
+                                 const cs_chain_result_t *d_chains, const int32_t *d_cseed_score, const uint8_t *d_bases, const uint64_t *d_read_offsets, uint32_t flags,
+                                 cs_aln_result_t *d_out, cs_aln_stats_t &st)
+{
+	if (int rc = gpu_state_(gp, device)) return rc;
+	cs_aligner_gpu &G = **gp;
+	hipStream_t s = G.s;
+	Lap lap(s, "cs_extend_chains_device");
+	const int64_t n = d_chains->n_reads, nc = (int64_t)d_chains->n_chains, ns = (int64_t)d_chains->n_seeds;
+	if (int rc = ensure(G.b[B_O_REG_OFF], ((size_t)n + 1) * 8)) return rc;
+	if (int rc = ensure(G.b[B_CTR], 8 * sizeof(unsigned long long))) return rc;
+	unsigned long long *ctr = (unsigned long long *)G.b[B_CTR].p;
+	uint64_t *reg_off = (uint64_t *)G.b[B_O_REG_OFF].p;
+	if ((n == 0 && nc > 0) || (nc == 0 && ns > 0)) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: chains without reads or seeds without chains");
+	const csa::DevIn D = {d_chains->chain_off, d_chains->cseed_off, d_read_offsets, d_chains->chains, n, (uint64_t)nc, (uint64_t)ns};
+	// [0] what the checks refuse, [1] n_bases = read_offsets[n_reads]: one small copy, one wait
+	HIP_TRYA(hipMemsetAsync(ctr, 0, 8 * sizeof(unsigned long long), s));
+	if (n > 0) hipLaunchKernelGGL(csa::check_reads_kernel, grid_for(G, n), dim3(256), 0, s, D, ctr);
+	if (nc > 0) hipLaunchKernelGGL(csa::check_chains_kernel, grid_for(G, nc), dim3(256), 0, s, D, ctr);
+	HIP_TRYA(hipGetLastError());
+	if (n > 0) HIP_TRYA(hipMemcpyAsync(ctr + 1, d_read_offsets + n, 8, hipMemcpyDeviceToDevice, s));
+	HIP_TRYA(hipMemcpyAsync(G.h_ctr, ctr, 2 * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRYA(hipStreamSynchronize(s));
+	if (G.h_ctr[0]) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: chain_off / cseed_off are not CSR offset arrays from 0 to n_chains / n_seeds that match the chains' seed counts, read_offsets do not start at 0 or decrease, or a read with chains has 65,536 bases or more");
+	const uint64_t n_bases = G.h_ctr[1];
+	lap("checks");
+	if (n > 0 && nc > 0) { hipLaunchKernelGGL(csa::reg_off_kernel, grid_for(G, n + 1), dim3(256), 0, s, D, reg_off); HIP_TRYA(hipGetLastError()); }
+	else HIP_TRYA(hipMemsetAsync(reg_off, 0, ((size_t)n + 1) * 8, s));
+	st.reads += (uint64_t)n;
+	d_out->n_reads = n; d_out->n_regs = 0; d_out->reg_off = reg_off; d_out->regs = (const cs_alnreg_t *)G.b[B_REGS].p;
+	if (ns == 0) { HIP_TRYA(hipStreamSynchronize(s)); return CS_OK; }
+	if (int rc = ref_up_(G, R, pac)) return rc;
+	const DevBatch in = {d_chains->chain_off, d_chains->cseed_off, d_read_offsets, d_chains->chains, d_chains->cseeds, d_cseed_score, d_bases, n, nc, ns, n_bases};
+	if (int rc = extend_core_(G, ext, R, o, in, st, lap, "cs_extend_chains_device")) return rc;
+	ctr = (unsigned long long *)G.b[B_CTR].p;
+	const cs_alnreg_t *regs = (const cs_alnreg_t *)G.b[B_REGS].p;
+	if (flags & CS_ALN_DEV_COMPACT) {
+		for (int which : {B_LIVE, B_LSCAN}) if (int rc = ensure(G.b[which], ((size_t)ns + 1) * 4)) return rc;
+		if (int rc = ensure(G.b[B_O_REGS], (size_t)ns * sizeof(cs_alnreg_t))) return rc;
+		uint32_t *live = (uint32_t *)G.b[B_LIVE].p, *scan = (uint32_t *)G.b[B_LSCAN].p;
+		hipLaunchKernelGGL(csa::live_kernel, grid_for(G, ns + 1), dim3(256), 0, s, regs, (uint64_t)ns, live);
+		HIP_TRYA(hipGetLastError());
+		size_t tb = 0;
+		HIP_TRYA(rocprim::exclusive_scan(nullptr, tb, live, scan, (uint32_t)0, (size_t)ns + 1, rocprim::plus<uint32_t>(), s));
+		if (int rc = ensure(G.b[B_SCAN], tb + 16)) return rc;
+		HIP_TRYA(rocprim::exclusive_scan(G.b[B_SCAN].p, tb, live, scan, (uint32_t)0, (size_t)ns + 1, rocprim::plus<uint32_t>(), s));
+		hipLaunchKernelGGL(csa::scatter_kernel, grid_for(G, ns * csa::REG_WORDS), dim3(256), 0, s, (const uint64_t *)regs, (uint64_t)ns, (const uint32_t *)live, (const uint32_t *)scan, (uint64_t *)G.b[B_O_REGS].p);
+		hipLaunchKernelGGL(csa::reg_off_live_kernel, grid_for(G, n + 1), dim3(256), 0, s, reg_off, n, (const uint32_t *)scan, (uint64_t)ns, ctr + 5);   // ([5], the long chains' count, has served)
+		HIP_TRYA(hipGetLastError());
+		lap("compaction");
+	}
+	HIP_TRYA(hipMemcpyAsync(G.h_ctr, ctr + 4, 2 * 8, hipMemcpyDeviceToHost, s));   // [4] purged, [5] live regions
+	HIP_TRYA(hipStreamSynchronize(s));
+	lap("counters");
+	st.purged += G.h_ctr[0]; st.regions += (uint64_t)ns;
+	if (flags & CS_ALN_DEV_COMPACT) { d_out->n_regs = G.h_ctr[1]; d_out->regs = (const cs_alnreg_t *)G.b[B_O_REGS].p; }
+	else { d_out->n_regs = (uint64_t)ns; d_out->regs = regs; }
 	return CS_OK;
 }

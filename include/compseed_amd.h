@@ -432,6 +432,23 @@ int  cs_aligner_create(const char *prefix, int device /* -1: host-side passes on
 void cs_aligner_destroy(cs_aligner_t *a);
 int  cs_extend_chains(cs_aligner_t *a, const cs_chain_result_t *chains, const int32_t *cseed_score, const uint8_t *bases,
                       const uint64_t *read_offsets, cs_aln_result_t *out);
+/* The same stage over device-resident chains: `d_chains` is a chain result as cs_chain_filter_device or cs_chain_batch_device returns it
+ * (device pointers on the aligner's GPU, host counts), `d_cseed_score` (may be NULL: score = len), `d_bases` and `d_read_offsets` are
+ * device memory; inputs must be COMPLETE when the call is made, as for the other device calls, and are not written.  `d_out->reg_off`
+ * (n_reads + 1) and `d_out->regs` are device arrays owned by the aligner, complete when the call returns and valid until the aligner's
+ * next cs_extend_chains or cs_extend_chains_device; n_reads and n_regs are host values.  flags 0: byte for byte what cs_extend_chains
+ * returns for the same chains (purged regions as qb = qe = -1, reg_off[r] = cseed_off[chain_off[r]]).  CS_ALN_DEV_COMPACT: the purged
+ * regions are left behind on the device -- each read's regions with qe > qb in unchanged order, reg_off counts them, n_regs is their
+ * number -- which is what cs_dedup_regions drops first anyway.  cs_aln_params_t.flags keep their meaning, and the call adds to the same
+ * cs_aln_stats_t counters (`regions` counts the regions before compaction).  Errors, in this order: a NULL `a`, `d_chains` or `d_out`
+ * or unknown flag bits CS_EINVAL; cs_extend_chains' pointer conditions, read as device pointers, CS_EINVAL; an aligner created with device
+ * -1 CS_EDEVICE; pen_clip5 != pen_clip3 CS_EINVAL; 2^31 seeds or more CS_ERANGE; inconsistent device input -- chain_off / cseed_off that
+ * are not CSR offset arrays from 0 to n_chains / n_seeds or disagree with the chains' n_seeds, read_offsets that do not start at 0 or decrease, a read with chains of
+ * 65,536 bases or more -- CS_EINVAL, found by checking kernels before any kernel follows an offset; a chain whose first seed lies outside
+ * the reference CS_EINVAL.  After any error the aligner is usable for the next call. */
+#define CS_ALN_DEV_COMPACT 1u   /* drop the regions with qe <= qb on the device (comp_seed.cpp:2387-2393) */
+int  cs_extend_chains_device(cs_aligner_t *a, const cs_chain_result_t *d_chains, const int32_t *d_cseed_score /* may be NULL: score = len */,
+                             const uint8_t *d_bases, const uint64_t *d_read_offsets, uint32_t flags, cs_aln_result_t *d_out);
 /* The pass behind the extension stage (comp_seed.cpp:2385-2395), host code: regions marked by the purge (qe <= qb) are dropped and
  * mem_sort_dedup_patch (comp_seed.cpp:629-687) runs over each read's rest -- of two regions that overlap by more than mask_level_redun on
  * read and reference the lower-scoring one goes; colinear neighbours close to one diagonal are merged when a banded global alignment over

@@ -4,6 +4,8 @@ GPU seeding -> cs_chain_batch -> cs_chain_filter -> cs_extend_chains -> cs_dedup
 chain row: the device chainer on the same reads, cs_chain_batch_gpu (host arrays) and cs_chain_batch_device (on a second, device-resident
 seeding of the batch), both checked equal to the host chains over the whole batch.  Beside the host chain_filter row: the device filter,
 cs_chain_filter_device (fed by the device chain call's result) and cs_chain_filter_gpu (host arrays), both checked equal to the host filter.
+Beside the host extend_chains row: cs_extend_chains_device on the device filter's result, with every region kept and with the purged ones
+left behind (CS_ALN_DEV_COMPACT), each with the time download_regions takes; checked equal to the host call's regions / its regions with qe > qb.
 usage: align_bench.py [reads] [--synth-mbp M]"""
 import gzip, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,6 +63,7 @@ def run(n=200000, synth_mbp=0.0):
         bases = np.ascontiguousarray(reads.reshape(-1)); off = (np.arange(n + 1, dtype=np.uint64) * np.uint64(L))
     ix = ca.Index.load(PREFIX); eng = ca.Engine(ix, 0); ch = ca.Chainer(PREFIX); al = ca.Aligner(PREFIX, 0)
     chd = ca.Chainer(PREFIX, device=0)   # the device chainer (cs_chain_batch_device / cs_chain_batch_gpu)
+    ald = ca.Aligner(PREFIX, 0)          # the aligner of the device rows (cs_extend_chains_device), buffers of its own
     d_b, d_o = eng.alloc(bases.nbytes), eng.alloc(off.nbytes)
     eng.upload(d_b, bases); eng.upload(d_o, off); eng.sync()
     out = {"reads": n, "reference": ("synthetic %g Mbp" % synth_mbp) if synth_mbp > 0 else "tests/golden/g1 (220 kbp, tandem arrays)"}
@@ -84,6 +87,15 @@ def run(n=200000, synth_mbp=0.0):
         # the chain filter on the GPU: from the device chain call's result, then host arrays in and out
         fs0 = chd.filter_stats(); t10 = time.perf_counter(); fd = chd.filter_device(dd, d_b, d_o); t11 = time.perf_counter(); fs1 = chd.filter_stats()
         assert same(ca.download_chains(eng, fd), f, FK), "cs_chain_filter_device differs from cs_chain_filter"
+        # the extension stage on the device filter's result (before filter_gpu reuses its buffers): all regions, then the live ones only
+        xs0 = ald.stats(); t14 = time.perf_counter(); xd = ald.extend_chains_device(fd, d_b, d_o); t15 = time.perf_counter(); xs1 = ald.stats()
+        xr = ca.download_regions(eng, xd); t16 = time.perf_counter()
+        assert same(xr, g, ("reg_off", "regs")), "cs_extend_chains_device differs from cs_extend_chains"
+        t17 = time.perf_counter(); xc = ald.extend_chains_device(fd, d_b, d_o, flags=ca.ALN_DEV_COMPACT); t18 = time.perf_counter()
+        xcr = ca.download_regions(eng, xc); t19 = time.perf_counter()
+        hr = np.asarray(g["regs"]); live = hr["qe"] > hr["qb"]
+        live_off = np.concatenate(([0], np.cumsum(live))).astype(np.uint64)[np.asarray(g["reg_off"]).astype(np.int64)]
+        assert xc["n_regs"] == int(live.sum()) and same(xcr, {"reg_off": live_off, "regs": hr[live]}, ("reg_off", "regs")), "the compacted regions differ from cs_extend_chains' regions with qe > qb"
         t12 = time.perf_counter(); fg = chd.filter_gpu(c["chain_off"], c["chains"], c["cseed_off"], c["cseeds"], bases, off, copy=False); t13 = time.perf_counter()
         assert same(fg, f, FK), "cs_chain_filter_gpu differs from cs_chain_filter"
     for name, a, b in (("seed (host call)", t0, t1), ("chain", t1, t2), ("chain_filter", t2, t3), ("extend_chains", t3, t4), ("dedup_regions", t4, t5)):
@@ -97,6 +109,12 @@ def run(n=200000, synth_mbp=0.0):
                                     "spill_reads": fs1["spill_reads"] - fs0["spill_reads"], "sw_seeds": fs1["sw_seeds"] - fs0["sw_seeds"], "launches": fs1["launches"] - fs0["launches"],
                                     "equal_to_host_filter": True}
     out["chain_filter (gpu, host arrays)"] = {"ms": 1e3 * (t13 - t12), "reads_per_s": n / (t13 - t12), "equal_to_host_filter": True, "note": "host arrays in and out: PCIe-bound"}
+    def reg_bytes(n_regs):   # what a download of reg_off and regs moves
+        return (n + 1) * 8 + int(n_regs) * ca.ALNREG_DT.itemsize
+    out["extend_chains (device)"] = {"ms": 1e3 * (t15 - t14), "reads_per_s": n / (t15 - t14), "download_regions_ms": 1e3 * (t16 - t15), "regions": xd["n_regs"],
+                                     "download_bytes": reg_bytes(xd["n_regs"]), "purged": xs1["purged"] - xs0["purged"], "equal_to_host_regions": True}
+    out["extend_chains (device, compact)"] = {"ms": 1e3 * (t18 - t17), "reads_per_s": n / (t18 - t17), "download_regions_ms": 1e3 * (t19 - t18), "live_regions": xc["n_regs"],
+                                              "download_bytes": reg_bytes(xc["n_regs"]), "equal_to_host_regions_with_qe_gt_qb": True}
     out["counts"] = {"seeds": int(res.n_seeds), "chains": int(c["chains"].size), "chains_after_filter": int(f["chains"].size), "regions": int(g["regs"].size),
                      "regions_after_dedup": int(d["regs"].size), "extensions": int(st1["pairs"] - st0["pairs"]), "ext_launches": int(st1["launches"] - st0["launches"])}
     per_read = np.diff(np.asarray(g["reg_off"]).astype(np.int64))
@@ -111,7 +129,7 @@ def run(n=200000, synth_mbp=0.0):
     if tmpdir:
         shutil.rmtree(tmpdir, ignore_errors=True)
     eng.free(d_b); eng.free(d_o)
-    for x in (al, chd, ch, eng, ix):
+    for x in (al, ald, chd, ch, eng, ix):
         x.close()
     return out
 
