@@ -13,7 +13,7 @@
 //   apply_kernel        a side's results into the regions: clipped or to the end of the read, truesc, the band used; retry list
 //   seedcov_kernel, purge_kernel   comp_seed.cpp:1758-1766 and :2141-2232 (one thread per read walks its regions in extension order)
 // Same results as the host driver it replaces, field by field (tests/test_gpu_align.py against the reference's own regions).
-#include "cs_internal.hpp"
+#include "dev_stage.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -23,16 +23,6 @@
 #include <vector>
 
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
-
-#define HIP_TRYA(expr)                                                                              \
-	do {                                                                                            \
-		hipError_t e__ = (expr);                                                                    \
-		if (e__ != hipSuccess) {                                                                    \
-			(void)hipGetLastError();                                                                \
-			return cs_fail_(e__ == hipErrorOutOfMemory ? CS_ENOMEM : CS_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-		}                                                                                           \
-	} while (0)
 
 namespace csa {
 constexpr int32_t UNSET = -99;            // the reference's H0_ (mapping/macro.h:44): a coordinate that has not been set yet
@@ -57,12 +47,6 @@ __device__ __forceinline__ int affordable_gap(const cs_aln_params_t &o, int qlen
 	l = l > 1 ? l : 1;
 	return l < (o.w << 1) ? l : (o.w << 1);
 }
-__device__ __forceinline__ uint8_t pac_base(const uint8_t *pac, int64_t p) { return (uint8_t)((pac[p >> 2] >> ((~p & 3) << 1)) & 3); }
-__device__ __forceinline__ uint8_t base_code(uint8_t c) // nst_nt4_table (bntseq.c:46-63); bytes 0..4 are codes already
-{
-	if (c <= 4) return c;
-	switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; case '-': return 5; default: return 4; }
-}
 
 __global__ void chain_read_kernel(const Args A)
 {
@@ -76,7 +60,7 @@ __global__ void query_kernel(const Args A)
 		int64_t lo = 0, hi = A.n_reads;
 		while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (A.read_off[mid] <= b) lo = mid; else hi = mid; }
 		const uint64_t b0 = A.read_off[lo], len = A.read_off[lo + 1] - b0, j = b - b0;
-		const uint8_t c = base_code(A.bases[b]);
+		const uint8_t c = cs_base_code_(A.bases[b]);
 		A.qbuf[b] = c; A.qbuf[A.n_bases + b0 + (len - 1 - j)] = c;
 	}
 }
@@ -124,7 +108,7 @@ __global__ void fill_kernel(const Args A)
 		uint8_t *t = A.tbuf + A.tb0[ci];
 		for (int64_t k = lane; k < L; k += 64) {
 			const int64_t p = w0 + k;
-			const uint8_t b = p < A.l_pac ? pac_base(A.pac, p) : (uint8_t)(3 - pac_base(A.pac, (A.l_pac << 1) - 1 - p));
+			const uint8_t b = (uint8_t)(p < A.l_pac ? cs_pac_base_(A.pac, p) : 3 - cs_pac_base_(A.pac, (A.l_pac << 1) - 1 - p));
 			t[k] = b; t[L + (L - 1 - k)] = b;
 		}
 	}
@@ -487,33 +471,18 @@ __global__ void reg_off_live_kernel(uint64_t *reg_off, int64_t n_reads, const ui
 } // namespace csa
 
 namespace {
-struct Buf { void *p = nullptr; size_t cap = 0; };
-int ensure(Buf &b, size_t bytes)
-{
-	if (bytes <= b.cap) return CS_OK;
-	if (b.p) (void)hipFree(b.p);
-	b.p = nullptr; b.cap = 0;
-	const size_t want = bytes + bytes / 8 + 256;
-	HIP_TRYA(hipMalloc(&b.p, want));
-	b.cap = want;
-	return CS_OK;
-}
 enum { B_CHAIN_OFF, B_CSEED_OFF, B_READ_OFF, B_CHAINS, B_CSEEDS, B_SCORE, B_BASES, B_PAC, B_CTG_OFF, B_CTG_LEN, B_CHAIN_READ, B_W0, B_WLEN2, B_TB0, B_QBUF, B_TBUF, B_ORD, B_REGS,
        B_REG_CI, B_LP, B_RP, B_RETRY, B_RES, B_CTR, B_SCAN, B_PFLAG, B_BIG, B_BIG_READS,
        B_O_REG_OFF, B_O_REGS, B_LIVE, B_LSCAN,   // cs_extend_chains_device: reg_off, the compacted regions, the live flags and their scan
        B_COUNT };
 } // namespace
 
-struct cs_aligner_gpu { int device = 0, n_cu = 256; hipStream_t s = nullptr; Buf b[B_COUNT]; bool pac_up = false; unsigned long long *h_ctr = nullptr; };
+struct cs_aligner_gpu : cs_dev_stage<B_COUNT> { bool pac_up = false; };
 
 void cs_aligner_gpu_release_(cs_aligner_gpu *g)
 {
 	if (!g) return;
-	(void)hipSetDevice(g->device);
-	if (g->s) (void)hipStreamSynchronize(g->s);
-	for (Buf &b : g->b) if (b.p) (void)hipFree(b.p);
-	if (g->h_ctr) (void)hipHostFree(g->h_ctr);
-	if (g->s) (void)hipStreamDestroy(g->s);
+	g->release();
 	delete g;
 }
 
@@ -529,34 +498,24 @@ struct Lap {
 	void operator()(const char *) {}
 #endif
 };
-dim3 grid_for(const cs_aligner_gpu &G, int64_t items, int per_block = 256) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)G.n_cu * 16))); }
 
 // the aligner's device state, made by its first call; the packed reference and the contig table go up once
 int gpu_state_(cs_aligner_gpu **gp, int device)
 {
-	HIP_TRYA(hipSetDevice(device));
-	if (*gp) return CS_OK;
-	cs_aligner_gpu *g = new cs_aligner_gpu(); g->device = device; *gp = g;
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) g->n_cu = prop.multiProcessorCount;
-	HIP_TRYA(hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking));
-	HIP_TRYA(hipHostMalloc((void **)&g->h_ctr, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-	return CS_OK;
-}
-int up_(cs_aligner_gpu &G, int which, const void *src, size_t bytes)
-{
-	if (int rc = ensure(G.b[which], bytes + 64)) return rc;
-	if (bytes) HIP_TRYA(hipMemcpyAsync(G.b[which].p, src, bytes, hipMemcpyHostToDevice, G.s));
+	if (*gp) { HIP_TRY(hipSetDevice(device)); return CS_OK; }
+	cs_aligner_gpu *g = new cs_aligner_gpu();
+	if (int rc = g->init(device, false)) { cs_aligner_gpu_release_(g); return rc; }
+	*gp = g;
 	return CS_OK;
 }
 int ref_up_(cs_aligner_gpu &G, const cs_refseq_view &R, const std::vector<uint8_t> &pac)
 {
 	if (G.pac_up) return CS_OK;
 	std::vector<int64_t> co(R.offset.begin(), R.offset.end()); std::vector<int32_t> cl(R.len.begin(), R.len.end());
-	if (int rc = up_(G, B_PAC, pac.data(), pac.size())) return rc;
-	if (int rc = up_(G, B_CTG_OFF, co.data(), co.size() * 8)) return rc;
-	if (int rc = up_(G, B_CTG_LEN, cl.data(), cl.size() * 4)) return rc;
-	HIP_TRYA(hipStreamSynchronize(G.s));          // (co / cl are locals)
+	if (int rc = G.up(B_PAC, pac.data(), pac.size())) return rc;
+	if (int rc = G.up(B_CTG_OFF, co.data(), co.size() * 8)) return rc;
+	if (int rc = G.up(B_CTG_LEN, cl.data(), cl.size() * 4)) return rc;
+	HIP_TRY(hipStreamSynchronize(G.s));          // (co / cl are locals)
 	G.pac_up = true;
 	return CS_OK;
 }
@@ -573,74 +532,70 @@ int extend_core_(cs_aligner_gpu &G, cs_extender_t *ext, const cs_refseq_view &R,
 	hipStream_t s = G.s;
 	const int64_t n = in.n, nc = in.nc, ns = in.ns;
 	const uint64_t n_bases = in.n_bases;
-	for (int which : {B_CHAIN_READ, B_BIG}) if (int rc = ensure(G.b[which], (size_t)nc * 4 + 64)) return rc;
-	if (int rc = ensure(G.b[B_BIG_READS], (size_t)n * 4 + 64)) return rc;
-	for (int which : {B_W0, B_WLEN2, B_TB0}) if (int rc = ensure(G.b[which], ((size_t)nc + 1) * 8 + 64)) return rc;
-	if (int rc = ensure(G.b[B_QBUF], (size_t)n_bases * 2 + 64)) return rc;
-	for (int which : {B_ORD, B_REG_CI}) if (int rc = ensure(G.b[which], (size_t)ns * 4 + 64)) return rc;
-	if (int rc = ensure(G.b[B_REGS], (size_t)ns * sizeof(cs_alnreg_t) + 64)) return rc;
-	for (int which : {B_LP, B_RP, B_RETRY}) if (int rc = ensure(G.b[which], (size_t)ns * sizeof(cs_ext_pair_t) + 64)) return rc;
-	if (int rc = ensure(G.b[B_RES], (size_t)ns * sizeof(cs_ext_result_t) + 64)) return rc;
-	if (int rc = ensure(G.b[B_CTR], 8 * sizeof(unsigned long long))) return rc;
-	HIP_TRYA(hipMemsetAsync(G.b[B_CTR].p, 0, 8 * sizeof(unsigned long long), s));
+	for (int which : {B_CHAIN_READ, B_BIG}) if (int rc = G.ensure(which, (size_t)nc * 4 + 64)) return rc;
+	if (int rc = G.ensure(B_BIG_READS, (size_t)n * 4 + 64)) return rc;
+	for (int which : {B_W0, B_WLEN2, B_TB0}) if (int rc = G.ensure(which, ((size_t)nc + 1) * 8 + 64)) return rc;
+	if (int rc = G.ensure(B_QBUF, (size_t)n_bases * 2 + 64)) return rc;
+	for (int which : {B_ORD, B_REG_CI}) if (int rc = G.ensure(which, (size_t)ns * 4 + 64)) return rc;
+	if (int rc = G.ensure(B_REGS, (size_t)ns * sizeof(cs_alnreg_t) + 64)) return rc;
+	for (int which : {B_LP, B_RP, B_RETRY}) if (int rc = G.ensure(which, (size_t)ns * sizeof(cs_ext_pair_t) + 64)) return rc;
+	if (int rc = G.ensure(B_RES, (size_t)ns * sizeof(cs_ext_result_t) + 64)) return rc;
+	if (int rc = G.ensure(B_CTR, 8 * sizeof(unsigned long long))) return rc;
+	HIP_TRY(hipMemsetAsync(G.b[B_CTR].p, 0, 8 * sizeof(unsigned long long), s));
 
 	csa::Args A;
 	A.chain_off = in.chain_off; A.cseed_off = in.cseed_off; A.read_off = in.read_off;
 	A.chains = in.chains; A.cseeds = in.cseeds; A.score = in.score;
 	A.bases = in.bases; A.n_reads = n; A.n_chains = nc; A.n_seeds = ns; A.l_pac = R.l_pac; A.n_bases = n_bases;
-	A.pac = (const uint8_t *)G.b[B_PAC].p; A.ctg_off = (const int64_t *)G.b[B_CTG_OFF].p; A.ctg_len = (const int32_t *)G.b[B_CTG_LEN].p; A.n_ctg = (int32_t)R.offset.size();
+	A.pac = G.at<uint8_t>(B_PAC); A.ctg_off = G.at<int64_t>(B_CTG_OFF); A.ctg_len = G.at<int32_t>(B_CTG_LEN); A.n_ctg = (int32_t)R.offset.size();
 	A.o = o;
-	A.chain_read = (uint32_t *)G.b[B_CHAIN_READ].p; A.w0 = (int64_t *)G.b[B_W0].p; A.wlen2 = (uint64_t *)G.b[B_WLEN2].p; A.tb0 = (uint64_t *)G.b[B_TB0].p;
-	A.qbuf = (uint8_t *)G.b[B_QBUF].p; A.tbuf = nullptr; A.ord = (uint32_t *)G.b[B_ORD].p; A.regs = (cs_alnreg_t *)G.b[B_REGS].p; A.reg_ci = (uint32_t *)G.b[B_REG_CI].p;
-	A.lp = (cs_ext_pair_t *)G.b[B_LP].p; A.rp = (cs_ext_pair_t *)G.b[B_RP].p; A.ctr = (unsigned long long *)G.b[B_CTR].p;
-	A.big = (uint32_t *)G.b[B_BIG].p; A.big_reads = (uint32_t *)G.b[B_BIG_READS].p;
+	A.chain_read = G.at<uint32_t>(B_CHAIN_READ); A.w0 = G.at<int64_t>(B_W0); A.wlen2 = G.at<uint64_t>(B_WLEN2); A.tb0 = G.at<uint64_t>(B_TB0);
+	A.qbuf = G.at<uint8_t>(B_QBUF); A.tbuf = nullptr; A.ord = G.at<uint32_t>(B_ORD); A.regs = G.at<cs_alnreg_t>(B_REGS); A.reg_ci = G.at<uint32_t>(B_REG_CI);
+	A.lp = G.at<cs_ext_pair_t>(B_LP); A.rp = G.at<cs_ext_pair_t>(B_RP); A.ctr = G.at<unsigned long long>(B_CTR);
+	A.big = G.at<uint32_t>(B_BIG); A.big_reads = G.at<uint32_t>(B_BIG_READS);
 	A.small_chain = (o.flags & CS_ALN_NO_LIGHT_PATHS) ? 0 : csa::SMALL_CHAIN; A.light_max = (o.flags & CS_ALN_NO_LIGHT_PATHS) ? 1 : 64;
 	A.purge_cap = (o.flags & CS_ALN_PURGE_FROM_HBM) ? 0 : csa::PURGE_CAP;
-	auto grid = [&](int64_t items, int per_block = 256) { return grid_for(G, items, per_block); };
 
 	lap("buffers");
-	hipLaunchKernelGGL(csa::chain_read_kernel, grid(n), dim3(256), 0, s, A);
-	hipLaunchKernelGGL(csa::query_kernel, grid((int64_t)n_bases), dim3(256), 0, s, A);
-	hipLaunchKernelGGL(csa::window_kernel, grid(nc), dim3(256), 0, s, A);
-	HIP_TRYA(hipGetLastError());
+	hipLaunchKernelGGL(csa::chain_read_kernel, G.grid(n), dim3(256), 0, s, A);
+	hipLaunchKernelGGL(csa::query_kernel, G.grid((int64_t)n_bases), dim3(256), 0, s, A);
+	hipLaunchKernelGGL(csa::window_kernel, G.grid(nc), dim3(256), 0, s, A);
+	HIP_TRY(hipGetLastError());
 	{ // every window's place in the target buffer: exclusive scan of 2 x length (one element more: the total)
-		HIP_TRYA(hipMemsetAsync(A.wlen2 + nc, 0, 8, s));
-		size_t tb = 0;
-		HIP_TRYA(rocprim::exclusive_scan(nullptr, tb, A.wlen2, A.tb0, (uint64_t)0, (size_t)nc + 1, rocprim::plus<uint64_t>(), s));
-		if (int rc = ensure(G.b[B_SCAN], tb + 16)) return rc;
-		HIP_TRYA(rocprim::exclusive_scan(G.b[B_SCAN].p, tb, A.wlen2, A.tb0, (uint64_t)0, (size_t)nc + 1, rocprim::plus<uint64_t>(), s));
+		HIP_TRY(hipMemsetAsync(A.wlen2 + nc, 0, 8, s));
+		if (int rc = G.scan<uint64_t>(B_SCAN, A.wlen2, A.tb0, (size_t)nc + 1, 0)) return rc;
 	}
-	HIP_TRYA(hipMemcpyAsync(G.h_ctr, A.tb0 + nc, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYA(hipMemcpyAsync(G.h_ctr + 1, A.ctr + 3, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYA(hipStreamSynchronize(s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.tb0 + nc, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr + 1, A.ctr + 3, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	if (G.h_ctr[1]) return cs_fail_(CS_EINVAL, std::string(who) + ": a chain's first seed lies outside the reference");
 	lap("queries, windows, scan");
 	const uint64_t t_bytes = G.h_ctr[0];
-	if (int rc = ensure(G.b[B_TBUF], (size_t)t_bytes + 64)) return rc;
-	A.tbuf = (uint8_t *)G.b[B_TBUF].p;
-	hipLaunchKernelGGL(csa::fill_kernel, grid(nc * 64), dim3(256), 0, s, A);
+	if (int rc = G.ensure(B_TBUF, (size_t)t_bytes + 64)) return rc;
+	A.tbuf = G.at<uint8_t>(B_TBUF);
+	hipLaunchKernelGGL(csa::fill_kernel, G.grid(nc * 64), dim3(256), 0, s, A);
 	lap("fill");
-	hipLaunchKernelGGL(csa::region_kernel, grid(nc), dim3(256), 0, s, A);
+	hipLaunchKernelGGL(csa::region_kernel, G.grid(nc), dim3(256), 0, s, A);
 	hipLaunchKernelGGL(csa::region_big_kernel, dim3((unsigned)G.n_cu * 8), dim3(256), 0, s, A);
-	HIP_TRYA(hipGetLastError());
-	HIP_TRYA(hipMemcpyAsync(G.h_ctr, A.ctr, 2 * 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYA(hipStreamSynchronize(s));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.ctr, 2 * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	const uint64_t n_left = G.h_ctr[0], n_right = G.h_ctr[1];
 	lap("regions");
 
 	// ---- the dynamic programming (extend.hip), each side: band w, then 2w for the pairs whose path came close to the band's edge
 	auto run_side = [&](cs_ext_pair_t *pairs, uint64_t cnt, bool is_left, int pen_clip) -> int {
-		cs_ext_pair_t *cur = pairs, *nxt = (cs_ext_pair_t *)G.b[B_RETRY].p;
+		cs_ext_pair_t *cur = pairs, *nxt = G.at<cs_ext_pair_t>(B_RETRY);
 		for (int attempt = 0; attempt < 2 && cnt; ++attempt) { // MAX_BAND_TRY (comp_seed.cpp:423)
 			const int w = o.w << attempt;
-			const int rc = cs_extend_batch_device(ext, (int64_t)cnt, cur, A.qbuf, n_bases * 2, A.tbuf, t_bytes, w, (cs_ext_result_t *)G.b[B_RES].p);
+			const int rc = cs_extend_batch_device(ext, (int64_t)cnt, cur, A.qbuf, n_bases * 2, A.tbuf, t_bytes, w, G.at<cs_ext_result_t>(B_RES));
 			if (rc != CS_OK) return rc;
 			st.pairs += cnt; st.launches++;
-			HIP_TRYA(hipMemsetAsync(A.ctr + 2, 0, 8, s));
-			hipLaunchKernelGGL(csa::apply_kernel, grid((int64_t)cnt), dim3(256), 0, s, A, (const cs_ext_pair_t *)cur, (const cs_ext_result_t *)G.b[B_RES].p, cnt, w, attempt, is_left ? 1 : 0, pen_clip, nxt);
-			HIP_TRYA(hipGetLastError());
-			HIP_TRYA(hipMemcpyAsync(G.h_ctr, A.ctr + 2, 8, hipMemcpyDeviceToHost, s));
-			HIP_TRYA(hipStreamSynchronize(s));
+			HIP_TRY(hipMemsetAsync(A.ctr + 2, 0, 8, s));
+			hipLaunchKernelGGL(csa::apply_kernel, G.grid((int64_t)cnt), dim3(256), 0, s, A, (const cs_ext_pair_t *)cur, G.at<cs_ext_result_t>(B_RES), cnt, w, attempt, is_left ? 1 : 0, pen_clip, nxt);
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(G.h_ctr, A.ctr + 2, 8, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipStreamSynchronize(s));
 			cnt = G.h_ctr[0]; st.retries += cnt;
 			std::swap(cur, nxt);
 		}
@@ -648,18 +603,18 @@ int extend_core_(cs_aligner_gpu &G, cs_extender_t *ext, const cs_refseq_view &R,
 	};
 	if (int rc = run_side(A.lp, n_left, true, o.pen_clip5)) return rc;
 	lap("left side");
-	if (n_right) { hipLaunchKernelGGL(csa::right_h0_kernel, grid((int64_t)n_right), dim3(256), 0, s, A.rp, n_right, (const cs_alnreg_t *)A.regs); HIP_TRYA(hipGetLastError()); HIP_TRYA(hipStreamSynchronize(s)); }
+	if (n_right) { hipLaunchKernelGGL(csa::right_h0_kernel, G.grid((int64_t)n_right), dim3(256), 0, s, A.rp, n_right, (const cs_alnreg_t *)A.regs); HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(s)); }
 	if (int rc = run_side(A.rp, n_right, false, o.pen_clip3)) return rc;
 
 	lap("right side");
-	hipLaunchKernelGGL(csa::seedcov_kernel, grid(ns), dim3(256), 0, s, A);
+	hipLaunchKernelGGL(csa::seedcov_kernel, G.grid(ns), dim3(256), 0, s, A);
 	lap("seedcov");
-	if (int rc = ensure(G.b[B_PFLAG], (size_t)ns + 64)) return rc;
-	HIP_TRYA(hipMemsetAsync(G.b[B_PFLAG].p, 0, (size_t)ns, s));
-	hipLaunchKernelGGL(csa::purge_kernel, grid(n * 64), dim3(256), 0, s, A);
+	if (int rc = G.ensure(B_PFLAG, (size_t)ns + 64)) return rc;
+	HIP_TRY(hipMemsetAsync(G.b[B_PFLAG].p, 0, (size_t)ns, s));
+	hipLaunchKernelGGL(csa::purge_kernel, G.grid(n * 64), dim3(256), 0, s, A);
 	lap("purge, light reads");
-	hipLaunchKernelGGL(csa::purge_big_kernel, dim3((unsigned)G.n_cu), dim3(csa::PB), 0, s, A, (uint8_t *)G.b[B_PFLAG].p);
-	HIP_TRYA(hipGetLastError());
+	hipLaunchKernelGGL(csa::purge_big_kernel, dim3((unsigned)G.n_cu), dim3(csa::PB), 0, s, A, G.at<uint8_t>(B_PFLAG));
+	HIP_TRY(hipGetLastError());
 	lap("purge");
 	return CS_OK;
 }
@@ -681,23 +636,23 @@ int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, c
 	if (ns == 0) { regs.clear(); return CS_OK; }
 	if (ns >= 0x7fffffffll || nc >= 0xffffffffll) return cs_fail_(CS_ERANGE, "cs_extend_chains: more than 2^31 regions in one call");
 	const uint64_t n_bases = read_offsets[n];
-	if (int rc = up_(G, B_CHAIN_OFF, chains->chain_off, ((size_t)n + 1) * 8)) return rc;
-	if (int rc = up_(G, B_CSEED_OFF, chains->cseed_off, ((size_t)nc + 1) * 8)) return rc;
-	if (int rc = up_(G, B_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
-	if (int rc = up_(G, B_CHAINS, chains->chains, (size_t)nc * sizeof(cs_chain_t))) return rc;
-	if (int rc = up_(G, B_CSEEDS, chains->cseeds, (size_t)ns * sizeof(cs_seed_t))) return rc;
-	if (cseed_score) { if (int rc = up_(G, B_SCORE, cseed_score, (size_t)ns * 4)) return rc; }
-	if (int rc = up_(G, B_BASES, bases, (size_t)n_bases)) return rc;
+	if (int rc = G.up(B_CHAIN_OFF, chains->chain_off, ((size_t)n + 1) * 8)) return rc;
+	if (int rc = G.up(B_CSEED_OFF, chains->cseed_off, ((size_t)nc + 1) * 8)) return rc;
+	if (int rc = G.up(B_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
+	if (int rc = G.up(B_CHAINS, chains->chains, (size_t)nc * sizeof(cs_chain_t))) return rc;
+	if (int rc = G.up(B_CSEEDS, chains->cseeds, (size_t)ns * sizeof(cs_seed_t))) return rc;
+	if (cseed_score) { if (int rc = G.up(B_SCORE, cseed_score, (size_t)ns * 4)) return rc; }
+	if (int rc = G.up(B_BASES, bases, (size_t)n_bases)) return rc;
 	if (int rc = ref_up_(G, R, pac)) return rc;
 	lap("uploads");
-	const DevBatch in = {(const uint64_t *)G.b[B_CHAIN_OFF].p, (const uint64_t *)G.b[B_CSEED_OFF].p, (const uint64_t *)G.b[B_READ_OFF].p, (const cs_chain_t *)G.b[B_CHAINS].p,
-	                     (const cs_seed_t *)G.b[B_CSEEDS].p, cseed_score ? (const int32_t *)G.b[B_SCORE].p : nullptr, (const uint8_t *)G.b[B_BASES].p, n, nc, ns, n_bases};
+	const DevBatch in = {G.at<uint64_t>(B_CHAIN_OFF), G.at<uint64_t>(B_CSEED_OFF), G.at<uint64_t>(B_READ_OFF), G.at<cs_chain_t>(B_CHAINS),
+	                     G.at<cs_seed_t>(B_CSEEDS), cseed_score ? G.at<int32_t>(B_SCORE) : nullptr, G.at<uint8_t>(B_BASES), n, nc, ns, n_bases};
 	if (int rc = extend_core_(G, ext, R, o, in, st, lap, "cs_extend_chains")) return rc;
 	regs.resize((size_t)ns);
 	lap("host resize");
-	HIP_TRYA(hipMemcpyAsync(regs.data(), G.b[B_REGS].p, (size_t)ns * sizeof(cs_alnreg_t), hipMemcpyDeviceToHost, s));
-	HIP_TRYA(hipMemcpyAsync(G.h_ctr, (unsigned long long *)G.b[B_CTR].p + 4, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYA(hipStreamSynchronize(s));
+	HIP_TRY(hipMemcpyAsync(regs.data(), G.b[B_REGS].p, (size_t)ns * sizeof(cs_alnreg_t), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, G.at<unsigned long long>(B_CTR) + 4, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	lap("download");
 	st.purged += G.h_ctr[0]; st.regions += (uint64_t)ns;
 	return CS_OK;
@@ -714,53 +669,50 @@ int cs_extend_chains_device_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t 
 	hipStream_t s = G.s;
 	Lap lap(s, "cs_extend_chains_device");
 	const int64_t n = d_chains->n_reads, nc = (int64_t)d_chains->n_chains, ns = (int64_t)d_chains->n_seeds;
-	if (int rc = ensure(G.b[B_O_REG_OFF], ((size_t)n + 1) * 8)) return rc;
-	if (int rc = ensure(G.b[B_CTR], 8 * sizeof(unsigned long long))) return rc;
-	unsigned long long *ctr = (unsigned long long *)G.b[B_CTR].p;
-	uint64_t *reg_off = (uint64_t *)G.b[B_O_REG_OFF].p;
+	if (int rc = G.ensure(B_O_REG_OFF, ((size_t)n + 1) * 8)) return rc;
+	if (int rc = G.ensure(B_CTR, 8 * sizeof(unsigned long long))) return rc;
+	unsigned long long *ctr = G.at<unsigned long long>(B_CTR);
+	uint64_t *reg_off = G.at<uint64_t>(B_O_REG_OFF);
 	if ((n == 0 && nc > 0) || (nc == 0 && ns > 0)) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: chains without reads or seeds without chains");
 	const csa::DevIn D = {d_chains->chain_off, d_chains->cseed_off, d_read_offsets, d_chains->chains, n, (uint64_t)nc, (uint64_t)ns};
 	// [0] what the checks refuse, [1] n_bases = read_offsets[n_reads]: one small copy, one wait
-	HIP_TRYA(hipMemsetAsync(ctr, 0, 8 * sizeof(unsigned long long), s));
-	if (n > 0) hipLaunchKernelGGL(csa::check_reads_kernel, grid_for(G, n), dim3(256), 0, s, D, ctr);
-	if (nc > 0) hipLaunchKernelGGL(csa::check_chains_kernel, grid_for(G, nc), dim3(256), 0, s, D, ctr);
-	HIP_TRYA(hipGetLastError());
-	if (n > 0) HIP_TRYA(hipMemcpyAsync(ctr + 1, d_read_offsets + n, 8, hipMemcpyDeviceToDevice, s));
-	HIP_TRYA(hipMemcpyAsync(G.h_ctr, ctr, 2 * 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYA(hipStreamSynchronize(s));
+	HIP_TRY(hipMemsetAsync(ctr, 0, 8 * sizeof(unsigned long long), s));
+	if (n > 0) hipLaunchKernelGGL(csa::check_reads_kernel, G.grid(n), dim3(256), 0, s, D, ctr);
+	if (nc > 0) hipLaunchKernelGGL(csa::check_chains_kernel, G.grid(nc), dim3(256), 0, s, D, ctr);
+	HIP_TRY(hipGetLastError());
+	if (n > 0) HIP_TRY(hipMemcpyAsync(ctr + 1, d_read_offsets + n, 8, hipMemcpyDeviceToDevice, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, ctr, 2 * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	if (G.h_ctr[0]) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: chain_off / cseed_off are not CSR offset arrays from 0 to n_chains / n_seeds that match the chains' seed counts, read_offsets do not start at 0 or decrease, or a read with chains has 65,536 bases or more");
 	const uint64_t n_bases = G.h_ctr[1];
 	lap("checks");
-	if (n > 0 && nc > 0) { hipLaunchKernelGGL(csa::reg_off_kernel, grid_for(G, n + 1), dim3(256), 0, s, D, reg_off); HIP_TRYA(hipGetLastError()); }
-	else HIP_TRYA(hipMemsetAsync(reg_off, 0, ((size_t)n + 1) * 8, s));
+	if (n > 0 && nc > 0) { hipLaunchKernelGGL(csa::reg_off_kernel, G.grid(n + 1), dim3(256), 0, s, D, reg_off); HIP_TRY(hipGetLastError()); }
+	else HIP_TRY(hipMemsetAsync(reg_off, 0, ((size_t)n + 1) * 8, s));
 	st.reads += (uint64_t)n;
-	d_out->n_reads = n; d_out->n_regs = 0; d_out->reg_off = reg_off; d_out->regs = (const cs_alnreg_t *)G.b[B_REGS].p;
-	if (ns == 0) { HIP_TRYA(hipStreamSynchronize(s)); return CS_OK; }
+	d_out->n_reads = n; d_out->n_regs = 0; d_out->reg_off = reg_off; d_out->regs = G.at<cs_alnreg_t>(B_REGS);
+	if (ns == 0) { HIP_TRY(hipStreamSynchronize(s)); return CS_OK; }
 	if (int rc = ref_up_(G, R, pac)) return rc;
 	const DevBatch in = {d_chains->chain_off, d_chains->cseed_off, d_read_offsets, d_chains->chains, d_chains->cseeds, d_cseed_score, d_bases, n, nc, ns, n_bases};
 	if (int rc = extend_core_(G, ext, R, o, in, st, lap, "cs_extend_chains_device")) return rc;
-	ctr = (unsigned long long *)G.b[B_CTR].p;
-	const cs_alnreg_t *regs = (const cs_alnreg_t *)G.b[B_REGS].p;
+	ctr = G.at<unsigned long long>(B_CTR);
+	const cs_alnreg_t *regs = G.at<cs_alnreg_t>(B_REGS);
 	if (flags & CS_ALN_DEV_COMPACT) {
-		for (int which : {B_LIVE, B_LSCAN}) if (int rc = ensure(G.b[which], ((size_t)ns + 1) * 4)) return rc;
-		if (int rc = ensure(G.b[B_O_REGS], (size_t)ns * sizeof(cs_alnreg_t))) return rc;
-		uint32_t *live = (uint32_t *)G.b[B_LIVE].p, *scan = (uint32_t *)G.b[B_LSCAN].p;
-		hipLaunchKernelGGL(csa::live_kernel, grid_for(G, ns + 1), dim3(256), 0, s, regs, (uint64_t)ns, live);
-		HIP_TRYA(hipGetLastError());
-		size_t tb = 0;
-		HIP_TRYA(rocprim::exclusive_scan(nullptr, tb, live, scan, (uint32_t)0, (size_t)ns + 1, rocprim::plus<uint32_t>(), s));
-		if (int rc = ensure(G.b[B_SCAN], tb + 16)) return rc;
-		HIP_TRYA(rocprim::exclusive_scan(G.b[B_SCAN].p, tb, live, scan, (uint32_t)0, (size_t)ns + 1, rocprim::plus<uint32_t>(), s));
-		hipLaunchKernelGGL(csa::scatter_kernel, grid_for(G, ns * csa::REG_WORDS), dim3(256), 0, s, (const uint64_t *)regs, (uint64_t)ns, (const uint32_t *)live, (const uint32_t *)scan, (uint64_t *)G.b[B_O_REGS].p);
-		hipLaunchKernelGGL(csa::reg_off_live_kernel, grid_for(G, n + 1), dim3(256), 0, s, reg_off, n, (const uint32_t *)scan, (uint64_t)ns, ctr + 5);   // ([5], the long chains' count, has served)
-		HIP_TRYA(hipGetLastError());
+		for (int which : {B_LIVE, B_LSCAN}) if (int rc = G.ensure(which, ((size_t)ns + 1) * 4)) return rc;
+		if (int rc = G.ensure(B_O_REGS, (size_t)ns * sizeof(cs_alnreg_t))) return rc;
+		uint32_t *live = G.at<uint32_t>(B_LIVE), *scan = G.at<uint32_t>(B_LSCAN);
+		hipLaunchKernelGGL(csa::live_kernel, G.grid(ns + 1), dim3(256), 0, s, regs, (uint64_t)ns, live);
+		HIP_TRY(hipGetLastError());
+		if (int rc = G.scan<uint32_t>(B_SCAN, live, scan, (size_t)ns + 1, 0)) return rc;
+		hipLaunchKernelGGL(csa::scatter_kernel, G.grid(ns * csa::REG_WORDS), dim3(256), 0, s, (const uint64_t *)regs, (uint64_t)ns, (const uint32_t *)live, (const uint32_t *)scan, G.at<uint64_t>(B_O_REGS));
+		hipLaunchKernelGGL(csa::reg_off_live_kernel, G.grid(n + 1), dim3(256), 0, s, reg_off, n, (const uint32_t *)scan, (uint64_t)ns, ctr + 5);   // ([5], the long chains' count, has served)
+		HIP_TRY(hipGetLastError());
 		lap("compaction");
 	}
-	HIP_TRYA(hipMemcpyAsync(G.h_ctr, ctr + 4, 2 * 8, hipMemcpyDeviceToHost, s));   // [4] purged, [5] live regions
-	HIP_TRYA(hipStreamSynchronize(s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, ctr + 4, 2 * 8, hipMemcpyDeviceToHost, s));   // [4] purged, [5] live regions
+	HIP_TRY(hipStreamSynchronize(s));
 	lap("counters");
 	st.purged += G.h_ctr[0]; st.regions += (uint64_t)ns;
-	if (flags & CS_ALN_DEV_COMPACT) { d_out->n_regs = G.h_ctr[1]; d_out->regs = (const cs_alnreg_t *)G.b[B_O_REGS].p; }
+	if (flags & CS_ALN_DEV_COMPACT) { d_out->n_regs = G.h_ctr[1]; d_out->regs = G.at<cs_alnreg_t>(B_O_REGS); }
 	else { d_out->n_regs = (uint64_t)ns; d_out->regs = regs; }
 	return CS_OK;
 }

@@ -16,7 +16,7 @@
 // The sort is klib's introsort as klib_sort.hpp restates it, compiled for the device: among equal weights its order decides which chain
 // is kept and which is shadowed, and it is not stable for any n but 2 (the first partition runs whatever n is).  The float compares of the
 // scan are the host's expressions; the unit is compiled without fast-math and with -ffp-contract=off like the rest.
-#include "cs_internal.hpp"
+#include "dev_stage.hpp"
 #include "klib_sort.hpp"
 
 #include <algorithm>
@@ -27,16 +27,6 @@
 #include <vector>
 
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
-
-#define HIP_TRYF(expr)                                                                              \
-	do {                                                                                            \
-		hipError_t e__ = (expr);                                                                    \
-		if (e__ != hipSuccess) {                                                                    \
-			(void)hipGetLastError();                                                                \
-			return cs_fail_(e__ == hipErrorOutOfMemory ? CS_ENOMEM : CS_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-		}                                                                                           \
-	} while (0)
 
 namespace csf {
 constexpr int LIGHT_MAX = 16;               // reads of more chains go one wave per read
@@ -236,12 +226,6 @@ __global__ void __launch_bounds__(64) wave_kernel(Args A)
 }
 
 // ---- mem_flt_chained_seeds: one lane per input seed; the lanes whose seed belongs to a kept chain of a long read do the work
-__device__ __forceinline__ uint8_t base_code(uint8_t c)   // cs_base_code_
-{
-	if (c <= 4) return c;
-	switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; case '-': return 5; default: return 4; }
-}
-__device__ __forceinline__ int pac_base(const uint8_t *pac, int64_t p) { return (pac[p >> 2] >> ((~p & 3) << 1)) & 3; }
 // the number of entries <= key in the ascending a[0..n), minus one
 __device__ __forceinline__ int64_t holder_of(const uint64_t *a, int64_t n, uint64_t key)
 {
@@ -297,14 +281,14 @@ __global__ void __launch_bounds__(64) sw_kernel(Args A)
 				if (qlen > 0 && tlen > 0) {   // striped_sw_score of chain_filter.cpp: H in place behind a carried diagonal, E beside it
 					const uint8_t *q = A.bases + A.read_off[r] + (uint64_t)qb;
 					for (int j = 0; j < qlen; ++j) {
-						qs[j * 64 + lane] = base_code(q[j]);
+						qs[j * 64 + lane] = cs_base_code_(q[j]);
 						he[j * 64 + lane] = 0;
 					}
 					const int slen = (qlen + 7) / 8, oe_del = o.o_del + o.e_del, oe_ins = o.o_ins + o.e_ins;
 					int best = 0;
 					for (int i = 0; i < tlen; ++i) {
 						const int64_t p = rb + i;
-						const int tb = p >= l_pac ? 3 - pac_base(A.pac, (l_pac << 1) - 1 - p) : pac_base(A.pac, p);
+						const int tb = p >= l_pac ? 3 - cs_pac_base_(A.pac, (l_pac << 1) - 1 - p) : cs_pac_base_(A.pac, p);
 						int f = 0, rowmax = 0, diag = 0, seg = 0;
 						for (int j = 0; j < qlen; ++j) {   // the main loop: F only from inside the position's own segment
 							if (seg == 0) f = 0;
@@ -369,26 +353,13 @@ __global__ void __launch_bounds__(256) compact_kernel(Args A)
 } // namespace csf
 
 namespace {
-struct Buf { void *p = nullptr; size_t cap = 0; };
-int ensure(Buf &b, size_t bytes)
-{
-	if (bytes <= b.cap) return CS_OK;
-	if (b.p) (void)hipFree(b.p);
-	b.p = nullptr; b.cap = 0;
-	const size_t want = bytes + bytes / 8 + 256;
-	HIP_TRYF(hipMalloc(&b.p, want));
-	b.cap = want;
-	return CS_OK;
-}
 enum { B_CTG_OFF, B_CTG_LEN, B_PAC, B_TAB, B_W, B_CB, B_CE, B_CNS, B_KFLAG, B_SRT, B_SPAN, B_KI, B_KFIRST, B_ALT, B_KEPTV, B_ORD, B_SSCORE, B_NCH, B_NSD, B_WAVE,
        B_CTR, B_SCAN, B_O_CHAIN_OFF, B_SBASE, B_O_CSEED_OFF, B_O_CHAINS, B_O_CSEEDS, B_O_SCORE,
        B_IN_CHAIN_OFF, B_IN_CHAINS, B_IN_CSEED_OFF, B_IN_CSEEDS, B_IN_BASES, B_IN_READ_OFF, B_COUNT };   // B_IN_*: cs_chain_filter_gpu's uploads
-constexpr int N_CTR = 8;
 } // namespace
 
-struct cs_chainer_flt_gpu {
-	int device = 0, n_cu = 256, n_ctg = 0; hipStream_t s = nullptr; hipEvent_t ev[4] = {};
-	Buf b[B_COUNT]; unsigned long long *h_ctr = nullptr; cs_flt_stats_t st = {};
+struct cs_chainer_flt_gpu : cs_dev_stage<B_COUNT> {
+	int n_ctg = 0; cs_flt_stats_t st = {};
 	bool tab_uploaded = false, have_pac = false; int32_t tab_a = 0, tab_mcw = 0; std::vector<int32_t> tab;
 	std::vector<cs_chain_t> h_chains; std::vector<uint64_t> h_chain_off, h_cseed_off; std::vector<cs_seed_t> h_cseeds; std::vector<int32_t> h_score;   // cs_chain_filter_gpu's result
 };
@@ -396,12 +367,7 @@ struct cs_chainer_flt_gpu {
 void cs_chainer_flt_gpu_release_(cs_chainer_flt_gpu *g)
 {
 	if (!g) return;
-	(void)hipSetDevice(g->device);
-	if (g->s) (void)hipStreamSynchronize(g->s);
-	for (Buf &b : g->b) if (b.p) (void)hipFree(b.p);
-	for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
-	if (g->h_ctr) (void)hipHostFree(g->h_ctr);
-	if (g->s) (void)hipStreamDestroy(g->s);
+	g->release();
 	delete g;
 }
 
@@ -409,20 +375,15 @@ namespace {
 int flt_init(cs_chainer *c)
 {
 	if (c->flt) return CS_OK;
-	const int device = cs_chainer_gpu_device_(c->gpu);
-	HIP_TRYF(hipSetDevice(device));
-	cs_chainer_flt_gpu *g = new cs_chainer_flt_gpu(); g->device = device; c->flt = g;   // (released with the chainer, whatever fails below)
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) g->n_cu = prop.multiProcessorCount;
-	HIP_TRYF(hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking));
-	for (hipEvent_t &e : g->ev) HIP_TRYF(hipEventCreate(&e));
-	HIP_TRYF(hipHostMalloc((void **)&g->h_ctr, N_CTR * sizeof(unsigned long long), hipHostMallocDefault));
+	cs_chainer_flt_gpu *g = new cs_chainer_flt_gpu();
+	if (int rc = g->init(cs_chainer_gpu_device_(c->gpu), true)) { cs_chainer_flt_gpu_release_(g); return rc; }
+	c->flt = g;   // (released with the chainer, whatever fails below)
 	const cs_refseq_view &R = c->ref;   // contig offsets and lengths, once
 	g->n_ctg = (int)R.offset.size();
-	if (int rc = ensure(g->b[B_CTG_OFF], R.offset.size() * 8 + 8)) return rc;
-	if (int rc = ensure(g->b[B_CTG_LEN], R.len.size() * 4 + 4)) return rc;
-	HIP_TRYF(hipMemcpy(g->b[B_CTG_OFF].p, R.offset.data(), R.offset.size() * 8, hipMemcpyHostToDevice));
-	HIP_TRYF(hipMemcpy(g->b[B_CTG_LEN].p, R.len.data(), R.len.size() * 4, hipMemcpyHostToDevice));
+	if (int rc = g->ensure(B_CTG_OFF, R.offset.size() * 8 + 8)) return rc;
+	if (int rc = g->ensure(B_CTG_LEN, R.len.size() * 4 + 4)) return rc;
+	HIP_TRY(hipMemcpy(g->b[B_CTG_OFF].p, R.offset.data(), R.offset.size() * 8, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(g->b[B_CTG_LEN].p, R.len.data(), R.len.size() * 4, hipMemcpyHostToDevice));
 	return CS_OK;
 }
 
@@ -458,11 +419,12 @@ int filter_device_(cs_chainer *c, const cs_flt_params_t &o, const cs_chain_resul
 {
 	if (int rc = flt_init(c)) return rc;
 	cs_chainer_flt_gpu &G = *c->flt;
-	HIP_TRYF(hipSetDevice(G.device));
+	constexpr int N_CTR = cs_chainer_flt_gpu::N_CTR;
+	HIP_TRY(hipSetDevice(G.device));
 	hipStream_t s = G.s;
 	const int64_t n = in.n_reads;
 	const uint64_t nc = in.n_chains, ns = in.n_seeds;
-	if (nc && in.chains == (const cs_chain_t *)G.b[B_O_CHAINS].p) return cs_fail_(CS_EINVAL, "cs_chain_filter_device: the input is this function's own previous output");
+	if (nc && in.chains == G.at<cs_chain_t>(B_O_CHAINS)) return cs_fail_(CS_EINVAL, "cs_chain_filter_device: the input is this function's own previous output");
 	const size_t per_chain = (size_t)nc + 1, per_seed = (size_t)ns + 1, per_read = (size_t)n + 1;
 	struct { int which; size_t bytes; } need[] = {
 		{B_TAB, (size_t)csf::MAX_READ_LEN * 4}, {B_W, per_chain * 4}, {B_CB, per_chain * 4}, {B_CE, per_chain * 4}, {B_CNS, per_chain * 4}, {B_KFLAG, per_chain},
@@ -470,41 +432,35 @@ int filter_device_(cs_chainer *c, const cs_flt_params_t &o, const cs_chain_resul
 		{B_ORD, per_chain * 4}, {B_NCH, per_read * 8}, {B_NSD, per_read * 8}, {B_WAVE, per_read * 4}, {B_CTR, N_CTR * 8},
 		{B_O_CHAIN_OFF, per_read * 8}, {B_SBASE, per_read * 8}, {B_O_CSEED_OFF, per_chain * 8}, {B_O_CHAINS, per_chain * sizeof(cs_chain_t)},
 		{B_O_CSEEDS, per_seed * sizeof(cs_seed_t)}, {B_O_SCORE, per_seed * 4}};
-	for (auto &q : need) if (int rc = ensure(G.b[q.which], q.bytes)) return rc;
+	for (auto &q : need) if (int rc = G.ensure(q.which, q.bytes)) return rc;
 	build_table(G, o);
-	if (!G.tab_uploaded) { HIP_TRYF(hipMemcpy(G.b[B_TAB].p, G.tab.data(), (size_t)csf::MAX_READ_LEN * 4, hipMemcpyHostToDevice)); G.tab_uploaded = true; }
+	if (!G.tab_uploaded) { HIP_TRY(hipMemcpy(G.b[B_TAB].p, G.tab.data(), (size_t)csf::MAX_READ_LEN * 4, hipMemcpyHostToDevice)); G.tab_uploaded = true; }
 	csf::Args A;
 	A.chain_off = in.chain_off; A.cseed_off = in.cseed_off; A.read_off = d_ro; A.chains = in.chains; A.cseeds = in.cseeds; A.bases = d_bases;
 	A.n_reads = n; A.n_chains = nc; A.n_seeds = ns; A.flags = flags; A.o = o;
-	A.l_pac = c->ref.l_pac; A.ctg_off = (const int64_t *)G.b[B_CTG_OFF].p; A.ctg_len = (const int32_t *)G.b[B_CTG_LEN].p; A.n_ctg = G.n_ctg; A.pac = (const uint8_t *)G.b[B_PAC].p;
-	A.tab = (const int32_t *)G.b[B_TAB].p;
-	A.w = (int32_t *)G.b[B_W].p; A.cb = (int32_t *)G.b[B_CB].p; A.ce = (int32_t *)G.b[B_CE].p; A.cns = (int32_t *)G.b[B_CNS].p; A.kflag = (uint8_t *)G.b[B_KFLAG].p;
-	A.srt = (csf::WRec *)G.b[B_SRT].p; A.span = (int2 *)G.b[B_SPAN].p; A.ki = (int32_t *)G.b[B_KI].p; A.kfirst = (int32_t *)G.b[B_KFIRST].p;
-	A.alt = (uint8_t *)G.b[B_ALT].p; A.keptv = (uint8_t *)G.b[B_KEPTV].p; A.ord = (uint32_t *)G.b[B_ORD].p; A.sscore = nullptr;
-	A.nch = (uint64_t *)G.b[B_NCH].p; A.nsd = (uint64_t *)G.b[B_NSD].p; A.wave_list = (uint32_t *)G.b[B_WAVE].p; A.ctr = (unsigned long long *)G.b[B_CTR].p;
-	A.o_chain_off = (uint64_t *)G.b[B_O_CHAIN_OFF].p; A.sbase = (uint64_t *)G.b[B_SBASE].p; A.o_cseed_off = (uint64_t *)G.b[B_O_CSEED_OFF].p;
-	A.o_chains = (cs_chain_t *)G.b[B_O_CHAINS].p; A.o_cseeds = (cs_seed_t *)G.b[B_O_CSEEDS].p; A.o_score = (int32_t *)G.b[B_O_SCORE].p;
+	A.l_pac = c->ref.l_pac; A.ctg_off = G.at<int64_t>(B_CTG_OFF); A.ctg_len = G.at<int32_t>(B_CTG_LEN); A.n_ctg = G.n_ctg; A.pac = G.at<uint8_t>(B_PAC);
+	A.tab = G.at<int32_t>(B_TAB);
+	A.w = G.at<int32_t>(B_W); A.cb = G.at<int32_t>(B_CB); A.ce = G.at<int32_t>(B_CE); A.cns = G.at<int32_t>(B_CNS); A.kflag = G.at<uint8_t>(B_KFLAG);
+	A.srt = G.at<csf::WRec>(B_SRT); A.span = G.at<int2>(B_SPAN); A.ki = G.at<int32_t>(B_KI); A.kfirst = G.at<int32_t>(B_KFIRST);
+	A.alt = G.at<uint8_t>(B_ALT); A.keptv = G.at<uint8_t>(B_KEPTV); A.ord = G.at<uint32_t>(B_ORD); A.sscore = nullptr;
+	A.nch = G.at<uint64_t>(B_NCH); A.nsd = G.at<uint64_t>(B_NSD); A.wave_list = G.at<uint32_t>(B_WAVE); A.ctr = G.at<unsigned long long>(B_CTR);
+	A.o_chain_off = G.at<uint64_t>(B_O_CHAIN_OFF); A.sbase = G.at<uint64_t>(B_SBASE); A.o_cseed_off = G.at<uint64_t>(B_O_CSEED_OFF);
+	A.o_chains = G.at<cs_chain_t>(B_O_CHAINS); A.o_cseeds = G.at<cs_seed_t>(B_O_CSEEDS); A.o_score = G.at<int32_t>(B_O_SCORE);
 	out.n_reads = n; out.n_chains = 0; out.n_seeds = 0;
 	out.chain_off = A.o_chain_off; out.chains = A.o_chains; out.cseed_off = A.o_cseed_off; out.cseeds = A.o_cseeds;
 	if (d_score) *d_score = A.o_score;
-	if (n == 0) {
-		HIP_TRYF(hipMemsetAsync(A.o_chain_off, 0, 8, s));
-		HIP_TRYF(hipMemsetAsync(A.o_cseed_off, 0, 8, s));
-		HIP_TRYF(hipStreamSynchronize(s));
-		return CS_OK;
-	}
-	auto grid = [&](int64_t items, int per_block) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)G.n_cu * 16))); };
-	HIP_TRYF(hipMemsetAsync(A.ctr, 0, N_CTR * 8, s));
-	HIP_TRYF(hipMemsetAsync(A.nch + n, 0, 8, s));
-	HIP_TRYF(hipMemsetAsync(A.nsd + n, 0, 8, s));
-	HIP_TRYF(hipEventRecord(G.ev[0], s));
+	if (n == 0) return G.empty_csr(A.o_chain_off, A.o_cseed_off);
+	HIP_TRY(hipMemsetAsync(A.ctr, 0, N_CTR * 8, s));
+	HIP_TRY(hipMemsetAsync(A.nch + n, 0, 8, s));
+	HIP_TRY(hipMemsetAsync(A.nsd + n, 0, 8, s));
+	HIP_TRY(hipEventRecord(G.ev[0], s));
 	unsigned launches = 1;
-	if (nc) { hipLaunchKernelGGL(csf::weight_kernel, grid((int64_t)nc, 256), dim3(256), 0, s, A); ++launches; }
-	hipLaunchKernelGGL(csf::classify_kernel, grid(n, 256), dim3(256), 0, s, A);
-	HIP_TRYF(hipGetLastError());
-	HIP_TRYF(hipEventRecord(G.ev[1], s));
-	HIP_TRYF(hipMemcpyAsync(G.h_ctr, A.ctr, N_CTR * 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYF(hipStreamSynchronize(s));
+	if (nc) { hipLaunchKernelGGL(csf::weight_kernel, G.grid((int64_t)nc, 256), dim3(256), 0, s, A); ++launches; }
+	hipLaunchKernelGGL(csf::classify_kernel, G.grid(n, 256), dim3(256), 0, s, A);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(G.ev[1], s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.ctr, N_CTR * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	if (G.h_ctr[2]) return cs_fail_(CS_EINVAL, "cs_chain_filter_device: a chain without seeds, offsets that are not a CSR, or n_seeds that disagrees with cseed_off");
 	if (G.h_ctr[3]) return cs_fail_(CS_ERANGE, "cs_chain_filter_device: a read of 65,536 bases or more");
 	const uint64_t n_wave = G.h_ctr[0];
@@ -513,43 +469,35 @@ int filter_device_(cs_chainer *c, const cs_flt_params_t &o, const cs_chain_resul
 		if (!d_bases) return cs_fail_(CS_EINVAL, "cs_chain_filter_device: the reads are needed for the seed test of long reads");
 		if (!G.have_pac) {
 			if (c->pac.empty()) { const int rc = cs_load_pac_(c->prefix.c_str(), c->ref.l_pac, c->pac); if (rc != CS_OK) { c->pac.clear(); return rc; } }
-			if (int rc = ensure(G.b[B_PAC], c->pac.size())) return rc;
-			HIP_TRYF(hipMemcpy(G.b[B_PAC].p, c->pac.data(), c->pac.size(), hipMemcpyHostToDevice));
+			if (int rc = G.ensure(B_PAC, c->pac.size())) return rc;
+			HIP_TRY(hipMemcpy(G.b[B_PAC].p, c->pac.data(), c->pac.size(), hipMemcpyHostToDevice));
 			G.have_pac = true;
 		}
-		A.pac = (const uint8_t *)G.b[B_PAC].p;
-		if (int rc = ensure(G.b[B_SSCORE], per_seed * 4)) return rc;
-		A.sscore = (int32_t *)G.b[B_SSCORE].p;
+		A.pac = G.at<uint8_t>(B_PAC);
+		if (int rc = G.ensure(B_SSCORE, per_seed * 4)) return rc;
+		A.sscore = G.at<int32_t>(B_SSCORE);
 	}
-	HIP_TRYF(hipEventRecord(G.ev[2], s));
-	if (!(flags & CS_FLT_WAVE_ONLY)) { hipLaunchKernelGGL(csf::light_kernel, grid(n, 256), dim3(256), 0, s, A); ++launches; }
+	HIP_TRY(hipEventRecord(G.ev[2], s));
+	if (!(flags & CS_FLT_WAVE_ONLY)) { hipLaunchKernelGGL(csf::light_kernel, G.grid(n, 256), dim3(256), 0, s, A); ++launches; }
 	if (n_wave) { hipLaunchKernelGGL(csf::wave_kernel, dim3((unsigned)std::min<uint64_t>(n_wave, (uint64_t)G.n_cu * 12)), dim3(64), 0, s, A); ++launches; }
 	if (need_sw && ns) {
 		hipLaunchKernelGGL(csf::sw_kernel, dim3((unsigned)std::min<uint64_t>((ns + 63) / 64, (uint64_t)G.n_cu * 64)), dim3(64), 0, s, A);
 		++launches;
 	}
-	HIP_TRYF(hipGetLastError());
-	{ // chain_off and the per-read seed bases: exclusive scans over n + 1 counts (the last one 0: the totals)
-		size_t tb = 0, tb2 = 0;
-		HIP_TRYF(rocprim::exclusive_scan(nullptr, tb, A.nch, A.o_chain_off, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-		HIP_TRYF(rocprim::exclusive_scan(nullptr, tb2, A.nsd, A.sbase, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-		tb = std::max(tb, tb2);
-		if (int rc = ensure(G.b[B_SCAN], tb + 16)) return rc;
-		HIP_TRYF(rocprim::exclusive_scan(G.b[B_SCAN].p, tb, A.nch, A.o_chain_off, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-		HIP_TRYF(rocprim::exclusive_scan(G.b[B_SCAN].p, tb, A.nsd, A.sbase, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-	}
-	hipLaunchKernelGGL(csf::compact_kernel, grid(n, 256), dim3(256), 0, s, A);
-	HIP_TRYF(hipGetLastError());
+	HIP_TRY(hipGetLastError());
+	// chain_off and the per-read seed bases: exclusive scans over n + 1 counts (the last one 0: the totals)
+	if (int rc = G.scan<uint64_t>(B_SCAN, A.nch, A.o_chain_off, A.nsd, A.sbase, (size_t)n + 1, 0)) return rc;
+	hipLaunchKernelGGL(csf::compact_kernel, G.grid(n, 256), dim3(256), 0, s, A);
+	HIP_TRY(hipGetLastError());
 	launches += 3;
-	HIP_TRYF(hipEventRecord(G.ev[3], s));
-	HIP_TRYF(hipMemcpyAsync(G.h_ctr, A.o_chain_off + n, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYF(hipMemcpyAsync(G.h_ctr + 2, A.sbase + n, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYF(hipMemcpyAsync(G.h_ctr + 1, A.ctr + 1, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYF(hipMemcpyAsync(G.h_ctr + 5, A.ctr + 5, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYF(hipStreamSynchronize(s));
+	HIP_TRY(hipEventRecord(G.ev[3], s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.o_chain_off + n, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr + 2, A.sbase + n, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr + 1, A.ctr + 1, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr + 5, A.ctr + 5, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	out.n_chains = G.h_ctr[0]; out.n_seeds = G.h_ctr[2];
-	float ms0 = 0.f, ms1 = 0.f;
-	if (hipEventElapsedTime(&ms0, G.ev[0], G.ev[1]) == hipSuccess && hipEventElapsedTime(&ms1, G.ev[2], G.ev[3]) == hipSuccess) G.st.kernel_ms += (double)ms0 + ms1;
+	G.add_kernel_ms(G.st.kernel_ms);
 	G.st.reads += (uint64_t)n; G.st.chains_in += nc; G.st.chains_out += out.n_chains; G.st.seeds_in += ns; G.st.seeds_out += out.n_seeds;
 	G.st.wave_reads += n_wave; G.st.spill_reads += G.h_ctr[1]; G.st.sw_seeds += G.h_ctr[5]; G.st.launches += launches;
 	return CS_OK;
@@ -569,7 +517,7 @@ extern "C" int cs_chain_filter_gpu(cs_chainer_t *c, const cs_flt_params_t *par, 
 	if (int rc = check_call("cs_chain_filter_gpu", c, par, in, read_offsets, flags, out)) return rc;
 	if (int rc = flt_init(c)) return rc;
 	cs_chainer_flt_gpu &G = *c->flt;
-	HIP_TRYF(hipSetDevice(G.device));
+	HIP_TRY(hipSetDevice(G.device));
 	const int64_t n = in->n_reads;
 	if (in->n_chains && in->chains == G.h_chains.data()) return cs_fail_(CS_EINVAL, "cs_chain_filter_gpu: the input is this function's own previous output");
 	// the reads are uploaded only when some read with chains is long enough for the seed test (the table is the device's own)
@@ -580,38 +528,23 @@ extern "C" int cs_chain_filter_gpu(cs_chainer_t *c, const cs_flt_params_t *par, 
 		need_bases = l < csf::MAX_READ_LEN && in->chain_off[r + 1] > in->chain_off[r] && G.tab[(size_t)l] != csf::NO_SW;
 	}
 	if (need_bases && !bases) return cs_fail_(CS_EINVAL, "cs_chain_filter_gpu: the reads are needed for the seed test of long reads");
-	auto up = [&](int which, const void *src, size_t bytes) -> int {
-		if (int rc = ensure(G.b[which], bytes + 64)) return rc;
-		if (bytes) HIP_TRYF(hipMemcpyAsync(G.b[which].p, src, bytes, hipMemcpyHostToDevice, G.s));
-		return CS_OK;
-	};
 	cs_chain_result_t d = *in;
 	if (n > 0) {
-		if (int rc = up(B_IN_CHAIN_OFF, in->chain_off, ((size_t)n + 1) * 8)) return rc;
-		if (int rc = up(B_IN_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
+		if (int rc = G.up(B_IN_CHAIN_OFF, in->chain_off, ((size_t)n + 1) * 8)) return rc;
+		if (int rc = G.up(B_IN_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
 		if (in->n_chains) {
-			if (int rc = up(B_IN_CHAINS, in->chains, (size_t)in->n_chains * sizeof(cs_chain_t))) return rc;
-			if (int rc = up(B_IN_CSEED_OFF, in->cseed_off, ((size_t)in->n_chains + 1) * 8)) return rc;
+			if (int rc = G.up(B_IN_CHAINS, in->chains, (size_t)in->n_chains * sizeof(cs_chain_t))) return rc;
+			if (int rc = G.up(B_IN_CSEED_OFF, in->cseed_off, ((size_t)in->n_chains + 1) * 8)) return rc;
 		}
-		if (in->n_seeds) { if (int rc = up(B_IN_CSEEDS, in->cseeds, (size_t)in->n_seeds * sizeof(cs_seed_t))) return rc; }
-		if (need_bases) { if (int rc = up(B_IN_BASES, bases, (size_t)read_offsets[n])) return rc; }
-		HIP_TRYF(hipStreamSynchronize(G.s));
-		d.chain_off = (const uint64_t *)G.b[B_IN_CHAIN_OFF].p; d.chains = (const cs_chain_t *)G.b[B_IN_CHAINS].p;
-		d.cseed_off = (const uint64_t *)G.b[B_IN_CSEED_OFF].p; d.cseeds = (const cs_seed_t *)G.b[B_IN_CSEEDS].p;
+		if (in->n_seeds) { if (int rc = G.up(B_IN_CSEEDS, in->cseeds, (size_t)in->n_seeds * sizeof(cs_seed_t))) return rc; }
+		if (need_bases) { if (int rc = G.up(B_IN_BASES, bases, (size_t)read_offsets[n])) return rc; }
+		HIP_TRY(hipStreamSynchronize(G.s));
+		d.chain_off = G.at<uint64_t>(B_IN_CHAIN_OFF); d.chains = G.at<cs_chain_t>(B_IN_CHAINS);
+		d.cseed_off = G.at<uint64_t>(B_IN_CSEED_OFF); d.cseeds = G.at<cs_seed_t>(B_IN_CSEEDS);
 	}
 	cs_chain_result_t dr; const int32_t *d_sc = nullptr;
-	if (int rc = filter_device_(c, *par, d, need_bases ? (const uint8_t *)G.b[B_IN_BASES].p : nullptr, n > 0 ? (const uint64_t *)G.b[B_IN_READ_OFF].p : nullptr, flags, dr, &d_sc)) return rc;
-	G.h_chain_off.resize((size_t)n + 1); G.h_chains.resize(dr.n_chains); G.h_cseed_off.resize(dr.n_chains + 1); G.h_cseeds.resize(dr.n_seeds); G.h_score.resize(dr.n_seeds);
-	HIP_TRYF(hipMemcpyAsync(G.h_chain_off.data(), dr.chain_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, G.s));
-	HIP_TRYF(hipMemcpyAsync(G.h_cseed_off.data(), dr.cseed_off, ((size_t)dr.n_chains + 1) * 8, hipMemcpyDeviceToHost, G.s));
-	if (dr.n_chains) HIP_TRYF(hipMemcpyAsync(G.h_chains.data(), dr.chains, (size_t)dr.n_chains * sizeof(cs_chain_t), hipMemcpyDeviceToHost, G.s));
-	if (dr.n_seeds) {
-		HIP_TRYF(hipMemcpyAsync(G.h_cseeds.data(), dr.cseeds, (size_t)dr.n_seeds * sizeof(cs_seed_t), hipMemcpyDeviceToHost, G.s));
-		HIP_TRYF(hipMemcpyAsync(G.h_score.data(), d_sc, (size_t)dr.n_seeds * 4, hipMemcpyDeviceToHost, G.s));
-	}
-	HIP_TRYF(hipStreamSynchronize(G.s));
-	out->n_reads = n; out->n_chains = dr.n_chains; out->n_seeds = dr.n_seeds;
-	out->chain_off = G.h_chain_off.data(); out->chains = G.h_chains.data(); out->cseed_off = G.h_cseed_off.data(); out->cseeds = G.h_cseeds.data();
+	if (int rc = filter_device_(c, *par, d, need_bases ? G.at<uint8_t>(B_IN_BASES) : nullptr, n > 0 ? G.at<uint64_t>(B_IN_READ_OFF) : nullptr, flags, dr, &d_sc)) return rc;
+	if (int rc = cs_download_chains_(G.s, dr, d_sc, G.h_chain_off, G.h_chains, G.h_cseed_off, G.h_cseeds, &G.h_score, out)) return rc;
 	if (cseed_score) *cseed_score = G.h_score.data();
 	return CS_OK;
 }

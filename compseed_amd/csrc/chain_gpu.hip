@@ -16,7 +16,7 @@
 //                     (both counts are at most its seed count); two exclusive scans over the per-read counts give chain_off and the seed
 //                     bases, and this kernel moves the chains and seeds into the output CSR and writes cseed_off.  No overflow case.
 // frac_rep is (float)l_rep / len as on the host: IEEE fp32 division is correctly rounded (no fast-math, no approximate reciprocal).
-#include "cs_internal.hpp"
+#include "dev_stage.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -24,16 +24,6 @@
 #include <vector>
 
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
-
-#define HIP_TRYC(expr)                                                                              \
-	do {                                                                                            \
-		hipError_t e__ = (expr);                                                                    \
-		if (e__ != hipSuccess) {                                                                    \
-			(void)hipGetLastError();                                                                \
-			return cs_fail_(e__ == hipErrorOutOfMemory ? CS_ENOMEM : CS_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-		}                                                                                           \
-	} while (0)
 
 namespace csc {
 constexpr int BT = 5, BMAX = 2 * BT - 1;   // the B-tree of chain.cpp (kb_init(chn, 512) with a 40-byte key)
@@ -363,37 +353,17 @@ __global__ void __launch_bounds__(256) compact_kernel(Args A)
 } // namespace csc
 
 namespace {
-struct Buf { void *p = nullptr; size_t cap = 0; };
-int ensure(Buf &b, size_t bytes)
-{
-	if (bytes <= b.cap) return CS_OK;
-	if (b.p) (void)hipFree(b.p);
-	b.p = nullptr; b.cap = 0;
-	const size_t want = bytes + bytes / 8 + 256;
-	HIP_TRYC(hipMalloc(&b.p, want));
-	b.cap = want;
-	return CS_OK;
-}
 enum { B_CTG_OFF, B_IS_ALT, B_KEY, B_CID, B_POOL, B_NEXT, B_TCH, B_TSD, B_NCH, B_NSD, B_WAVE, B_TREE, B_NODE0, B_ARENA, B_CTR, B_SCAN,
        B_CHAIN_OFF, B_SBASE, B_CSEED_OFF, B_CHAINS, B_CSEEDS,
        B_IN_MEM_OFF, B_IN_MEMS, B_IN_SEED_OFF, B_IN_SEEDS, B_IN_READ_OFF, B_COUNT };   // B_IN_*: cs_chain_batch_gpu's uploads
-constexpr int N_CTR = 8;
 } // namespace
 
-struct cs_chainer_gpu {
-	int device = 0, n_cu = 256, n_ctg = 0; hipStream_t s = nullptr; hipEvent_t ev[4] = {};
-	Buf b[B_COUNT]; unsigned long long *h_ctr = nullptr; cs_chain_stats_t st = {};
-};
+struct cs_chainer_gpu : cs_dev_stage<B_COUNT> { int n_ctg = 0; cs_chain_stats_t st = {}; };
 
 void cs_chainer_gpu_release_(cs_chainer_gpu *g)
 {
 	if (!g) return;
-	(void)hipSetDevice(g->device);
-	if (g->s) (void)hipStreamSynchronize(g->s);
-	for (Buf &b : g->b) if (b.p) (void)hipFree(b.p);
-	for (hipEvent_t e : g->ev) if (e) (void)hipEventDestroy(e);
-	if (g->h_ctr) (void)hipHostFree(g->h_ctr);
-	if (g->s) (void)hipStreamDestroy(g->s);
+	g->release();
 	delete g;
 }
 
@@ -406,20 +376,15 @@ int gpu_init(cs_chainer *c, int device)
 	const hipError_t he = hipGetDeviceCount(&ndev);
 	if (he != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return cs_fail_(CS_EDEVICE, "no HIP device: the device chainer has no CPU path"); }
 	if (device < 0 || device >= ndev) return cs_fail_(CS_EINVAL, "cs_chainer_create_device: no such device");
-	HIP_TRYC(hipSetDevice(device));
-	cs_chainer_gpu *g = new cs_chainer_gpu(); g->device = device; c->gpu = g;
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) g->n_cu = prop.multiProcessorCount;
-	HIP_TRYC(hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking));
-	for (hipEvent_t &e : g->ev) HIP_TRYC(hipEventCreate(&e));
-	HIP_TRYC(hipHostMalloc((void **)&g->h_ctr, N_CTR * sizeof(unsigned long long), hipHostMallocDefault));
+	cs_chainer_gpu *g = new cs_chainer_gpu(); c->gpu = g;   // (released with the chainer, whatever fails below)
+	if (int rc = g->init(device, true)) return rc;
 	const cs_refseq_view &R = c->ref;   // contig offsets and ALT flags, once
 	g->n_ctg = (int)R.offset.size();
 	std::vector<int32_t> alt(R.is_alt.begin(), R.is_alt.end());
-	if (int rc = ensure(g->b[B_CTG_OFF], R.offset.size() * 8 + 8)) return rc;
-	if (int rc = ensure(g->b[B_IS_ALT], alt.size() * 4 + 4)) return rc;
-	HIP_TRYC(hipMemcpy(g->b[B_CTG_OFF].p, R.offset.data(), R.offset.size() * 8, hipMemcpyHostToDevice));
-	HIP_TRYC(hipMemcpy(g->b[B_IS_ALT].p, alt.data(), alt.size() * 4, hipMemcpyHostToDevice));
+	if (int rc = g->ensure(B_CTG_OFF, R.offset.size() * 8 + 8)) return rc;
+	if (int rc = g->ensure(B_IS_ALT, alt.size() * 4 + 4)) return rc;
+	HIP_TRY(hipMemcpy(g->b[B_CTG_OFF].p, R.offset.data(), R.offset.size() * 8, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(g->b[B_IS_ALT].p, alt.data(), alt.size() * 4, hipMemcpyHostToDevice));
 	return CS_OK;
 }
 
@@ -427,7 +392,8 @@ int gpu_init(cs_chainer *c, int device)
 int chain_device_(cs_chainer *c, const cs_chain_params_t &o, const cs_result_t &S, const uint64_t *d_ro, uint32_t flags, cs_chain_result_t &out)
 {
 	cs_chainer_gpu &G = *c->gpu;
-	HIP_TRYC(hipSetDevice(G.device));
+	constexpr int N_CTR = cs_chainer_gpu::N_CTR;
+	HIP_TRY(hipSetDevice(G.device));
 	hipStream_t s = G.s;
 	const int64_t n = S.n_reads;
 	const uint64_t ns = S.n_seeds;
@@ -438,68 +404,56 @@ int chain_device_(cs_chainer *c, const cs_chain_params_t &o, const cs_result_t &
 		{B_TSD, per_seed * sizeof(cs_seed_t)}, {B_NCH, per_read * 8}, {B_NSD, per_read * 8}, {B_WAVE, per_read * 4}, {B_TREE, per_read * 4}, {B_NODE0, per_read * 8},
 		{B_CTR, N_CTR * 8}, {B_CHAIN_OFF, per_read * 8}, {B_SBASE, per_read * 8}, {B_CSEED_OFF, per_seed * 8}, {B_CHAINS, per_seed * sizeof(cs_chain_t)},
 		{B_CSEEDS, per_seed * sizeof(cs_seed_t)}};
-	for (auto &q : need) if (int rc = ensure(G.b[q.which], q.bytes)) return rc;
+	for (auto &q : need) if (int rc = G.ensure(q.which, q.bytes)) return rc;
 	csc::Args A;
 	A.mem_off = S.mem_off; A.seed_off = S.seed_off; A.read_off = d_ro; A.mems = S.mems; A.seeds = S.seeds;
 	A.n_reads = n; A.n_mems = S.n_mems; A.n_seeds = ns; A.l_pac = c->ref.l_pac;
-	A.ctg_off = (const int64_t *)G.b[B_CTG_OFF].p; A.is_alt = (const int32_t *)G.b[B_IS_ALT].p; A.n_ctg = G.n_ctg; A.flags = flags; A.o = o;
-	A.key = (int64_t *)G.b[B_KEY].p; A.cid = (int32_t *)G.b[B_CID].p; A.pool = (csc::Chain *)G.b[B_POOL].p; A.next_of = (uint32_t *)G.b[B_NEXT].p;
-	A.tch = (cs_chain_t *)G.b[B_TCH].p; A.tsd = (cs_seed_t *)G.b[B_TSD].p; A.nch = (uint64_t *)G.b[B_NCH].p; A.nsd = (uint64_t *)G.b[B_NSD].p;
-	A.wave_list = (uint32_t *)G.b[B_WAVE].p; A.tree_list = (uint32_t *)G.b[B_TREE].p; A.tree_node0 = (uint64_t *)G.b[B_NODE0].p; A.arena = nullptr;
-	A.ctr = (unsigned long long *)G.b[B_CTR].p;
-	A.chain_off = (uint64_t *)G.b[B_CHAIN_OFF].p; A.sbase = (uint64_t *)G.b[B_SBASE].p; A.cseed_off = (uint64_t *)G.b[B_CSEED_OFF].p;
-	A.chains = (cs_chain_t *)G.b[B_CHAINS].p; A.cseeds = (cs_seed_t *)G.b[B_CSEEDS].p;
+	A.ctg_off = G.at<int64_t>(B_CTG_OFF); A.is_alt = G.at<int32_t>(B_IS_ALT); A.n_ctg = G.n_ctg; A.flags = flags; A.o = o;
+	A.key = G.at<int64_t>(B_KEY); A.cid = G.at<int32_t>(B_CID); A.pool = G.at<csc::Chain>(B_POOL); A.next_of = G.at<uint32_t>(B_NEXT);
+	A.tch = G.at<cs_chain_t>(B_TCH); A.tsd = G.at<cs_seed_t>(B_TSD); A.nch = G.at<uint64_t>(B_NCH); A.nsd = G.at<uint64_t>(B_NSD);
+	A.wave_list = G.at<uint32_t>(B_WAVE); A.tree_list = G.at<uint32_t>(B_TREE); A.tree_node0 = G.at<uint64_t>(B_NODE0); A.arena = nullptr;
+	A.ctr = G.at<unsigned long long>(B_CTR);
+	A.chain_off = G.at<uint64_t>(B_CHAIN_OFF); A.sbase = G.at<uint64_t>(B_SBASE); A.cseed_off = G.at<uint64_t>(B_CSEED_OFF);
+	A.chains = G.at<cs_chain_t>(B_CHAINS); A.cseeds = G.at<cs_seed_t>(B_CSEEDS);
 	out.n_reads = n; out.chain_off = A.chain_off; out.chains = A.chains; out.cseed_off = A.cseed_off; out.cseeds = A.cseeds;
 	G.st.reads += (uint64_t)n;
 	if (n == 0) {
-		HIP_TRYC(hipMemsetAsync(A.chain_off, 0, 8, s));
-		HIP_TRYC(hipMemsetAsync(A.cseed_off, 0, 8, s));
-		HIP_TRYC(hipStreamSynchronize(s));
 		out.n_chains = 0; out.n_seeds = 0;
-		return CS_OK;
+		return G.empty_csr(A.chain_off, A.cseed_off);
 	}
-	auto grid = [&](int64_t items, int per_block) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)G.n_cu * 16))); };
-	HIP_TRYC(hipMemsetAsync(A.ctr, 0, N_CTR * 8, s));
-	HIP_TRYC(hipMemsetAsync(A.nch + n, 0, 8, s));
-	HIP_TRYC(hipMemsetAsync(A.nsd + n, 0, 8, s));
-	HIP_TRYC(hipEventRecord(G.ev[0], s));
-	hipLaunchKernelGGL(csc::fast_kernel, grid(n, 256), dim3(256), 0, s, A);
+	HIP_TRY(hipMemsetAsync(A.ctr, 0, N_CTR * 8, s));
+	HIP_TRY(hipMemsetAsync(A.nch + n, 0, 8, s));
+	HIP_TRY(hipMemsetAsync(A.nsd + n, 0, 8, s));
+	HIP_TRY(hipEventRecord(G.ev[0], s));
+	hipLaunchKernelGGL(csc::fast_kernel, G.grid(n, 256), dim3(256), 0, s, A);
 	hipLaunchKernelGGL(csc::fast_wave_kernel, dim3((unsigned)G.n_cu * 8), dim3(64), 0, s, A);
-	HIP_TRYC(hipGetLastError());
-	HIP_TRYC(hipEventRecord(G.ev[1], s));
-	HIP_TRYC(hipMemcpyAsync(G.h_ctr, A.ctr, N_CTR * 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYC(hipStreamSynchronize(s));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(G.ev[1], s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.ctr, N_CTR * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	if (G.h_ctr[3]) return cs_fail_(CS_EINVAL, "cs_chain_batch_device: mem_off / seed_off disagree with n_mems / n_seeds");
 	const uint64_t n_tree = G.h_ctr[1], n_nodes = G.h_ctr[2];
 	unsigned launches = 2;
-	HIP_TRYC(hipEventRecord(G.ev[2], s));
+	HIP_TRY(hipEventRecord(G.ev[2], s));
 	if (n_tree) {
-		if (int rc = ensure(G.b[B_ARENA], (size_t)n_nodes * sizeof(csc::Node))) return rc;
-		A.arena = (csc::Node *)G.b[B_ARENA].p;
-		hipLaunchKernelGGL(csc::tree_kernel, grid((int64_t)n_tree, 256), dim3(256), 0, s, A);
+		if (int rc = G.ensure(B_ARENA, (size_t)n_nodes * sizeof(csc::Node))) return rc;
+		A.arena = G.at<csc::Node>(B_ARENA);
+		hipLaunchKernelGGL(csc::tree_kernel, G.grid((int64_t)n_tree, 256), dim3(256), 0, s, A);
 		++launches;
 	}
-	{ // chain_off and the per-read seed bases: exclusive scans over n + 1 counts (the last one 0: the totals)
-		size_t tb = 0, tb2 = 0;
-		HIP_TRYC(rocprim::exclusive_scan(nullptr, tb, A.nch, A.chain_off, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-		HIP_TRYC(rocprim::exclusive_scan(nullptr, tb2, A.nsd, A.sbase, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-		tb = std::max(tb, tb2);
-		if (int rc = ensure(G.b[B_SCAN], tb + 16)) return rc;
-		HIP_TRYC(rocprim::exclusive_scan(G.b[B_SCAN].p, tb, A.nch, A.chain_off, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-		HIP_TRYC(rocprim::exclusive_scan(G.b[B_SCAN].p, tb, A.nsd, A.sbase, (uint64_t)0, (size_t)n + 1, rocprim::plus<uint64_t>(), s));
-	}
-	hipLaunchKernelGGL(csc::compact_kernel, grid(n, 256), dim3(256), 0, s, A);
-	HIP_TRYC(hipGetLastError());
+	// chain_off and the per-read seed bases: exclusive scans over n + 1 counts (the last one 0: the totals)
+	if (int rc = G.scan<uint64_t>(B_SCAN, A.nch, A.chain_off, A.nsd, A.sbase, (size_t)n + 1, 0)) return rc;
+	hipLaunchKernelGGL(csc::compact_kernel, G.grid(n, 256), dim3(256), 0, s, A);
+	HIP_TRY(hipGetLastError());
 	launches += 3;
-	HIP_TRYC(hipEventRecord(G.ev[3], s));
-	HIP_TRYC(hipMemcpyAsync(G.h_ctr, A.chain_off + n, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYC(hipMemcpyAsync(G.h_ctr + 1, A.sbase + n, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYC(hipMemcpyAsync(G.h_ctr + 2, A.ctr + 4, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRYC(hipStreamSynchronize(s));
+	HIP_TRY(hipEventRecord(G.ev[3], s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.chain_off + n, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr + 1, A.sbase + n, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr + 2, A.ctr + 4, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	if (G.h_ctr[2]) return cs_fail_(CS_EDEVICE, "cs_chain_batch_device: a tree outgrew its arena reserve");
 	out.n_chains = G.h_ctr[0]; out.n_seeds = G.h_ctr[1];
-	float ms0 = 0.f, ms1 = 0.f;
-	if (hipEventElapsedTime(&ms0, G.ev[0], G.ev[1]) == hipSuccess && hipEventElapsedTime(&ms1, G.ev[2], G.ev[3]) == hipSuccess) G.st.kernel_ms += (double)ms0 + ms1;
+	G.add_kernel_ms(G.st.kernel_ms);
 	G.st.seeds += ns; G.st.chains += out.n_chains; G.st.tree_reads += n_tree; G.st.launches += launches;
 	return CS_OK;
 }
@@ -538,36 +492,23 @@ extern "C" int cs_chain_batch_gpu(cs_chainer_t *c, const cs_chain_params_t *par,
 {
 	if (int rc = check_call("cs_chain_batch_gpu", c, par, seeds, read_offsets, flags, out)) return rc;
 	cs_chainer_gpu &G = *c->gpu;
-	HIP_TRYC(hipSetDevice(G.device));
+	HIP_TRY(hipSetDevice(G.device));
 	const int64_t n = seeds->n_reads;
 	const uint64_t n_mems = n ? seeds->mem_off[n] : 0, n_seeds = n ? seeds->seed_off[n] : 0;   // (the offsets decide, as in cs_chain_batch)
-	auto up = [&](int which, const void *src, size_t bytes) -> int {
-		if (int rc = ensure(G.b[which], bytes + 64)) return rc;
-		if (bytes) HIP_TRYC(hipMemcpyAsync(G.b[which].p, src, bytes, hipMemcpyHostToDevice, G.s));
-		return CS_OK;
-	};
 	cs_result_t d = *seeds;
 	d.n_mems = n_mems; d.n_seeds = n_seeds;
 	if (n > 0) {
-		if (int rc = up(B_IN_MEM_OFF, seeds->mem_off, ((size_t)n + 1) * 8)) return rc;
-		if (int rc = up(B_IN_MEMS, seeds->mems, (size_t)n_mems * sizeof(cs_intv_t))) return rc;
-		if (int rc = up(B_IN_SEED_OFF, seeds->seed_off, ((size_t)n + 1) * 8)) return rc;
-		if (int rc = up(B_IN_SEEDS, seeds->seeds, (size_t)n_seeds * sizeof(cs_seed_t))) return rc;
-		if (int rc = up(B_IN_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
-		d.mem_off = (const uint64_t *)G.b[B_IN_MEM_OFF].p; d.mems = (const cs_intv_t *)G.b[B_IN_MEMS].p;
-		d.seed_off = (const uint64_t *)G.b[B_IN_SEED_OFF].p; d.seeds = (const cs_seed_t *)G.b[B_IN_SEEDS].p;
+		if (int rc = G.up(B_IN_MEM_OFF, seeds->mem_off, ((size_t)n + 1) * 8)) return rc;
+		if (int rc = G.up(B_IN_MEMS, seeds->mems, (size_t)n_mems * sizeof(cs_intv_t))) return rc;
+		if (int rc = G.up(B_IN_SEED_OFF, seeds->seed_off, ((size_t)n + 1) * 8)) return rc;
+		if (int rc = G.up(B_IN_SEEDS, seeds->seeds, (size_t)n_seeds * sizeof(cs_seed_t))) return rc;
+		if (int rc = G.up(B_IN_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
+		d.mem_off = G.at<uint64_t>(B_IN_MEM_OFF); d.mems = G.at<cs_intv_t>(B_IN_MEMS);
+		d.seed_off = G.at<uint64_t>(B_IN_SEED_OFF); d.seeds = G.at<cs_seed_t>(B_IN_SEEDS);
 	}
 	cs_chain_result_t dr;
-	if (int rc = chain_device_(c, *par, d, n > 0 ? (const uint64_t *)G.b[B_IN_READ_OFF].p : nullptr, flags, dr)) return rc;
-	c->chain_off.resize((size_t)n + 1); c->chains.resize(dr.n_chains); c->cseed_off.resize(dr.n_chains + 1); c->cseeds.resize(dr.n_seeds);
-	HIP_TRYC(hipMemcpyAsync(c->chain_off.data(), dr.chain_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, G.s));
-	HIP_TRYC(hipMemcpyAsync(c->cseed_off.data(), dr.cseed_off, ((size_t)dr.n_chains + 1) * 8, hipMemcpyDeviceToHost, G.s));
-	if (dr.n_chains) HIP_TRYC(hipMemcpyAsync(c->chains.data(), dr.chains, (size_t)dr.n_chains * sizeof(cs_chain_t), hipMemcpyDeviceToHost, G.s));
-	if (dr.n_seeds) HIP_TRYC(hipMemcpyAsync(c->cseeds.data(), dr.cseeds, (size_t)dr.n_seeds * sizeof(cs_seed_t), hipMemcpyDeviceToHost, G.s));
-	HIP_TRYC(hipStreamSynchronize(G.s));
-	out->n_reads = n; out->n_chains = dr.n_chains; out->n_seeds = dr.n_seeds;
-	out->chain_off = c->chain_off.data(); out->chains = c->chains.data(); out->cseed_off = c->cseed_off.data(); out->cseeds = c->cseeds.data();
-	return CS_OK;
+	if (int rc = chain_device_(c, *par, d, n > 0 ? G.at<uint64_t>(B_IN_READ_OFF) : nullptr, flags, dr)) return rc;
+	return cs_download_chains_(G.s, dr, nullptr, c->chain_off, c->chains, c->cseed_off, c->cseeds, nullptr, out);
 }
 
 extern "C" int cs_chainer_stats(const cs_chainer_t *c, cs_chain_stats_t *st)

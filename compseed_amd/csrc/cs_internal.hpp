@@ -17,15 +17,24 @@ int cs_fail_(int code, const std::string &msg); // records the calling thread's 
 struct cs_refseq_view { int64_t l_pac; std::vector<int64_t> offset; std::vector<int32_t> len; std::vector<uint8_t> is_alt; };
 int cs_load_contigs_(const char *prefix, cs_refseq_view &ref);
 int cs_load_pac_(const char *prefix, int64_t l_pac, std::vector<uint8_t> &pac); // <prefix>.pac: four bases per byte, first base in the top bits (bntseq.c:236-237)
-inline uint8_t cs_pac_base_(const std::vector<uint8_t> &pac, int64_t p) { return (uint8_t)((pac[(size_t)(p >> 2)] >> ((~p & 3) << 1)) & 3); }
+// The two base decoders exist once, for the host passes and for the kernels of align_gpu.hip and chain_filter_gpu.hip alike (this header is
+// also compiled as plain C++, where CS_HD is nothing).  cs_pac_base_ returns int: a narrower return type costs csf::sw_kernel a register.
+#ifdef __HIP__
+#define CS_HD __host__ __device__
+#else
+#define CS_HD
+#endif
+CS_HD inline int cs_pac_base_(const uint8_t *pac, int64_t p) { return (pac[p >> 2] >> ((~p & 3) << 1)) & 3; }
+inline uint8_t cs_pac_base_(const std::vector<uint8_t> &pac, int64_t p) { return (uint8_t)cs_pac_base_(pac.data(), p); }
 // ASCII -> code as the reference's table does it (nst_nt4_table, bntseq.c:46-63): ACGT in either case 0..3, '-' 5, everything else 4;
 // bytes 0..4 are codes already (comp_seed.cpp:2258-2260 converts only bytes above 4)
-inline uint8_t cs_base_code_(uint8_t c)
+CS_HD inline uint8_t cs_base_code_(uint8_t c)
 {
 	if (c <= 4) return c;
 	switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; case '-': return 5; default: return 4; }
 }
 
+// The device stage states: what they have in common (device, stream, events, pinned counters, buffers) is cs_dev_stage of dev_stage.hpp.
 // the device side of a chainer (chain_gpu.hip: cs_chain_batch_device / cs_chain_batch_gpu)
 struct cs_chainer_gpu;
 void cs_chainer_gpu_release_(cs_chainer_gpu *g);

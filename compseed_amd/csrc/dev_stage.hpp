@@ -1,0 +1,126 @@
+// dev_stage.hpp -- the host half that the device stage units share (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip; extend.hip and
+// the engine's units take the error macro): the HIP error macro, a grow-only device buffer, the state every stage keeps (device, stream,
+// timing events, pinned counter words, buffers) with its creation, its release and the launch / upload / scan helpers, and the download
+// of a chain result.  Header-only; a stage keeps its own `enum { B_... }` of buffers and its kernels' Args, and derives its state from
+// cs_dev_stage<B_COUNT>.
+#pragma once
+#include "cs_internal.hpp"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+
+#define HIP_TRY(expr)                                                                               \
+	do {                                                                                            \
+		hipError_t e__ = (expr);                                                                    \
+		if (e__ != hipSuccess) {                                                                    \
+			(void)hipGetLastError();                                                                \
+			return cs_fail_(e__ == hipErrorOutOfMemory ? CS_ENOMEM : CS_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); \
+		}                                                                                           \
+	} while (0)
+
+// grow-only device memory; a failed growth leaves the buffer empty (p == nullptr, cap == 0), never dangling
+struct cs_dev_buf { void *p = nullptr; size_t cap = 0; };
+inline int cs_dev_ensure(cs_dev_buf &b, size_t bytes)
+{
+	if (bytes <= b.cap) return CS_OK;
+	if (b.p) (void)hipFree(b.p);
+	b.p = nullptr; b.cap = 0;
+	const size_t want = bytes + bytes / 8 + 256;
+	HIP_TRY(hipMalloc(&b.p, want));
+	b.cap = want;
+	return CS_OK;
+}
+
+template <int N_BUF> struct cs_dev_stage {
+	static constexpr int N_CTR = 8;                                   // pinned counter words, and the size of a stage's device counter block
+	int device = 0, n_cu = 256; hipStream_t s = nullptr; hipEvent_t ev[4] = {};   // ev: two pairs around a call's kernels (init's `timing`)
+	unsigned long long *h_ctr = nullptr; cs_dev_buf b[N_BUF];
+
+	// Whatever init returns, the owner releases the state: release copes with any prefix of this.
+	int init(int device, bool timing)
+	{
+		HIP_TRY(hipSetDevice(device));
+		this->device = device;
+		hipDeviceProp_t prop;
+		if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+		HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+		if (timing) for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+		HIP_TRY(hipHostMalloc((void **)&h_ctr, N_CTR * sizeof(unsigned long long), hipHostMallocDefault));
+		return CS_OK;
+	}
+	void release()   // the stream's work first, then what it used, the stream last
+	{
+		(void)hipSetDevice(device);
+		if (s) (void)hipStreamSynchronize(s);
+		for (cs_dev_buf &x : b) if (x.p) (void)hipFree(x.p);
+		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+		if (h_ctr) (void)hipHostFree(h_ctr);
+		if (s) (void)hipStreamDestroy(s);
+	}
+
+	int ensure(int which, size_t bytes) { return cs_dev_ensure(b[which], bytes); }
+	template <class T> T *at(int which) const { return (T *)b[which].p; }
+	dim3 grid(int64_t items, int per_block = 256) const { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)n_cu * 16))); }
+	int up(int which, const void *src, size_t bytes)   // host -> b[which] on the stream; the caller keeps src alive until it has waited
+	{
+		if (int rc = ensure(which, bytes + 64)) return rc;
+		if (bytes) HIP_TRY(hipMemcpyAsync(b[which].p, src, bytes, hipMemcpyHostToDevice, s));
+		return CS_OK;
+	}
+	// exclusive sums on the stream, rocprim's scratch in b[scratch]; the two-array form: one scratch buffer of the larger size, two scans
+	template <class T> int scan(int scratch, T *in, T *out, size_t n, T init)   // (`in` is not const: the kernels rocprim instantiates carry the iterator types)
+	{
+		size_t tb = 0;
+		HIP_TRY(rocprim::exclusive_scan(nullptr, tb, in, out, init, n, rocprim::plus<T>(), s));
+		if (int rc = ensure(scratch, tb + 16)) return rc;
+		HIP_TRY(rocprim::exclusive_scan(b[scratch].p, tb, in, out, init, n, rocprim::plus<T>(), s));
+		return CS_OK;
+	}
+	template <class T> int scan(int scratch, T *in, T *out, T *in2, T *out2, size_t n, T init)
+	{
+		size_t tb = 0, tb2 = 0;
+		HIP_TRY(rocprim::exclusive_scan(nullptr, tb, in, out, init, n, rocprim::plus<T>(), s));
+		HIP_TRY(rocprim::exclusive_scan(nullptr, tb2, in2, out2, init, n, rocprim::plus<T>(), s));
+		tb = std::max(tb, tb2);
+		if (int rc = ensure(scratch, tb + 16)) return rc;
+		HIP_TRY(rocprim::exclusive_scan(b[scratch].p, tb, in, out, init, n, rocprim::plus<T>(), s));
+		HIP_TRY(rocprim::exclusive_scan(b[scratch].p, tb, in2, out2, init, n, rocprim::plus<T>(), s));
+		return CS_OK;
+	}
+	int empty_csr(uint64_t *chain_off, uint64_t *cseed_off)   // the result of a call without reads: both offset arrays are {0}
+	{
+		HIP_TRY(hipMemsetAsync(chain_off, 0, 8, s));
+		HIP_TRY(hipMemsetAsync(cseed_off, 0, 8, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		return CS_OK;
+	}
+	void add_kernel_ms(double &kernel_ms) const   // ev[0]..ev[1] and ev[2]..ev[3], after the stream has been waited for
+	{
+		float ms0 = 0.f, ms1 = 0.f;
+		if (hipEventElapsedTime(&ms0, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&ms1, ev[2], ev[3]) == hipSuccess) kernel_ms += (double)ms0 + ms1;
+	}
+};
+
+// a chain result in device memory into host vectors (d_score / score: the filter's seed scores, or null), and `out` onto the vectors
+inline int cs_download_chains_(hipStream_t s, const cs_chain_result_t &d, const int32_t *d_score, std::vector<uint64_t> &chain_off, std::vector<cs_chain_t> &chains,
+                               std::vector<uint64_t> &cseed_off, std::vector<cs_seed_t> &cseeds, std::vector<int32_t> *score, cs_chain_result_t *out)
+{
+	const size_t n = (size_t)d.n_reads;
+	chain_off.resize(n + 1); chains.resize(d.n_chains); cseed_off.resize(d.n_chains + 1); cseeds.resize(d.n_seeds);
+	if (score) score->resize(d.n_seeds);
+	HIP_TRY(hipMemcpyAsync(chain_off.data(), d.chain_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(cseed_off.data(), d.cseed_off, ((size_t)d.n_chains + 1) * 8, hipMemcpyDeviceToHost, s));
+	if (d.n_chains) HIP_TRY(hipMemcpyAsync(chains.data(), d.chains, (size_t)d.n_chains * sizeof(cs_chain_t), hipMemcpyDeviceToHost, s));
+	if (d.n_seeds) {
+		HIP_TRY(hipMemcpyAsync(cseeds.data(), d.cseeds, (size_t)d.n_seeds * sizeof(cs_seed_t), hipMemcpyDeviceToHost, s));
+		if (score) HIP_TRY(hipMemcpyAsync(score->data(), d_score, (size_t)d.n_seeds * 4, hipMemcpyDeviceToHost, s));
+	}
+	HIP_TRY(hipStreamSynchronize(s));
+	out->n_reads = d.n_reads; out->n_chains = d.n_chains; out->n_seeds = d.n_seeds;
+	out->chain_off = chain_off.data(); out->chains = chains.data(); out->cseed_off = cseed_off.data(); out->cseeds = cseeds.data();
+	return CS_OK;
+}

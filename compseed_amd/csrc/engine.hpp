@@ -4,9 +4,11 @@
 //                  kernels of the default SMEM path, smem_common.hpp and smem_{reads,fwd,bwd,text,sort}.hpp
 //   pipelines.hip  the host pipeline (cs_engine_submit / collect, blocking host variants) and the device pipeline
 //   inspect.hip    digest and gather of the last result, index validation, primitives, the random-line probe
+//   dev_stage.hpp  HIP_TRY, and the host half shared by the stage units outside the engine (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip)
 // Kernels are defined in the unit that launches them; the headers included by more than one unit hold types and __device__ functions.
 #pragma once
 #include "cs_internal.hpp"
+#include "dev_stage.hpp"
 #include "fm_device.hpp"
 
 #include <algorithm>
@@ -24,15 +26,6 @@ using namespace csd;
 extern thread_local std::string g_err;
 inline int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
-#define HIP_TRY(expr)                                                                              \
-	do {                                                                                           \
-		hipError_t e__ = (expr);                                                                   \
-		if (e__ != hipSuccess) {                                                                   \
-			(void)hipGetLastError();                                                               \
-			return fail(e__ == hipErrorOutOfMemory ? CS_ENOMEM : CS_EDEVICE,                       \
-			            std::string(#expr) + ": " + hipGetErrorString(e__));                       \
-		}                                                                                          \
-	} while (0)
 #define CS_TRY(expr) do { int rc__ = (expr); if (rc__ != CS_OK) return rc__; } while (0)
 
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)std::max<int64_t>(1, (n + block - 1) / block); }

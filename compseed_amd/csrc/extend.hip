@@ -20,7 +20,7 @@
 // code over a scratch area in HBM.  The target row base is a lane-indexed register window, re-read every 64 rows.
 //
 // This kernel is integer-compute-bound (VALU + cross-lane), not HBM-bound: a pair reads its two sequences once and writes 24 bytes.
-#include "cs_internal.hpp"
+#include "dev_stage.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -28,15 +28,6 @@
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-
-#define HIP_TRYX(expr)                                                                              \
-	do {                                                                                            \
-		hipError_t e__ = (expr);                                                                    \
-		if (e__ != hipSuccess) {                                                                    \
-			(void)hipGetLastError();                                                                \
-			return cs_fail_(e__ == hipErrorOutOfMemory ? CS_ENOMEM : CS_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-		}                                                                                           \
-	} while (0)
 
 namespace cse {
 
@@ -538,7 +529,7 @@ static int grow(void **p, size_t *cap, size_t need)
 	if (*p) (void)hipFree(*p);
 	*p = nullptr; *cap = 0;
 	const size_t want = need + need / 4 + 256;
-	HIP_TRYX(hipMalloc(p, want));
+	HIP_TRY(hipMalloc(p, want));
 	*cap = want;
 	return CS_OK;
 }
@@ -559,10 +550,10 @@ extern "C" int cs_extender_create(int device, const cs_ext_params_t *par, cs_ext
 	if (!par) { cs_ext_params_default(&dp); par = &dp; }
 	if (par->e_del < 1 || par->e_ins < 1 || par->o_del < 0 || par->o_ins < 0 || par->zdrop < 0) return cs_fail_(CS_EINVAL, "cs_extender_create: gap extension penalties must be positive, gap opens and zdrop non-negative");
 	int ndev = 0;
-	HIP_TRYX(hipGetDeviceCount(&ndev));
+	HIP_TRY(hipGetDeviceCount(&ndev));
 	if (ndev <= 0) return cs_fail_(CS_EDEVICE, "no HIP device: the extension kernel has no CPU path");
 	if (device < 0 || device >= ndev) return cs_fail_(CS_EINVAL, "device ordinal out of range");
-	HIP_TRYX(hipSetDevice(device));
+	HIP_TRY(hipSetDevice(device));
 	cs_extender *x = new cs_extender();
 	x->device = device;
 	hipDeviceProp_t prop;
@@ -614,11 +605,11 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
                          int32_t w, cs_ext_result_t *d_out)
 {
 	hipStream_t s = x->stream;
-	HIP_TRYX(hipMemsetAsync(x->d_ctr, 0, 4 * sizeof(unsigned long long), s));
+	HIP_TRY(hipMemsetAsync(x->d_ctr, 0, 4 * sizeof(unsigned long long), s));
 	hipLaunchKernelGGL(cse::max_qlen_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)x->n_cu * 8)), dim3(256), 0, s, d_pairs, n, x->d_ctr + 3);
-	HIP_TRYX(hipGetLastError());
-	HIP_TRYX(hipMemcpyAsync(x->h_ctr, x->d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-	HIP_TRYX(hipStreamSynchronize(s));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(x->h_ctr, x->d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	const int64_t max_q = (int64_t)x->h_ctr[3];
 	if (max_q > 65535) return cs_fail_(CS_ERANGE, "cs_extend_batch: a query is longer than 65535 bases (MAX_READ_LEN, mapping/comp_seed.h:39)");
 	if ((int64_t)x->P.best * max_q > (1 << 29)) return cs_fail_(CS_ERANGE, "cs_extend_batch: scores would not fit the kernel's 30-bit range");
@@ -626,7 +617,7 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
 	A.pairs = d_pairs; A.n = n; A.qbuf = d_q; A.tbuf = d_t; A.q_bytes = q_bytes; A.t_bytes = t_bytes; A.out = d_out; A.w = w; A.max_qlen = (int32_t)std::max<int64_t>(max_q, 1);
 	A.P = x->P; A.mat = (const int8_t *)(x->d_ctr + 4); A.scratch = nullptr; A.err = x->d_ctr; A.stat = x->d_ctr + 1;
 	const size_t per_wave = ((size_t)2 * (A.max_qlen + 2) + ((A.max_qlen + 3) >> 2)) * 4; // bytes of LDS per wave
-	HIP_TRYX(hipEventRecord(x->ev0, s));
+	HIP_TRY(hipEventRecord(x->ev0, s));
 	A.packed16 = 0; A.min_qlen16 = x->min_qlen16;
 	int64_t n_lanes = 0;
 	if (x->lanes && n < (1ll << 32)) { // short queries: one pair per lane, pairs sorted by (query-length class, target length, query length)
@@ -634,19 +625,19 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
 		if (int rc = grow(&x->d_keys2, &x->c_keys2, (size_t)n * 4)) return rc;
 		if (int rc = grow(&x->d_idx, &x->c_idx, (size_t)n * 4)) return rc;
 		if (int rc = grow(&x->d_idx2, &x->c_idx2, (size_t)n * 4)) return rc;
-		HIP_TRYX(hipMemsetAsync(x->d_cls, 0, 16 * sizeof(unsigned long long), s));
+		HIP_TRY(hipMemsetAsync(x->d_cls, 0, 16 * sizeof(unsigned long long), s));
 		hipLaunchKernelGGL(cse::lanes_keys_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)x->n_cu * 8)), dim3(256), 0, s, A, (uint32_t *)x->d_keys, (uint32_t *)x->d_idx, x->d_cls);
-		HIP_TRYX(hipGetLastError());
-		HIP_TRYX(hipMemcpyAsync(x->h_cls, x->d_cls, 2 * cse::LANES_NCLASS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(x->h_cls, x->d_cls, 2 * cse::LANES_NCLASS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 		size_t tb = 0;
-		HIP_TRYX(rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)x->d_keys, (uint32_t *)x->d_keys2, (uint32_t *)x->d_idx, (uint32_t *)x->d_idx2, (size_t)n, 0u, 32u, s));
+		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)x->d_keys, (uint32_t *)x->d_keys2, (uint32_t *)x->d_idx, (uint32_t *)x->d_idx2, (size_t)n, 0u, 32u, s));
 		if (int rc = grow(&x->d_sort, &x->c_sort, tb + 16)) return rc;
-		HIP_TRYX(rocprim::radix_sort_pairs(x->d_sort, tb, (uint32_t *)x->d_keys, (uint32_t *)x->d_keys2, (uint32_t *)x->d_idx, (uint32_t *)x->d_idx2, (size_t)n, 0u, 32u, s));
-		HIP_TRYX(hipStreamSynchronize(s));
+		HIP_TRY(rocprim::radix_sort_pairs(x->d_sort, tb, (uint32_t *)x->d_keys, (uint32_t *)x->d_keys2, (uint32_t *)x->d_idx, (uint32_t *)x->d_idx2, (size_t)n, 0u, 32u, s));
+		HIP_TRY(hipStreamSynchronize(s));
 		int64_t first = 0;
 		// one launch per class (its LDS size), the largest first, spread over three streams: the tail of one class is filled by the next
-		HIP_TRYX(hipEventRecord(x->ev_fork, s));
-		for (int k = 0; k < 2; ++k) HIP_TRYX(hipStreamWaitEvent(x->side[k], x->ev_fork, 0));
+		HIP_TRY(hipEventRecord(x->ev_fork, s));
+		for (int k = 0; k < 2; ++k) HIP_TRY(hipStreamWaitEvent(x->side[k], x->ev_fork, 0));
 		int64_t start[2 * cse::LANES_NCLASS]; int by_size[2 * cse::LANES_NCLASS];
 		for (int c = 0; c < 2 * cse::LANES_NCLASS; ++c) { start[c] = first; first += (int64_t)x->h_cls[c]; by_size[c] = c; }
 		std::sort(by_size, by_size + 2 * cse::LANES_NCLASS, [&](int a, int b) { return x->h_cls[a] > x->h_cls[b]; });
@@ -663,9 +654,9 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
 			if (qin) hipLaunchKernelGGL((cse::extend_lanes_kernel<uint32_t, true>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)x->d_idx2, start[c], cnt, qmax);
 			else if (narrow) hipLaunchKernelGGL((cse::extend_lanes_kernel<uint16_t, false>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)x->d_idx2, start[c], cnt, qmax);
 			else hipLaunchKernelGGL((cse::extend_lanes_kernel<uint32_t, false>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)x->d_idx2, start[c], cnt, qmax);
-			HIP_TRYX(hipGetLastError());
+			HIP_TRY(hipGetLastError());
 		}
-		for (int k = 0; k < 2; ++k) { HIP_TRYX(hipEventRecord(x->ev_join[k], x->side[k])); HIP_TRYX(hipStreamWaitEvent(s, x->ev_join[k], 0)); }
+		for (int k = 0; k < 2; ++k) { HIP_TRY(hipEventRecord(x->ev_join[k], x->side[k])); HIP_TRY(hipStreamWaitEvent(s, x->ev_join[k], 0)); }
 		n_lanes = first;
 		A.packed16 = 1;                    // extend_kernel below takes only what the key kernel marked DECLINED
 	}
@@ -676,7 +667,7 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
 			const int wpb = per_wave16 <= 15 * 1024 ? 4 : per_wave16 <= 30 * 1024 ? 2 : 1;
 			const int64_t blocks = std::min<int64_t>((n + wpb - 1) / wpb, (int64_t)x->n_cu * (wpb == 4 ? 8 : wpb == 2 ? 4 : 2));
 			hipLaunchKernelGGL(cse::extend16_kernel, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(64 * wpb), per_wave16 * wpb, s, A);
-			HIP_TRYX(hipGetLastError());
+			HIP_TRY(hipGetLastError());
 			A.packed16 = 1;
 		}
 	}
@@ -691,13 +682,13 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
 		A.scratch = (int32_t *)x->d_scratch;
 		hipLaunchKernelGGL(cse::extend_kernel<false>, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, s, A);
 	}
-	HIP_TRYX(hipGetLastError());
+	HIP_TRY(hipGetLastError());
 done:
-	HIP_TRYX(hipEventRecord(x->ev1, s));
-	HIP_TRYX(hipMemcpyAsync(x->h_ctr, x->d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-	HIP_TRYX(hipStreamSynchronize(s));
+	HIP_TRY(hipEventRecord(x->ev1, s));
+	HIP_TRY(hipMemcpyAsync(x->h_ctr, x->d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
 	float ms = 0.f;
-	HIP_TRYX(hipEventElapsedTime(&ms, x->ev0, x->ev1));
+	HIP_TRY(hipEventElapsedTime(&ms, x->ev0, x->ev1));
 	x->st.pairs += (uint64_t)n; x->st.cells += x->h_ctr[1]; x->st.rows += x->h_ctr[2]; x->st.kernel_ms += ms; x->st.launches++;
 	if (x->h_ctr[0]) return cs_fail_(CS_EINVAL, "cs_extend_batch: " + std::to_string(x->h_ctr[0]) + " pair(s) with qlen < 1, tlen < 0 or offsets outside the sequence buffers (their results are zero)");
 	return CS_OK;
@@ -708,7 +699,7 @@ extern "C" int cs_extend_batch_device(cs_extender_t *x, int64_t n_pairs, const c
 {
 	if (!x || n_pairs < 0 || w < 0 || (n_pairs > 0 && (!d_pairs || !d_out))) return cs_fail_(CS_EINVAL, "cs_extend_batch_device: bad argument");
 	if (n_pairs == 0) return CS_OK;
-	HIP_TRYX(hipSetDevice(x->device));
+	HIP_TRY(hipSetDevice(x->device));
 	return extend_device(x, n_pairs, d_pairs, d_qbuf, q_bytes, d_tbuf, t_bytes, w, d_out);
 }
 
@@ -717,15 +708,15 @@ extern "C" int cs_extend_batch(cs_extender_t *x, int64_t n_pairs, const cs_ext_p
 {
 	if (!x || n_pairs < 0 || w < 0 || (n_pairs > 0 && (!pairs || !out)) || (q_bytes && !qbuf) || (t_bytes && !tbuf)) return cs_fail_(CS_EINVAL, "cs_extend_batch: bad argument");
 	if (n_pairs == 0) return CS_OK;
-	HIP_TRYX(hipSetDevice(x->device));
+	HIP_TRY(hipSetDevice(x->device));
 	if (int rc = grow(&x->d_pairs, &x->c_pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t))) return rc;
 	if (int rc = grow(&x->d_out, &x->c_out, (size_t)n_pairs * sizeof(cs_ext_result_t))) return rc;
 	if (int rc = grow(&x->d_q, &x->c_q, (size_t)q_bytes + 64)) return rc;
 	if (int rc = grow(&x->d_t, &x->c_t, (size_t)t_bytes + 64)) return rc;
 	hipStream_t s = x->stream;
-	HIP_TRYX(hipMemcpyAsync(x->d_pairs, pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t), hipMemcpyHostToDevice, s));
-	if (q_bytes) HIP_TRYX(hipMemcpyAsync(x->d_q, qbuf, (size_t)q_bytes, hipMemcpyHostToDevice, s));
-	if (t_bytes) HIP_TRYX(hipMemcpyAsync(x->d_t, tbuf, (size_t)t_bytes, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(x->d_pairs, pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t), hipMemcpyHostToDevice, s));
+	if (q_bytes) HIP_TRY(hipMemcpyAsync(x->d_q, qbuf, (size_t)q_bytes, hipMemcpyHostToDevice, s));
+	if (t_bytes) HIP_TRY(hipMemcpyAsync(x->d_t, tbuf, (size_t)t_bytes, hipMemcpyHostToDevice, s));
 	const int rc = extend_device(x, n_pairs, (const cs_ext_pair_t *)x->d_pairs, (const uint8_t *)x->d_q, q_bytes, (const uint8_t *)x->d_t, t_bytes, w, (cs_ext_result_t *)x->d_out);
 	const std::string keep = rc != CS_OK ? std::string(cs_last_error()) : std::string();
 	if (rc == CS_OK || rc == CS_EINVAL) { // (CS_EINVAL from skipped pairs: the other results are valid and are delivered)
@@ -742,12 +733,12 @@ extern "C" int cs_extend_batch(cs_extender_t *x, int64_t n_pairs, const cs_ext_p
 extern "C" int cs_extender_upload(cs_extender_t *x, const uint8_t *qbuf, uint64_t q_bytes, const uint8_t *tbuf, uint64_t t_bytes)
 {
 	if (!x || (q_bytes && !qbuf) || (t_bytes && !tbuf)) return cs_fail_(CS_EINVAL, "cs_extender_upload: bad argument");
-	HIP_TRYX(hipSetDevice(x->device));
+	HIP_TRY(hipSetDevice(x->device));
 	if (int rc = grow(&x->d_q, &x->c_q, (size_t)q_bytes + 64)) return rc;
 	if (int rc = grow(&x->d_t, &x->c_t, (size_t)t_bytes + 64)) return rc;
-	if (q_bytes) HIP_TRYX(hipMemcpyAsync(x->d_q, qbuf, (size_t)q_bytes, hipMemcpyHostToDevice, x->stream));
-	if (t_bytes) HIP_TRYX(hipMemcpyAsync(x->d_t, tbuf, (size_t)t_bytes, hipMemcpyHostToDevice, x->stream));
-	HIP_TRYX(hipStreamSynchronize(x->stream));
+	if (q_bytes) HIP_TRY(hipMemcpyAsync(x->d_q, qbuf, (size_t)q_bytes, hipMemcpyHostToDevice, x->stream));
+	if (t_bytes) HIP_TRY(hipMemcpyAsync(x->d_t, tbuf, (size_t)t_bytes, hipMemcpyHostToDevice, x->stream));
+	HIP_TRY(hipStreamSynchronize(x->stream));
 	x->res_q = q_bytes; x->res_t = t_bytes;
 	return CS_OK;
 }
@@ -755,11 +746,11 @@ extern "C" int cs_extend_batch_resident(cs_extender_t *x, int64_t n_pairs, const
 {
 	if (!x || n_pairs < 0 || w < 0 || (n_pairs > 0 && (!pairs || !out))) return cs_fail_(CS_EINVAL, "cs_extend_batch_resident: bad argument");
 	if (n_pairs == 0) return CS_OK;
-	HIP_TRYX(hipSetDevice(x->device));
+	HIP_TRY(hipSetDevice(x->device));
 	if (int rc = grow(&x->d_pairs, &x->c_pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t))) return rc;
 	if (int rc = grow(&x->d_out, &x->c_out, (size_t)n_pairs * sizeof(cs_ext_result_t))) return rc;
 	hipStream_t s = x->stream;
-	HIP_TRYX(hipMemcpyAsync(x->d_pairs, pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t), hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(x->d_pairs, pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t), hipMemcpyHostToDevice, s));
 	const int rc = extend_device(x, n_pairs, (const cs_ext_pair_t *)x->d_pairs, (const uint8_t *)x->d_q, x->res_q, (const uint8_t *)x->d_t, x->res_t, w, (cs_ext_result_t *)x->d_out);
 	const std::string keep = rc != CS_OK ? std::string(cs_last_error()) : std::string();
 	if (rc == CS_OK || rc == CS_EINVAL) {

@@ -1,0 +1,189 @@
+"""One Chainer and one Aligner through a sequence of batches that no single stage test states: the largest golden run (the buffers
+grow), an empty batch, the smallest run, a call the checking kernels refuse with CS_EINVAL, the first run again.  The three device stages
+(chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip) keep their state -- stream, events, pinned counters, grow-only buffers -- in one shared
+layer (compseed_amd/csrc/dev_stage.hpp); after every step each stage's result must be, byte for byte, what freshly created handles return
+for the same input and what the host calls cs_chain_batch / cs_chain_filter return, for the host-array forms and for the *_device forms
+chained on the device.  Then the handles close, and so does a chainer whose filter state was never made."""
+import functools
+
+import numpy as np
+import pytest
+
+import _data
+from test_chain import golden_chains
+from test_gpu_chain_device import _cp, _golden_in
+from test_gpu_extend_chains_device import Dev, _same_regs
+
+pytestmark = pytest.mark.gpu
+
+CHAIN_KEYS = ("chain_off", "chains", "cseed_off", "cseeds")
+FLT_KEYS = CHAIN_KEYS + ("cseed_score",)
+BIG = ("repeat100", "default")            # the golden run with the most seeds and chains (120 reads)
+SMALL = ("ragged", "default")              # a sixth of its chains, but 300 reads: the per-read buffers grow when the others need not
+STEPS = [BIG, None, SMALL, "refused", BIG]                                           # None: the batch without reads
+
+
+def _same(a, b, keys, what):
+    for k in keys:
+        assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), (what, k)
+
+
+@functools.lru_cache(maxsize=None)
+def _batch(run):
+    """-> (mem_off, mems, seed_off, seeds), bases, read offsets, chain parameters of a golden run, or of the batch without reads"""
+    import compseed_amd as ca
+    if run is None:
+        z8 = np.zeros(1, np.uint64)
+        return (z8, np.zeros(0, ca.INTV_DT), z8, np.zeros(0, ca.SEED_DT)), np.zeros(0, np.uint8), z8, ca.ChainParams()
+    z, kw = _data.load_golden(*run)
+    bases, off = _data.load_reads(run[0])
+    mem_off, mems, seed_off, seeds = _golden_in(z)
+    return (np.ascontiguousarray(mem_off, np.uint64), mems, np.ascontiguousarray(seed_off, np.uint64), seeds), bases, off, _cp(kw)
+
+
+class _DevSeeds:
+    """golden seeds in device memory, in the form Chainer.chain_device takes an on-device Result"""
+
+    def __init__(self, dev, seeds_in, n_seeds=None):
+        mem_off, mems, seed_off, seeds = seeds_in
+        self.n_reads, self.n_mems, self.n_seeds = mem_off.size - 1, mems.size, seeds.size if n_seeds is None else n_seeds
+        self.ptr = dict(mem_off=dev.up(mem_off), mems=dev.up(mems), seed_off=dev.up(seed_off), seeds=dev.up(seeds))
+
+
+def _host_pass(chainer, al, run):
+    """chain_gpu -> filter_gpu -> extend_chains over host arrays"""
+    seeds_in, bases, off, cp = _batch(run)
+    ch = chainer.chain_gpu(*seeds_in, off, cp)
+    fl = chainer.filter_gpu(*(ch[k] for k in CHAIN_KEYS), bases, off)
+    return ch, fl, al.extend_chains(*(fl[k] for k in CHAIN_KEYS), bases, off, cseed_score=fl["cseed_score"])
+
+
+def _device_pass(eng, dev, chainer, al, run):
+    """chain_device -> filter_device -> extend_chains_device, every stage reading the one before it in device memory"""
+    import compseed_amd as ca
+    seeds_in, bases, off, cp = _batch(run)
+    d_b, d_o = dev.up(bases), dev.up(off)
+    d = chainer.chain_device(_DevSeeds(dev, seeds_in), d_o, cp)
+    ch = ca.download_chains(eng, d)
+    fd = chainer.filter_device(d, d_b, d_o)
+    fl = ca.download_chains(eng, fd)
+    r = al.extend_chains_device(fd, d_b, d_o)
+    assert (d["n_reads"], fd["n_reads"], r["n_reads"]) == (off.size - 1,) * 3 and r["n_regs"] == fl["cseeds"].size
+    return ch, fl, ca.download_regions(eng, r)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    import compseed_amd as ca
+    ix = ca.Index.load(_data.PREFIX)
+    e = ca.Engine(ix, 0)
+    yield e
+    e.close()
+    ix.close()
+
+
+@pytest.fixture(scope="module")
+def fresh(eng):
+    """run -> the three results of fresh handles (host-array forms and device forms) and of the host calls; computed once per run"""
+    import compseed_amd as ca
+    cache = {}
+
+    def get(run):
+        if run not in cache:
+            seeds_in, bases, off, cp = _batch(run)
+            chainer, al = ca.Chainer(_data.PREFIX, device=0), ca.Aligner(_data.PREFIX, 0)
+            by_host_arrays = _host_pass(chainer, al, run)
+            host_ch = chainer.chain(*seeds_in, off, cp, threads=4)
+            host_fl = chainer.filter(*(host_ch[k] for k in CHAIN_KEYS), bases, off, threads=4)
+            chainer.close(); al.close()
+            chainer, al, dev = ca.Chainer(_data.PREFIX, device=0), ca.Aligner(_data.PREFIX, 0), Dev(eng)
+            by_device_arrays = _device_pass(eng, dev, chainer, al, run)
+            dev.free(); chainer.close(); al.close()
+            for got in (by_host_arrays, by_device_arrays):
+                _same(got[0], host_ch, CHAIN_KEYS, (run, "fresh chainer against cs_chain_batch"))
+                _same(got[1], host_fl, FLT_KEYS, (run, "fresh chainer against cs_chain_filter"))
+            _same_regs(by_device_arrays[2], by_host_arrays[2]["reg_off"], by_host_arrays[2]["regs"], (run, "fresh aligners"))
+            cache[run] = (host_ch, host_fl, by_host_arrays[2])
+        return cache[run]
+    return get
+
+
+def _check(got, want, what):
+    _same(got[0], want[0], CHAIN_KEYS, (what, "chains"))
+    _same(got[1], want[1], FLT_KEYS, (what, "filtered chains"))
+    _same_regs(got[2], want[2]["reg_off"], want[2]["regs"], (what, "regions"))
+
+
+def _refused(call, what):
+    import compseed_amd as ca
+    with pytest.raises(ca.CSError) as ei:
+        call()
+    assert ei.value.code == -1, what
+
+
+def _seed_off_decreasing(seed_off):
+    """a copy in which one read's seeds end before they begin (the next read takes them: nothing reaches beyond n_seeds)"""
+    bad = seed_off.copy()
+    r = int(np.nonzero(bad[:-2] > 0)[0][0])
+    bad[r + 1] = bad[r] - np.uint64(1)
+    return bad
+
+
+def _cseed_off_beyond(cseed_off):
+    bad = cseed_off.copy()
+    bad[-1] += np.uint64(1)                                   # the last chain ends one seed behind n_seeds
+    return bad
+
+
+def test_the_runs_differ_in_size():
+    big, small = _batch(BIG), _batch(SMALL)
+    assert BIG == max(_data.golden_runs(), key=lambda run: golden_chains(*run)["pos"].size)
+    assert big[0][3].size > 2 * small[0][3].size and golden_chains(*BIG)["pos"].size > 2 * golden_chains(*SMALL)["pos"].size > 0
+    assert big[2].size < small[2].size
+
+
+def test_host_array_forms_on_reused_handles(fresh):
+    import compseed_amd as ca
+    chainer, al = ca.Chainer(_data.PREFIX, device=0), ca.Aligner(_data.PREFIX, 0)
+    for i, run in enumerate(STEPS):
+        if run == "refused":
+            seeds_in, bases, off, cp = _batch(BIG)
+            ch, fl, _ = fresh(BIG)
+            _refused(lambda: chainer.chain_gpu(seeds_in[0], seeds_in[1], _seed_off_decreasing(seeds_in[2]), seeds_in[3], off, cp), "seed_off decreasing")
+            _refused(lambda: chainer.filter_gpu(ch["chain_off"], ch["chains"], _cseed_off_beyond(ch["cseed_off"]), ch["cseeds"], bases, off), "cseed_off beyond n_seeds")
+            _refused(lambda: al.extend_chains(fl["chain_off"], fl["chains"], _cseed_off_beyond(fl["cseed_off"]), fl["cseeds"], bases, off, cseed_score=fl["cseed_score"]),
+                     "cseed_off beyond n_seeds")
+            continue
+        _check(_host_pass(chainer, al, run), fresh(run), (i, run))
+    chainer.close(); al.close()
+    assert not chainer._h
+
+
+def test_device_forms_on_reused_handles(eng, fresh):
+    import compseed_amd as ca
+    chainer, al, dev = ca.Chainer(_data.PREFIX, device=0), ca.Aligner(_data.PREFIX, 0), Dev(eng)
+    for i, run in enumerate(STEPS):
+        if run == "refused":
+            seeds_in, bases, off, cp = _batch(BIG)
+            ch, fl, _ = fresh(BIG)
+            d_b, d_o = dev.up(bases), dev.up(off)
+            _refused(lambda: chainer.chain_device(_DevSeeds(dev, seeds_in, n_seeds=seeds_in[3].size - 1), d_o, cp), "n_seeds below seed_off[n_reads]")
+            bad_ch = dev.chains(ch["chain_off"], ch["chains"], _cseed_off_beyond(ch["cseed_off"]), ch["cseeds"])
+            _refused(lambda: chainer.filter_device(bad_ch, d_b, d_o), "cseed_off beyond n_seeds")
+            bad_fl = dev.chains(fl["chain_off"], fl["chains"], _cseed_off_beyond(fl["cseed_off"]), fl["cseeds"])
+            _refused(lambda: al.extend_chains_device(bad_fl, d_b, d_o, d_cseed_score=dev.up(fl["cseed_score"])), "cseed_off beyond n_seeds")
+            continue
+        _check(_device_pass(eng, dev, chainer, al, run), fresh(run), (i, run))
+        dev.free()
+    dev.free(); chainer.close(); al.close()
+
+
+def test_a_chainer_without_filter_state_closes():
+    import compseed_amd as ca
+    seeds_in, _, off, cp = _batch(SMALL)
+    chainer = ca.Chainer(_data.PREFIX, device=0)
+    assert chainer.chain_gpu(*seeds_in, off, cp)["chains"].size > 0 and chainer.filter_stats()["reads"] == 0
+    chainer.close()
+    assert not chainer._h
+    never_used = ca.Chainer(_data.PREFIX, device=0)
+    never_used.close()
