@@ -154,11 +154,15 @@ __global__ void lcp_fill_kernel(const DevIndex ix, const A fsa, uint8_t *lcp)
 		lcp[r] = (r == 0 || r > ix.seq_len) ? 0 : (uint8_t)text_lcp(ix, fsa.get(r - 1), fsa.get(r), 255u);
 }
 template <typename A>
-__global__ void rep_fill_kernel(const DevIndex ix, const A fsa, const uint8_t *lcp, uint8_t *rep)
+__global__ void rep_fill_kernel(const DevIndex ix, const A fsa, const uint8_t *lcp, uint8_t *rep, uint64_t *isa_fuse)
 {
 	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= ix.seq_len; r += (uint64_t)gridDim.x * blockDim.x) {
-		uint8_t a = lcp[r], b = lcp[r + 1];
-		rep[fsa.get(r)] = a > b ? a : b; // row 0 (the empty suffix) writes rep[seq_len] = 0
+		const uint8_t a = lcp[r], b = lcp[r + 1], v = a > b ? a : b;
+		const uint64_t p = fsa.get(r);
+		rep[p] = v; // row 0 (the empty suffix) writes rep[seq_len] = 0
+		// 8-byte inverse-SA entries carry the same byte above the rank (DevIndex::isa_fused): the top byte of entry p, which this thread
+		// alone writes and nothing reads here
+		if (isa_fuse) reinterpret_cast<uint8_t *>(isa_fuse + p)[7] = v;
 	}
 }
 
@@ -330,7 +334,7 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 		if (verbose) { fprintf(stderr, "[cs_engine] text mode: %s\n", ix.text2 ? "on" : "off"); fflush(stderr); }
 	}
 	// re-seeding from the text (smem_text.hpp, r2text_kernel): capped LCP array and repeat-length array, 1 byte per row each
-	ix.lcp = nullptr; ix.rep = nullptr;
+	ix.lcp = nullptr; ix.rep = nullptr; ix.isa_fused = 0;
 	{
 		size_t free_b = 0, total_b = 0;
 		HIP_TRY(hipMemGetInfo(&free_b, &total_b));
@@ -340,16 +344,16 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 			unsigned grid = (unsigned)std::min<uint64_t>((rows + 256) / 256, 1u << 22);
 			if (ix.fsa40) {
 				hipLaunchKernelGGL(lcp_fill_kernel<Pack40>, dim3(grid), dim3(256), 0, c.stream, ix, Pack40{e->d_fsa40.p}, e->d_lcp.p);
-				hipLaunchKernelGGL(rep_fill_kernel<Pack40>, dim3(grid), dim3(256), 0, c.stream, ix, Pack40{e->d_fsa40.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p);
+				hipLaunchKernelGGL(rep_fill_kernel<Pack40>, dim3(grid), dim3(256), 0, c.stream, ix, Pack40{e->d_fsa40.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p, (uint64_t *)nullptr);
 			} else if (ix.fsa32) {
 				hipLaunchKernelGGL(lcp_fill_kernel<Plain<uint32_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint32_t>{e->d_fsa32.p}, e->d_lcp.p);
-				hipLaunchKernelGGL(rep_fill_kernel<Plain<uint32_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint32_t>{e->d_fsa32.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p);
+				hipLaunchKernelGGL(rep_fill_kernel<Plain<uint32_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint32_t>{e->d_fsa32.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p, (uint64_t *)nullptr);
 			} else {
 				hipLaunchKernelGGL(lcp_fill_kernel<Plain<uint64_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint64_t>{e->d_fsa64.p}, e->d_lcp.p);
-				hipLaunchKernelGGL(rep_fill_kernel<Plain<uint64_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint64_t>{e->d_fsa64.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p);
+				hipLaunchKernelGGL(rep_fill_kernel<Plain<uint64_t>>, dim3(grid), dim3(256), 0, c.stream, ix, Plain<uint64_t>{e->d_fsa64.p}, (const uint8_t *)e->d_lcp.p, e->d_rep.p, e->d_isa64.p);
 			}
 			HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(c.stream));
-			ix.lcp = e->d_lcp.p; ix.rep = e->d_rep.p;
+			ix.lcp = e->d_lcp.p; ix.rep = e->d_rep.p; ix.isa_fused = ix.isa64 ? 1u : 0u;
 		}
 		if (verbose) {
 			HIP_TRY(hipMemGetInfo(&free_b, &total_b));

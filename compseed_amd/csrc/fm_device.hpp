@@ -49,6 +49,10 @@ struct DevIndex {
 	// isa64 are then null
 	const uint4 *fsa40;
 	const uint4 *isa40;
+	// isa64 entries carry rep[p] in bits 56..63 above the rank (set by rep_fill_kernel, engine.hip): where a kernel asks "is the k-mer at p
+	// unique, and if so what is its rank" the answer is ONE load (isa_rep_direct).  Wave-uniform; 0 for isa32 / isa40, which have no spare byte
+	// per entry, and when rep[] is off.  Every other reader of isa64 goes through isa_direct, which masks the byte off.
+	uint32_t isa_fused;
 };
 __host__ __device__ inline bool has_full_sa(const DevIndex &ix) { return ix.fsa32 || ix.fsa64 || ix.fsa40; }
 
@@ -342,7 +346,12 @@ __device__ __forceinline__ uint64_t sa_direct(const DevIndex &ix, uint64_t k)
 	return ix.fsa32 ? (uint64_t)ix.fsa32[k] : ix.fsa64 ? ix.fsa64[k] : load40(ix.fsa40, k);
 }
 
-__device__ __forceinline__ uint64_t isa_direct(const DevIndex &ix, uint64_t pos) { return ix.isa32 ? (uint64_t)ix.isa32[pos] : ix.isa64 ? ix.isa64[pos] : load40(ix.isa40, pos); }
+// an isa64 entry: rank in bits 0..39, rep[p] in bits 56..63 when DevIndex::isa_fused.  (Ranks fit: engine creation refuses an index of 2^37
+// symbols or more, whatever the entry width.)
+constexpr uint64_t ISA_RANK_MASK = (1ull << 40) - 1ull;
+__device__ __forceinline__ uint64_t isa_direct(const DevIndex &ix, uint64_t pos) { return ix.isa32 ? (uint64_t)ix.isa32[pos] : ix.isa64 ? ix.isa64[pos] & ISA_RANK_MASK : load40(ix.isa40, pos); }
+// rank and rep[pos] from one load (only where ix.isa_fused)
+__device__ __forceinline__ uint64_t isa_rep_direct(const DevIndex &ix, uint64_t pos, uint32_t &rep) { const uint64_t w = ix.isa64[pos]; rep = (uint32_t)(w >> 56); return w & ISA_RANK_MASK; }
 
 // 32 text bases from position pos on (2 bits each, base j in bits 2j..2j+1); the text buffer is padded
 __device__ __forceinline__ uint64_t text_win(const DevIndex &ix, uint64_t pos)

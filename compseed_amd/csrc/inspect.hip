@@ -140,6 +140,7 @@ __global__ void check_rows_kernel(const DevIndex ix, uint32_t cap, unsigned long
 		if (l >= cap) ++v[4];
 		else if (!(a + l == ix.seq_len || (b + l < ix.seq_len && base(a + l) < base(b + l)))) ++v[0];
 		if (isa_direct(ix, b) != r) ++v[1];
+		else if (ix.isa_fused && (uint32_t)(ix.isa64[b] >> 56) != (uint32_t)ix.rep[b]) ++v[1]; // the rep byte that rides in the entry
 		if (b == 0) { if (r != ix.primary) ++v[2]; }
 		else {
 			if (r == ix.primary) ++v[2];

@@ -292,8 +292,11 @@ static int launch_r3text(const cs_engine *e, PassCtx *c, const SplitRun &R, cons
 	HIP_TRY(hipMemcpyAsync(c->d_cnt_snap.p, c->d_cnt.p, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
 	HIP_TRY(hipEventRecord(c->ev_r3a, s));
 	HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_r3a, 0));
-	hipLaunchKernelGGL(r3text_kernel, dim3((unsigned)std::min<uint64_t>((uint64_t)e->n_cu * 16, ((uint64_t)nb + 255) / 256)), dim3(256), 0, c->stream2, R.A,
-	                   (const uint32_t *)c->d_cnt_snap.p, c->d_sctr.p + SC_R3_TEXT_SEEDS, (const uint8_t *)c->d_pending.p);
+	const dim3 grid((unsigned)std::min<uint64_t>((uint64_t)e->n_cu * 16, ((uint64_t)nb + 255) / 256));
+	// (the instantiation follows the index: 8-byte inverse-SA entries that carry rep[] answer "unique? its rank" with one load)
+	if (e->ix.isa_fused)
+		hipLaunchKernelGGL(r3text_kernel<true>, grid, dim3(256), 0, c->stream2, R.A, (const uint32_t *)c->d_cnt_snap.p, c->d_sctr.p + SC_R3_TEXT_SEEDS, (const uint8_t *)c->d_pending.p);
+	else hipLaunchKernelGGL(r3text_kernel<false>, grid, dim3(256), 0, c->stream2, R.A, (const uint32_t *)c->d_cnt_snap.p, c->d_sctr.p + SC_R3_TEXT_SEEDS, (const uint8_t *)c->d_pending.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->ev_r3b, c->stream2));
 	return CS_OK;

@@ -212,16 +212,19 @@ __global__ __launch_bounds__(256, CS_R2_WAVES) void r2text_kernel(const SplitArg
 // that many neighbours share k1 bases).  At most max_intv - 1 bytes of lcp[] on either side: two cache lines instead of the
 // dozens of bwt_extend calls such a seed costs in a repeat.  False when a capped value (255) would decide.
 // 0: the arrays cannot tell; 1: L; 2: max_intv - 1 neighbours share 255 bases or more (every prefix of up to 254 bases has max_intv occurrences)
-__device__ __forceinline__ int r3_text_len(const DevIndex &ix, uint64_t p, int k1, uint32_t max_intv, int &L, LaneCtr &C)
+// HAVE_ISA: the caller holds ISA[p] already (isa_p, from the fused entry it loaded for rep[p]); otherwise it is read here
+template <bool HAVE_ISA>
+__device__ __forceinline__ int r3_text_len(const DevIndex &ix, uint64_t p, uint64_t isa_p, int k1, uint32_t max_intv, int &L, LaneCtr &C)
 {
 	if (max_intv < 2 || max_intv > 41) return 0;
 	const uint32_t m = max_intv - 1;
 	if (p >= ix.seq_len) return 0;
-	uint64_t up = isa_direct(ix, p), dn = up + 1;
+	uint64_t up = isa_p;
+	if (!HAVE_ISA) { up = isa_direct(ix, p); ++C.isa; }
+	uint64_t dn = up + 1;
 	LcpReader Lu = {ix.lcp, ~0ull, 0, 0}, Ld = {ix.lcp, ~0ull, 0, 0}; // one window per side: ~3 dependent loads instead of up to 19
 	struct Tally { LcpReader &A, &B; LaneCtr &C; __device__ ~Tally() { C.lcp += LcpReader::BYTES * (A.loads + B.loads); } } tally = {Lu, Ld, C};
 	uint32_t mu = Lu.at(up), md = Ld.at(dn), val = 0;
-	++C.isa;
 	for (uint32_t t = 0; t < m; ++t) {
 		val = mu > md ? mu : md;
 		if (val < (uint32_t)k1) { L = k1; return 1; }      // fewer than max_intv occurrences already at k1 bases
@@ -251,11 +254,23 @@ __global__ void mark_pending_kernel(const uint64_t *fq, const unsigned long long
 // `pending[r] == 0` and no more than `cap` mems: every SMEM of the read is in its list.  Then the text answers everything: the mem that
 // covers [x, x + k1) and reaches furthest to the right ends where the longest match from x ends (a longer one would sit in an SMEM of
 // its own, which would be in the list), and if no mem covers it the k1-mer does not occur at all.
+//
+// What the kernel waits for is the chain of dependent round trips per read, at 5 waves/SIMD, so:
+//   * FUSED (DevIndex::isa_fused): rep[p] comes with ISA[p] in one 8-byte entry, so "unique? then its rank" is one round trip, not two
+//     dependent ones.  Chosen per instantiation; isa32 / isa40 indexes run the <false> one, which reads rep[] itself.
+//   * the [begin, end) of the read's first R3_REG (two) mems of rounds 1/2 are loaded once per read and kept in registers (16 bits each:
+//     reads are shorter than 65535 bases); the cover searches scan those and go to memory only for mems beyond them.  Measured at 0, 2, 4
+//     and 6: 2 is fastest, more come back as spills.
+//   * a `complete` read has no other writer of its mem list while this kernel runs, so its slots come from a lane-local counter that
+//     starts at the snapshot count, and out_cnt[r] is stored once at the end; other reads take their slots with atomics as before
+//     (the thin iterations beside the kernel may append to their lists).  One lane emits a read's seeds in order either way.
+template <bool FUSED>
 __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArgs A, const uint32_t *cnt_snap, unsigned long long *n_text_seeds, const uint8_t *pending)
 {
 	const DevIndex &ix = A.ix;
 	const int k1 = A.min_seed_len + 1;
 	const int jk = (A.jump && A.jump_k <= A.min_seed_len) ? A.jump_k : 0;
+	constexpr uint32_t R3_REG = 2; // mems of rounds 1/2 held in registers (measured at 0, 2, 4, 6: DESIGN 4.3)
 	unsigned long long my_q = 0, my_hits = 0, my_text = 0;
 	LaneCtr C = {0, 0, 0, 0, 0};
 	WaveCtr W;
@@ -264,23 +279,56 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 		const uint32_t cs = cnt_snap[r], nm0 = cs < A.cap ? cs : A.cap; // the mems of rounds 1 and 2 known to be complete
 		const bool complete = pending[r] == 0 && cs <= A.cap;
 		const OutMem *mine = A.out + (size_t)r * A.cap;
+		uint32_t mreg[R3_REG]; // begin << 16 | end of mems 0 .. R3_REG - 1 (0: none, covers nothing)
+#pragma unroll
+		for (uint32_t a = 0; a < R3_REG; ++a) {
+			mreg[a] = 0;
+			if (a < nm0) { const uint64_t info = mine[a].info; mreg[a] = (uint32_t)(info >> 32) << 16 | ((uint32_t)info & 0xffffu); }
+		}
+		C.mem += nm0 < R3_REG ? nm0 : R3_REG;
+		auto pos_of = [&](int best) -> uint64_t { // text position of mem `best`
+			++C.sa;
+			return sa_direct(ix, mine[best].x0);
+		};
+		uint32_t next_slot = cs; // complete reads: the next free slot of the read's list
 		int cb = 0, ce = 0; uint64_t cp = 0; // the mem the cursor is in: [cb, ce) at text position cp
 		bool covered = false;
 		int x = 0;
 		PackedReader rd; rd.start(A.seqp, rb, (uint32_t)r, 0);
+		// the mem that covers [x, x + k1) and reaches beyond `ce` furthest (the first of them in list order; any occurrence of it will do)
+		auto cover = [&](int x, int &cb, int &ce) -> int {
+			int best = -1;
+#pragma unroll
+			for (uint32_t a = 0; a < R3_REG; ++a) {
+				const int mb = (int)(mreg[a] >> 16), me = (int)(mreg[a] & 0xffffu);
+				if (x >= mb && x + k1 <= me && me > ce) { best = (int)a; cb = mb; ce = me; }
+			}
+			for (uint32_t a = R3_REG; a < nm0; ++a) {
+				const uint64_t info = mine[a].info; const int mb = (int)(info >> 32), me = (int)(uint32_t)info;
+				++C.mem;
+				if (x >= mb && x + k1 <= me && me > ce) { best = (int)a; cb = mb; ce = me; }
+			}
+			return best;
+		};
+		auto take = [&](uint32_t n) -> uint32_t {
+			if (complete) { const uint32_t k0 = next_slot; next_slot += n; return k0; }
+			return atomicAdd(&A.out_cnt[r], n);
+		};
+		auto put = [&](uint32_t kk, const OutMem &m) {
+			if (kk < A.cap) A.out[(size_t)r * A.cap + kk] = m;
+			else {
+				unsigned long long sl = atomicAdd(A.ovf_cnt, 1ull);
+				if (sl < A.ovf_cap) { OvfRec o = {m, (uint32_t)r, 0}; A.ovf[sl] = o; } else atomicMax(A.err, 1ull);
+			}
+		};
 		while (x < len) {
 			if (rd.at(x) > 3) { ++x; continue; }
 			if (!(x >= cb && x + k1 <= ce)) { // look for a mem that covers [x, x + k1)
 				cb = ce = 0;
-				int best = -1;
-				for (uint32_t a = 0; a < nm0; ++a) { // the one that reaches furthest (any occurrence of it will do)
-					const uint64_t info = mine[a].info; const int mb = (int)(info >> 32), me = (int)(uint32_t)info;
-					++C.mem;
-					if (x >= mb && x + k1 <= me && me > ce) { best = (int)a; cb = mb; ce = me; }
-				}
+				const int best = cover(x, cb, ce);
 				covered = best >= 0;
 				if (covered) {
-					cp = sa_direct(ix, mine[best].x0); ++C.sa;
+					cp = pos_of(best);
 					if (cp >= ix.seq_len || cp + (uint64_t)(ce - cb) > ix.seq_len) cb = ce = 0; // (a mem lies inside the text)
 				}
 			}
@@ -297,50 +345,53 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 			if (x >= cb && x + k1 <= ce && ix.rep) {
 				const uint64_t p = cp + (uint64_t)(x - cb);
 				// Inside a mem the next seeds start k1 apart as long as each k1-mer is unique, so up to four of them are resolved
-				// at once: four rep[] bytes, then eight independent inverse-SA reads, one counter update for the four mems.
-				{
-					constexpr int SPEC = 4;
-					int ns = (ce - x) / k1; if (ns > SPEC) ns = SPEC;
-					uint32_t vj[SPEC];
+				// at once, one counter update for the four mems.  Unfused: four rep[] bytes, then two inverse-SA reads for each of
+				// the leading unique ones.  FUSED: the four entries bring the rep bytes and the forward ranks, and the four
+				// reverse-strand ranks are asked for in the same round trip, before it is known which of them are needed -- the
+				// kernel waits for dependent round trips, it is not short of requests, so a few wasted entries
+				// (about one in five) are cheaper than a second trip.
+				constexpr int SPEC = 4;
+				int ns = (ce - x) / k1; if (ns > SPEC) ns = SPEC; // (>= 1: the mem covers [x, x + k1))
+				uint32_t vj[SPEC]; uint64_t a0[SPEC], a1[SPEC];
 #pragma unroll
-					for (int j = 0; j < SPEC; ++j) vj[j] = j < ns ? (uint32_t)ix.rep[p + (uint64_t)(j * k1)] : 255u;
-					C.rep += (uint32_t)ns; // (single bytes, one line apiece: counted like the 8-byte loads of r2text_kernel)
-					int nu = 0; // leading unique k1-mers
+				for (int j = 0; j < SPEC; ++j) {
+					vj[j] = 255u; a0[j] = a1[j] = 0;
+					if (j < ns) {
+						const uint64_t pj = p + (uint64_t)(j * k1);
+						if (FUSED) { a0[j] = isa_rep_direct(ix, pj, vj[j]); a1[j] = isa_direct(ix, ix.seq_len - (pj + (uint64_t)k1)); } // (pj + k1 <= cp + ce - cb <= seq_len)
+						else vj[j] = (uint32_t)ix.rep[pj];
+					}
+				}
+				if (FUSED) C.isa += 2u * (uint32_t)ns; else C.rep += (uint32_t)ns; // (single entries, one line apiece: a byte of rep[] is counted like the 8-byte loads of r2text_kernel)
+				int nu = 0; // leading unique k1-mers
 #pragma unroll
-					for (int j = 0; j < SPEC; ++j) if (nu == j && vj[j] < (uint32_t)k1) nu = j + 1;
-					if (nu > 0) {
-						uint64_t a0[SPEC], a1[SPEC];
+				for (int j = 0; j < SPEC; ++j) if (nu == j && vj[j] < (uint32_t)k1) nu = j + 1;
+				if (nu > 0) {
+					if (!FUSED) {
 #pragma unroll
 						for (int j = 0; j < SPEC; ++j) {
 							const uint64_t pj = p + (uint64_t)(j * k1);
 							a0[j] = j < nu ? isa_direct(ix, pj) : 0; a1[j] = j < nu ? isa_direct(ix, ix.seq_len - (pj + (uint64_t)k1)) : 0;
 						}
 						C.isa += 2u * (uint32_t)nu;
-						const uint32_t k0 = atomicAdd(&A.out_cnt[r], (uint32_t)nu);
-#pragma unroll
-						for (int j = 0; j < SPEC; ++j) {
-							if (j < nu) {
-								OutMem m = {a0[j], a1[j], 1, (uint64_t)(uint32_t)(x + j * k1) << 32 | (uint32_t)(x + (j + 1) * k1)};
-								const uint32_t kk = k0 + (uint32_t)j;
-								if (kk < A.cap) A.out[(size_t)r * A.cap + kk] = m;
-								else {
-									unsigned long long sl = atomicAdd(A.ovf_cnt, 1ull);
-									if (sl < A.ovf_cap) { OvfRec o = {m, (uint32_t)r, 0}; A.ovf[sl] = o; } else atomicMax(A.err, 1ull);
-								}
-							}
-						}
-						my_q += (unsigned)(nu * (k1 - 1)); my_hits += (unsigned)(nu * (k1 - 1)); my_text += (unsigned)nu;
-						x += nu * k1;
-						continue;
 					}
+					const uint32_t k0 = take((uint32_t)nu);
+#pragma unroll
+					for (int j = 0; j < SPEC; ++j) {
+						if (j < nu) {
+							OutMem m = {a0[j], a1[j], 1, (uint64_t)(uint32_t)(x + j * k1) << 32 | (uint32_t)(x + (j + 1) * k1)};
+							put(k0 + (uint32_t)j, m);
+						}
+					}
+					my_q += (unsigned)(nu * (k1 - 1)); my_hits += (unsigned)(nu * (k1 - 1)); my_text += (unsigned)nu;
+					x += nu * k1;
+					continue;
 				}
-				const uint32_t v = ix.rep[p];
+				// the k1-mer at p is repeated (vj[0] >= k1): a short walk over lcp[] counts its occurrences
 				Intv iv = {0, 0, 0}; bool ok = false;
-				++C.rep;
-				if (v < (uint32_t)k1) { iv.x0 = isa_direct(ix, p); iv.x1 = isa_direct(ix, ix.seq_len - (p + (uint64_t)k1)); iv.x2 = 1; ok = true; C.isa += 2; }
 				int L = k1;
-				if (!ok && k1 < 255) {
-					const int st = r3_text_len(ix, p, k1, (uint32_t)(A.max_mem_intv > 0xffffffffull ? 0xffffffffull : A.max_mem_intv), L, C);
+				if (k1 < 255) {
+					const int st = r3_text_len<FUSED>(ix, p, a0[0], k1, (uint32_t)(A.max_mem_intv > 0xffffffffull ? 0xffffffffull : A.max_mem_intv), L, C);
 					if (st == 1 && x + L <= ce) ok = text_interval(ix, p, (uint32_t)L, iv, C) && iv.x2 < A.max_mem_intv;
 					else if (ce == len && ((st == 1 && x + L > ce) || (st == 2 && ce - x <= 254))) {
 						// Every prefix of [x, len) has max_mem_intv occurrences or more (the mem reaches the read's end, so the read is the
@@ -353,24 +404,21 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 						// ... and where the mem ends inside the read, the longest match from x ends with it -- if no other mem covers x
 						// and reaches further (this one was picked for an earlier x): one base more and nothing is left, which is below
 						// max_mem_intv but reports nothing either (bwt.c:370-371)
-						int best = -1, bmb = cb, bme = ce;
-						for (uint32_t a = 0; a < nm0; ++a) {
-							const uint64_t info = mine[a].info; const int mb = (int)(info >> 32), me = (int)(uint32_t)info;
-							++C.mem;
-							if (x >= mb && x + k1 <= me && me > bme) { best = (int)a; bmb = mb; bme = me; }
-						}
+						int bmb = cb, bme = ce;
+						const int best = cover(x, bmb, bme);
 						if (best < 0) {
 							my_q += (unsigned)(ce - x); my_hits += (unsigned)(ce - x);
 							x = ce + 1;
 							continue;
 						}
-						cb = bmb; ce = bme; cp = sa_direct(ix, mine[best].x0); ++C.sa;
+						cb = bmb; ce = bme; cp = pos_of(best);
 						if (!(cp >= ix.seq_len || cp + (uint64_t)(ce - cb) > ix.seq_len)) continue; // the same question again, inside that mem
 						cb = ce = 0;                                                                // (cannot happen; then the index answers)
 					}
 				}
 				if (ok) {
-					emit_mem(A, (uint32_t)r, iv, (uint32_t)x, (uint32_t)(x + L));
+					const OutMem m = {iv.x0, iv.x1, iv.x2, (uint64_t)(uint32_t)x << 32 | (uint32_t)(x + L)};
+					put(take(1u), m);
 					my_q += (unsigned)(L - 1); my_hits += (unsigned)(L - 1); ++my_text;
 					x += L;
 					continue;
@@ -401,11 +449,15 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 				if (b > 3) { nx = i + 1; break; }
 				if (dead) { if (i - x >= A.min_seed_len) { nx = i + 1; break; } continue; }
 				const Intv y = extend1<false>(ix, ik, 3 - (int)b, W); ++my_q;
-				if (y.x2 < A.max_mem_intv && i - x >= A.min_seed_len) { if (y.x2 > 0) emit_mem(A, (uint32_t)r, y, (uint32_t)x, (uint32_t)(i + 1)); nx = i + 1; break; }
+				if (y.x2 < A.max_mem_intv && i - x >= A.min_seed_len) {
+					if (y.x2 > 0) { const OutMem m = {y.x0, y.x1, y.x2, (uint64_t)(uint32_t)x << 32 | (uint32_t)(i + 1)}; put(take(1u), m); }
+					nx = i + 1; break;
+				}
 				ik = y; dead = y.x2 == 0;
 			}
 			x = nx;
 		}
+		if (complete && next_slot != cs) A.out_cnt[r] = next_slot;
 	}
 	for (int o = 32; o > 0; o >>= 1) { my_q += __shfl_xor(my_q, o); my_hits += __shfl_xor(my_hits, o); my_text += __shfl_xor(my_text, o); }
 	if ((threadIdx.x & 63u) == 0) { atomicAdd(A.n_queries, my_q); if (my_hits) atomicAdd(A.n_sst_hits, my_hits); if (my_text) atomicAdd(n_text_seeds, my_text); }
