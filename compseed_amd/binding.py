@@ -189,6 +189,7 @@ class FltStats(C.Structure):
 
 FLT_WAVE_ONLY = 1     # CS_FLT_WAVE_ONLY: every read through the wave-per-read path of the device chain filter (A/B switch, same results)
 CHAIN_TREE_ONLY = 1   # CS_CHAIN_TREE_ONLY: every read through the B-tree path of the device chainer (A/B switch, same results)
+EXT_VECTOR_ZDROP = 16   # CS_EXT_VECTOR_ZDROP: Z-drop as the reference's vectorised extension tests it (unpriced diagonal shift, live at zdrop 0)
 ALN_DEV_COMPACT = 1   # CS_ALN_DEV_COMPACT: cs_extend_chains_device leaves the purged regions (qe <= qb) behind on the device
 
 

@@ -47,7 +47,10 @@ extern "C" int cs_aligner_create(const char *prefix, int device, const cs_aln_pa
 	if (rc != CS_OK) { delete A; return rc; }
 	cs_ext_params_t xp;
 	for (int i = 0, k = 0; i < 5; ++i) for (int j = 0; j < 5; ++j) xp.mat[k++] = (int8_t)(i == 4 || j == 4 ? -1 : i == j ? o.a : -o.b); // bwa_fill_scmat (bwalib/bwa.c:17-29)
-	xp.o_del = o.o_del; xp.e_del = o.e_del; xp.o_ins = o.o_ins; xp.e_ins = o.e_ins; xp.zdrop = o.zdrop; xp.end_bonus = o.pen_clip5; xp.flags = 0;
+	xp.o_del = o.o_del; xp.e_del = o.e_del; xp.o_ins = o.o_ins; xp.e_ins = o.e_ins; xp.zdrop = o.zdrop; xp.end_bonus = o.pen_clip5;
+	// mem_chain2aln_across_reads_V2 extends through the reference's vectorised code, whose Z-drop test is ksw_extend2's only at unit gap extensions and zdrop > 0
+	// (bandedSWA.cpp ZSCORE8 / ZSCORE16: no gap-extension factor, live at zdrop 0): the stage's regions under -E 2 or -d 0 are that test's (tests/golden/aln2)
+	xp.flags = CS_EXT_VECTOR_ZDROP;
 	// (the end bonus only enters the band limit, ksw.c:402-410; the reference builds one object per side, with pen_clip5 and pen_clip3,
 	// comp_seed.cpp:1702-1708: two extenders are kept when the two differ)
 	A->device = device;

@@ -55,7 +55,7 @@ __device__ __forceinline__ int wave_scan_max(int v) // inclusive: lane l gets ma
 }
 __device__ __forceinline__ int wave_shift_up(int v, int lane0) { return dpp_take<0x138, 0xf>(lane0, v); } // lane l gets v[l-1], lane 0 gets lane0 (wave_shr:1)
 
-struct ExtParams { int32_t match, mismatch, o_del, e_del, o_ins, e_ins, zdrop, end_bonus, best; }; // match / mismatch = mat[0] / mat[1]; best = largest matrix entry
+struct ExtParams { int32_t match, mismatch, o_del, e_del, o_ins, e_ins, zdrop, end_bonus, best, vec_zdrop; }; // match / mismatch = mat[0] / mat[1]; best = largest matrix entry; vec_zdrop: CS_EXT_VECTOR_ZDROP
 
 struct ExtArgs {
 	const cs_ext_pair_t *pairs; int64_t n;
@@ -107,6 +107,7 @@ __global__ __launch_bounds__(256, 8) void extend_kernel(const ExtArgs A)
 		}
 		const uint8_t *qg = A.qbuf + pr.q_off, *tg = A.tbuf + pr.t_off;
 		const bool vec_rule = qlen < 32768 && tlen < 32768 && h0 + (qlen < tlen ? qlen : tlen) * P.match < 32768;
+		const bool vec_zdrop = vec_rule && P.vec_zdrop;           // CS_EXT_VECTOR_ZDROP: for the pairs the reference's vectorised code takes
 		if (A.packed16 && A.out[p].score != DECLINED) continue;   // extend16_kernel ran first and took this pair
 		// ---- row "-1" (ksw.c:398-400): the seed's score decays along the query by one insertion; both arrays cleared
 		const int v1 = h0 > oe_ins ? h0 - oe_ins : 0;
@@ -176,10 +177,10 @@ __global__ __launch_bounds__(256, 8) void extend_kernel(const ExtArgs A)
 			if (row_max > top) {
 				top = row_max; top_i = i; top_j = row_arg;
 				const int d = row_arg - i; off = imax(off, d < 0 ? -d : d);
-			} else if (P.zdrop > 0) { // Z-drop with the diagonal shift priced as a gap extension (ksw.c:461-467)
+			} else if (vec_zdrop || P.zdrop > 0) { // Z-drop with the diagonal shift priced as a gap extension (ksw.c:461-467), or as the reference's vectorised code tests it
 				const int di = i - top_i, dj = row_arg - top_j;
-				if (di > dj) { if (top - row_max - (di - dj) * e_del > P.zdrop) break; }
-				else if (top - row_max - (dj - di) * e_ins > P.zdrop) break;
+				if (di > dj) { if (top - row_max - (di - dj) * (vec_zdrop ? 1 : e_del) > P.zdrop) break; }
+				else if (top - row_max - (dj - di) * (vec_zdrop ? 1 : e_ins) > P.zdrop) break;
 			}
 			const int nbeg = first_nz < end ? first_nz : end;
 			const int jz = hlast != 0 ? end : (last_nz >= nbeg ? last_nz : nbeg - 1);
@@ -344,10 +345,10 @@ __global__ __launch_bounds__(256, 8) void extend16_kernel(const ExtArgs A)
 			if (row_max > top) {
 				top = row_max; top_i = i; top_j = row_arg;
 				const int d = row_arg - i; off = imax(off, d < 0 ? -d : d);
-			} else if (P.zdrop > 0) {
+			} else if (P.vec_zdrop || P.zdrop > 0) {
 				const int di = i - top_i, dj = row_arg - top_j;
-				if (di > dj) { if (top - row_max - (di - dj) * e_del > P.zdrop) break; }
-				else if (top - row_max - (dj - di) * e_ins > P.zdrop) break;
+				if (di > dj) { if (top - row_max - (di - dj) * (P.vec_zdrop ? 1 : e_del) > P.zdrop) break; }
+				else if (top - row_max - (dj - di) * (P.vec_zdrop ? 1 : e_ins) > P.zdrop) break;
 			}
 			const int nbeg = first_nz < end ? first_nz : end;
 			const int jz = hlast != 0 ? end : (last_nz >= nbeg ? last_nz : nbeg - 1);
@@ -476,10 +477,10 @@ __global__ __launch_bounds__(64) void extend_lanes_kernel(const ExtArgs A, const
 		if (m > top) {
 			top = m; top_i = i; top_j = mj;
 			const int d = mj - i; off = imax(off, d < 0 ? -d : d);
-		} else if (P.zdrop > 0) { // Z-drop with the diagonal shift priced as a gap extension (ksw.c:461-467)
+		} else if (P.vec_zdrop || P.zdrop > 0) { // Z-drop with the diagonal shift priced as a gap extension (ksw.c:461-467), or unpriced and live at 0 (CS_EXT_VECTOR_ZDROP)
 			const int di = i - top_i, dj = mj - top_j;
-			if (di > dj) { if (top - m - (di - dj) * e_del > P.zdrop) break; }
-			else if (top - m - (dj - di) * e_ins > P.zdrop) break;
+			if (di > dj) { if (top - m - (di - dj) * (P.vec_zdrop ? 1 : e_del) > P.zdrop) break; }
+			else if (top - m - (dj - di) * (P.vec_zdrop ? 1 : e_ins) > P.zdrop) break;
 		}
 		// the live columns (ksw.c:470-473 look at the arrays as this row leaves them): the zero cells at either edge are usually none or one,
 		// so two short scans are cheaper than keeping track of them in every cell
@@ -560,6 +561,7 @@ extern "C" int cs_extender_create(int device, const cs_ext_params_t *par, cs_ext
 	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) x->n_cu = prop.multiProcessorCount;
 	x->P.match = par->mat[0]; x->P.mismatch = par->mat[1];
 	x->P.o_del = par->o_del; x->P.e_del = par->e_del; x->P.o_ins = par->o_ins; x->P.e_ins = par->e_ins; x->P.zdrop = par->zdrop; x->P.end_bonus = par->end_bonus;
+	x->P.vec_zdrop = (par->flags & CS_EXT_VECTOR_ZDROP) ? 1 : 0;
 	x->P.best = 0;
 	for (int k = 0; k < 25; ++k) x->P.best = std::max<int>(x->P.best, par->mat[k]);
 	// extend16_kernel: int16 arithmetic incl. the F carry's decay over a 128-column chunk, and the vectorised scoring rule written as

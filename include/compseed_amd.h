@@ -390,6 +390,10 @@ typedef struct { int8_t mat[25]; int32_t o_del, e_del, o_ins, e_ins, zdrop, end_
 #define CS_EXT_PACKED16_ALL 2u   /* ... all queries of the 16-bit class through it */
 #define CS_EXT_NO_LANES     4u   /* do not use the one-pair-per-lane kernel for short queries (A/B tests): every pair goes one wave per pair */
 #define CS_EXT_LANES_QIN    8u   /* lane kernel, 8-bit class: the query base inside the score cell (one LDS read per cell, a third more LDS); exact; an experiment */
+#define CS_EXT_VECTOR_ZDROP 16u  /* NOT an A/B switch: Z-drop as the reference's vectorised getScores8 / getScores16 test it (mapping/bandedSWA.cpp ZSCORE8 / ZSCORE16), for the
+                                  * pairs of its two vector classes: the shift off the best cell's diagonal is not multiplied by the gap extension, and zdrop 0 does not
+                                  * switch the test off.  The same function as ksw_extend2's at e_del = e_ins = 1 and zdrop > 0 (mem_opt_init); cs_extend_chains sets it,
+                                  * because mem_chain2aln_across_reads_V2 extends through that code */
 typedef struct { uint64_t q_off, t_off; int32_t qlen, tlen, h0, reserved; } cs_ext_pair_t;   /* reserved: not looked at (the caller's own tag, e.g. the region a pair belongs to) */
 typedef struct { int32_t score, qle, tle, gtle, gscore, max_off; } cs_ext_result_t;
 typedef struct { uint64_t pairs, cells, rows, launches; double kernel_ms; } cs_ext_stats_t;   /* cells = DP cells computed (inside the adaptive band) */

@@ -30,7 +30,7 @@ static inline int imax(int a, int b) { return a > b ? a : b; }
  * side scores w_ambig = -1, equal codes score the match, anything else the mismatch (mapping/bandedSWA.cpp:286-290, AMBIG :44). */
 int cso_bsw_score(const cso_bsw_params_t *P, int vec_rule, int t, int q)
 {
-	if (!vec_rule) return P->mat[5 * t + q];
+	if (!(vec_rule & 1)) return P->mat[5 * t + q];
 	if (t == 4 || q == 4) return -1;
 	return t == q ? P->mat[0] : P->mat[1];
 }
@@ -91,6 +91,10 @@ int cso_extend_pair_rule(const cso_bsw_params_t *P, int vec_rule, int qlen, cons
 		if (row_max > top) {
 			top = row_max; top_i = i; top_j = row_arg;
 			off = imax(off, abs(row_arg - i));
+		} else if (vec_rule & 2) { /* the vectorised code's Z-drop (ZSCORE8 / ZSCORE16, mapping/bandedSWA.cpp:268-281, 311-324): the diagonal shift is not
+		                            * priced by the gap extension (`insdel` is computed and never used) and nothing switches the test off at zdrop 0 */
+			const int di = i - top_i, dj = row_arg - top_j;
+			if (top - row_max - abs(di - dj) > P->zdrop) break;
 		} else if (P->zdrop > 0) { /* Z-drop with the diagonal shift priced as a gap extension (ksw.c:461-467) */
 			const int di = i - top_i, dj = row_arg - top_j;
 			if (di > dj) { if (top - row_max - (di - dj) * P->e_del > P->zdrop) break; }

@@ -106,7 +106,9 @@ typedef struct { int32_t score, qle, tle, gtle, gscore, max_off; } cso_bsw_resul
 void cso_bsw_params_default(cso_bsw_params_t *P);
 int  cso_bsw_score(const cso_bsw_params_t *P, int vec_rule, int t, int q);
 int  cso_bsw_uses_vec_rule(const cso_bsw_params_t *P, int qlen, int tlen, int h0);
-/* vec_rule 0: ksw_extend2 / scalarBandedSWA (the matrix); 1: getScores8 / getScores16 (compare the codes); cso_extend_pair picks as the reference does */
+/* vec_rule 0: ksw_extend2 / scalarBandedSWA (the matrix); 1: getScores8 / getScores16 (compare the codes); cso_extend_pair picks as the reference does.
+ * + 2: Z-drop as the vectorised code tests it -- the diagonal shift unpriced (x 1, not x e_del / e_ins) and the test live at zdrop 0 -- which is
+ * ksw_extend2's test at unit gap extensions and zdrop > 0 (the defaults); 3 = what getScores8 / getScores16 compute at any scoring */
 int  cso_extend_pair_rule(const cso_bsw_params_t *P, int vec_rule, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int w, int h0, cso_bsw_result_t *out);
 int  cso_extend_pair(const cso_bsw_params_t *P, int qlen, const uint8_t *query, int tlen, const uint8_t *target, int w, int h0, cso_bsw_result_t *out);
 int  cso_extend_batch(const cso_bsw_params_t *P, int64_t n, const cso_bsw_pair_t *pairs, const uint8_t *qbuf, const uint8_t *tbuf, int w,

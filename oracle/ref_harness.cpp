@@ -16,6 +16,9 @@
 //   u64 mem_off[n_reads+1];  {u64 x0,x1,x2,info} mems[n_mems]
 //   u64 seed_off[n_reads+1]; {i64 rbeg; i32 qbeg; i32 len} seeds[n_seeds]
 // With --prim FILE N SEED it also dumps known-answer vectors for the primitives (format below at dump_prims).
+// --chains / --aln / --dedup dump the reference's chains, its extension stage and mem_sort_dedup_patch (formats at the options' code below);
+// -A -M -O -Od -Oi -E -Ed -Ei -L -w -d set the scoring fields of mem_opt_t those stages read, --cap-seeds cuts each read's filtered chains to a
+// seed total (reads of exactly 63 / 64 / 65 regions: tests/golden/make_golden.py aln2).
 
 #include <cstdio>
 #include <cstdlib>
@@ -246,12 +249,16 @@ static int time_mode(const mem_opt_t *opt, const bwt_t *bwt, const std::vector<s
 int main(int argc, char **argv)
 {
 	if (argc < 4) {
-		fprintf(stderr, "usage: ref_dump <idx prefix> <reads.txt> <out.bin> [-k INT] [-r FLOAT] [-y INT] [-c INT] [-s INT] [-B batch] [--prim FILE N SEED]\n");
+		fprintf(stderr, "usage: ref_dump <idx prefix> <reads.txt> <out.bin> [-k INT] [-r FLOAT] [-y INT] [-c INT] [-s INT] [-B batch] [--prim FILE N SEED]\n"
+		                "       [--chains FILE] [--aln FILE [--dedup FILE] [--cap-seeds K1,K2,...]] [--time T]\n"
+		                "       scoring (written into mem_opt_t as they are, nothing scaled by -A): [-A match] [-M mismatch] [-O gap open | -Od del | -Oi ins]\n"
+		                "       [-E gap extension | -Ed del | -Ei ins] [-L clip penalty, both ends] [-w band] [-d zdrop]\n");
 		return 1;
 	}
 	mem_opt_t *opt = mem_opt_init();
 	int batch = BATCH_SIZE;
 	const char *prim_fn = 0, *chain_fn = 0, *aln_fn = 0, *dedup_fn = 0; long prim_n = 0; uint64_t prim_seed = 1; int time_threads = 0;
+	std::vector<long> cap_seeds;   // --cap-seeds: read r keeps its leading chains while their seed total stays <= cap_seeds[r % size]
 	for (int i = 4; i < argc; i++) {
 		std::string a = argv[i];
 		if (a == "-k") opt->min_seed_len = atoi(argv[++i]);
@@ -260,6 +267,22 @@ int main(int argc, char **argv)
 		else if (a == "-c") opt->max_occ = atoi(argv[++i]);
 		else if (a == "-s") opt->split_width = atoi(argv[++i]);
 		else if (a == "-B") batch = atoi(argv[++i]);
+		// the scoring fields the stage behind chaining reads (main.cpp's -A -B -O -E -L -w -d; -B is the batch here, so the mismatch is -M).
+		// The values go into opt as given: main.cpp's scaling of the other penalties by -A is not replayed.
+		else if (a == "-A") opt->a = atoi(argv[++i]);
+		else if (a == "-M") opt->b = atoi(argv[++i]);
+		else if (a == "-O") opt->o_del = opt->o_ins = atoi(argv[++i]);
+		else if (a == "-Od") opt->o_del = atoi(argv[++i]);
+		else if (a == "-Oi") opt->o_ins = atoi(argv[++i]);
+		else if (a == "-E") opt->e_del = opt->e_ins = atoi(argv[++i]);
+		else if (a == "-Ed") opt->e_del = atoi(argv[++i]);
+		else if (a == "-Ei") opt->e_ins = atoi(argv[++i]);
+		else if (a == "-L") opt->pen_clip5 = opt->pen_clip3 = atoi(argv[++i]);
+		else if (a == "-w") opt->w = atoi(argv[++i]);
+		else if (a == "-d") opt->zdrop = atoi(argv[++i]);
+		else if (a == "--cap-seeds") {
+			for (const char *p = argv[++i]; *p; ) { char *e; long k = strtol(p, &e, 10); if (e == p || k < 0) { fprintf(stderr, "bad --cap-seeds list\n"); return 1; } cap_seeds.push_back(k); p = *e == ',' ? e + 1 : e; }
+		}
 		else if (a == "--prim") { prim_fn = argv[++i]; prim_n = atol(argv[++i]); prim_seed = strtoull(argv[++i], 0, 10); }
 		else if (a == "--chains") chain_fn = argv[++i];
 		else if (a == "--aln") aln_fn = argv[++i];
@@ -268,6 +291,7 @@ int main(int argc, char **argv)
 		else { fprintf(stderr, "unknown option %s\n", argv[i]); return 1; }
 	}
 	if (batch < 1 || batch > BATCH_SIZE) { fprintf(stderr, "batch must be in [1,%d]\n", BATCH_SIZE); return 1; }
+	bwa_fill_scmat(opt->a, opt->b, opt->mat);   // mem_opt_init filled it for the defaults
 	bwa_verbose = 1;
 	bwaidx_t *idx = bwa_idx_load(argv[1], aln_fn ? BWA_IDX_ALL : chain_fn ? (BWA_IDX_BWT | BWA_IDX_BNS) : BWA_IDX_BWT);
 	if (!idx) { fprintf(stderr, "cannot load index %s\n", argv[1]); return 1; }
@@ -429,6 +453,13 @@ int main(int argc, char **argv)
 				mem_chain_v chn = mem_chain(opt, idx->bns, sq[r].l_seq, match, sd);
 				chn.n = mem_chain_flt(opt, chn.n, chn.a);
 				mem_flt_chained_seeds(opt, idx->bns, idx->pac, sq[r].l_seq, codes[r].data(), chn.n, chn.a);
+				if (!cap_seeds.empty()) { // --cap-seeds: the read's leading chains while their seeds (= regions of the stage) stay within the cap
+					const long cap = cap_seeds[(b0 + r) % cap_seeds.size()];
+					long tot = 0; size_t keep = 0;
+					while (keep < chn.n && tot + chn.a[keep].n <= cap) tot += chn.a[keep++].n;
+					for (size_t c = keep; c < chn.n; c++) free(chn.a[c].seeds);
+					chn.n = keep;
+				}
 				chain_ar[r] = chn;
 				kv_init(reg_ar[r]);
 				for (size_t c = 0; c < chn.n; c++) {

@@ -172,10 +172,10 @@ class BswParams(C.Structure):
                 ("zdrop", C.c_int32), ("end_bonus", C.c_int32)]
 
 
-def bsw_fixture(tag):
-    """tests/golden/bsw1/<tag>.bsw.npz -> dict(mat, meta [n,17] = kind w zdrop end_bonus o_del e_del o_ins e_ins qlen tlen h0 | score qle tle gtle
+def bsw_fixture(tag, directory=None):
+    """tests/golden/bsw1/<tag>.bsw.npz (or <directory>/<tag>.bsw.npz) -> dict(mat, meta [n,17] = kind w zdrop end_bonus o_del e_del o_ins e_ins qlen tlen h0 | score qle tle gtle
     gscore max_off, pairs (BSW_PAIR_DT), qbuf, tbuf, want (BSW_RES_DT))"""
-    z = np.load(os.path.join(BSW_DIR, tag + ".bsw.npz"))
+    z = np.load(os.path.join(directory or BSW_DIR, tag + ".bsw.npz"))
     meta = z["meta"]
     pairs = np.zeros(meta.shape[0], dtype=BSW_PAIR_DT)
     pairs["q_off"], pairs["t_off"] = z["q_off"][:-1], z["t_off"][:-1]
@@ -203,7 +203,8 @@ def bsw_params(mat, key):
 
 
 def bsw_extend(fx, rule=None, threads=4):
-    """the oracle on every record of a fixture; rule None = the reference's dispatch per pair, 0 = matrix (ksw_extend2), 1 = vector rule"""
+    """the oracle on every record of a fixture; rule None = the reference's dispatch per pair, 0 = matrix (ksw_extend2), 1 = vector rule,
+    3 = vector rule and the vectorised code's Z-drop test (cs_oracle.h)"""
     L = lib()
     L.cso_extend_batch.argtypes = [C.POINTER(BswParams), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.cso_extend_pair_rule.argtypes = [C.POINTER(BswParams), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]

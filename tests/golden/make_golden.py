@@ -19,6 +19,10 @@ What is produced (all data, no reference source text):
   c2/config2.json                    `make_golden.py bigref`: md5 of bwaidx's five files for a 64 Mbp genome (its bwt_bwtgen2 branch)
   ddp1/                              `make_golden.py ddp`: the regions mem_sort_dedup_patch leaves, for aln1's and flt1's read sets and one with long gaps (regions merged by the patch)
   flt1/                              `make_golden.py flt`: 90 long reads (800-1500 bases): the reference's unfiltered chains, and what its two chain filters leave (+ regions)
+  aln2/                              `make_golden.py aln2`: the extension stage and mem_sort_dedup_patch where aln1 / ddp1 do not reach: non-default scoring, band and
+                                     Z-drop (`params.*`, with the unfiltered chains), reads at the ends of the contigs and across their join (`ends`), and
+                                     reads cut to exactly 63, 64 and 65 regions (`cap64`).  The recipe checks that the sets reach all that; files are written
+                                     with a fixed time stamp, so a rerun reproduces them byte for byte (aln2/MANIFEST.json)
   alt1/                              `make_golden.py alt`: main100's chains with a <prefix>.alt file naming chr2 (is_alt of the chains)
   c1/config1.json                    BASELINE configs[0] (E. coli-size genome, 100 k x 100 bp reads): the reference's counters and
                                      md5 digests of its complete output (`make_golden.py config1` regenerates only this)
@@ -227,7 +231,7 @@ def parse_bsw(path):
     return mat, meta, qs, ts
 
 
-def save_bsw(path, mat, meta, qs, ts, cap):
+def save_bsw(path, mat, meta, qs, ts, cap, save=np.savez_compressed):
     """drop exact duplicates (tandem arrays extend the same pair hundreds of times), keep at most `cap` records at a constant stride"""
     seen, keep = set(), []
     for i, (r, q, t) in enumerate(zip(meta, qs, ts)):
@@ -240,8 +244,8 @@ def save_bsw(path, mat, meta, qs, ts, cap):
     ql = np.array([len(qs[i]) for i in keep], dtype=np.uint64); tl = np.array([len(ts[i]) for i in keep], dtype=np.uint64)
     q_off = np.zeros(len(keep) + 1, np.uint64); np.cumsum(ql, out=q_off[1:])
     t_off = np.zeros(len(keep) + 1, np.uint64); np.cumsum(tl, out=t_off[1:])
-    np.savez_compressed(path, mat=mat, meta=m, q_off=q_off, t_off=t_off, qbuf=np.frombuffer(b"".join(qs[i] for i in keep), dtype=np.uint8),
-                        tbuf=np.frombuffer(b"".join(ts[i] for i in keep), dtype=np.uint8))
+    save(path, mat=mat, meta=m, q_off=q_off, t_off=t_off, qbuf=np.frombuffer(b"".join(qs[i] for i in keep), dtype=np.uint8),
+         tbuf=np.frombuffer(b"".join(ts[i] for i in keep), dtype=np.uint8))
     return len(meta), len(keep)
 
 
@@ -495,6 +499,141 @@ def make_ddp():
     print(json.dumps({k: v for k, v in summary.items() if k != "md5"}, indent=1))
 
 
+def save_npz(path, **arrays):
+    """np.savez_compressed with a fixed time stamp in the zip entries: the same arrays give the same bytes on every run"""
+    import io, zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            zi = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            zi.compress_type = zipfile.ZIP_DEFLATED
+            zi.external_attr = 0o644 << 16
+            zf.writestr(zi, buf.getvalue(), compresslevel=9)
+
+
+# aln2's parameter sets: name -> (harness flags, the cs_aln_params_t fields they set).  The harness writes the values into mem_opt_t as they
+# are (main.cpp's scaling by -A is not replayed), so every other field of mem_opt_t keeps mem_opt_init's value: min_chain_weight 0,
+# max_chain_extend 1 << 30, max_chain_gap 10000, mask_level 0.5, drop_ratio 0.5, mask_level_redun 0.95.
+ALN2_PARAMS = {
+    "w10": (["-w", "10"], dict(w=10)),                                                                      # retries at 10 -> 20
+    "odei": (["-Od", "4", "-Ei", "3", "-w", "7", "-L", "0"], dict(o_del=4, e_ins=3, w=7, pen_clip5=0, pen_clip3=0)),   # one side of each gap cost alone
+    "a2": (["-A", "2", "-M", "3", "-O", "5", "-E", "2", "-L", "9", "-d", "40"], dict(a=2, b=3, o_del=5, o_ins=5, e_del=2, e_ins=2, pen_clip5=9, pen_clip3=9, zdrop=40)),
+    "w3d0": (["-w", "3", "-d", "0"], dict(w=3, zdrop=0)),                                                   # no region leaves w = 3 and the purge keeps nearly all
+    # scores above 255 at 150 bases.  zdrop stays below 128: the reference's 8-bit class keeps it in a signed byte (_mm256_set1_epi8(zdrop),
+    # bandedSWA.cpp), above 127 it wraps negative and every lane of that class stops after its first row (at -d 150 a 40-base exact match
+    # scored 63 = h0 + 3) -- that build's arithmetic, not the stage's definition
+    "a3big": (["-A", "3", "-M", "7", "-O", "14", "-E", "4", "-L", "12", "-w", "9", "-d", "120"],
+              dict(a=3, b=7, o_del=14, o_ins=14, e_del=4, e_ins=4, pen_clip5=12, pen_clip3=12, w=9, zdrop=120)),
+    "oied": (["-M", "2", "-Oi", "9", "-Ed", "3", "-w", "5", "-d", "60", "-L", "2"], dict(b=2, o_ins=9, e_del=3, w=5, zdrop=60, pen_clip5=2, pen_clip3=2)),   # the other side alone
+}
+ALN2_DEFAULTS = dict(a=1, b=4, o_del=6, e_del=1, o_ins=6, e_ins=1, pen_clip5=5, pen_clip3=5, w=100, zdrop=100)
+
+
+def aln2_end_reads(contigs, n_run):
+    """reads that start or stop at the first or last base of either contig with 0-70 random bases hanging over, reads across the join of the
+    contigs, and reads into and over chr1's N run (bwaidx put random bases there): each in both strands, at 100, 150 and 251 bases"""
+    rng = random.Random(20261018)
+    rnd = lambda k: "".join(rng.choice("ACGT") for _ in range(k))
+    c1, c2 = contigs[0][1], contigs[1][1]
+    reads = []
+    for L in (100, 150, 251):
+        both = lambda r: reads.extend([r, revcomp(r)])
+        for c in (c1, c2):
+            for h in [0] + [rng.randint(1, 70) for _ in range(5)]:
+                both(rnd(h) + c[:L - h])                 # the contig's first base at read position h
+                both(c[len(c) - (L - h):] + rnd(h))      # its last base, then h bases of nothing
+        for cut in [L // 2] + [rng.randint(20, L - 20) for _ in range(3)]:
+            both(c1[len(c1) - cut:] + c2[:L - cut])      # across the join: chr1's tail, chr2's head
+        for at in [0, L // 2] + [rng.randint(10, L - 10) for _ in range(2)]:
+            both(c1[n_run[0] - at:n_run[0] - at + L].replace("N", "A"))   # the N run begins at read position `at`
+    return reads
+
+
+def make_aln2():
+    import tempfile
+    d = os.path.join(HERE, "aln2"); os.makedirs(d, exist_ok=True)
+    g1 = os.path.join(HERE, "g1")
+    fa = gzip.open(os.path.join(g1, "ref.fa.gz"), "rt").read().split(">")[1:]
+    contigs = [(c.split("\n")[0], "".join(c.split("\n")[1:]).upper()) for c in fa]
+    l_pac, join = sum(len(s) for _, s in contigs), len(contigs[0][1])
+    n0 = contigs[0][1].find("N"); n_run = (n0, n0 + len(contigs[0][1][n0:]) - len(contigs[0][1][n0:].lstrip("N")))
+    assert n0 > 300 and n_run[1] - n_run[0] == 57
+    lines = lambda path: [x for x in open(path).read().split("\n")]
+    rep = lines(os.path.join(g1, "repeat100.txt"))[:-1]
+    ind = lines(os.path.join(HERE, "aln1", "indel150_400.txt"))[:-1]
+    gap = lines(os.path.join(HERE, "ddp1", "gap3k.txt"))[:-1]
+    ends = aln2_end_reads(contigs, n_run)
+    read_sets = {"ends": ends, "cap64": rep + ind,
+                 # the mix: indels (retries), the tandem array and the low-complexity stretch (the LDS purge: reads of more than 64 regions), the contigs' ends,
+                 # and 3-kb reads with a gap (chains of 8 and 9 seeds, regions the patch merges)
+                 "params": ind[:60] + rep[10:30] + rep[60:80] + ends[::5] + gap[:20]}
+    assert len(read_sets["params"]) <= 200
+    for name, rd in read_sets.items():
+        open(os.path.join(d, name + ".txt"), "w").write("".join(x + "\n" for x in rd))
+    runs = [("ends", "ends", [], {}), ("cap64", "cap64", ["--cap-seeds", "63,64,65"], {})]
+    runs += [("params." + k, "params", fl, prm) for k, (fl, prm) in ALN2_PARAMS.items()]
+    manifest = {"l_pac": l_pac, "join": join, "sets": {}}
+    cov = {"per_read": [], "chain_n_nondefault": [], "edges": {k: 0 for k in ("0", "join_fwd", "l_pac", "join_rev", "2l_pac")}, "max_score": 0}
+    with tempfile.TemporaryDirectory() as td:
+        tmp, ctmp, atmp, dtmp = (os.path.join(td, x) for x in ("o.bin", "c.bin", "a.bin", "d.bin"))
+        for name, rset, flags, prm in runs:
+            cmd = [os.path.join(REFBIN, "ref_dump"), os.path.join(g1, "ref"), os.path.join(d, rset + ".txt"), tmp, *flags, "--aln", atmp, "--dedup", dtmp]
+            if rset == "params":
+                cmd += ["--chains", ctmp]
+            r = run(cmd)
+            if r.returncode:
+                sys.exit(r.stderr)
+            a, z = parse_aln(atmp), parse_ddp(dtmp)
+            save_npz(os.path.join(d, name + ".aln.npz"), **a)
+            save_npz(os.path.join(d, name + ".ddp.npz"), **z)
+            if rset == "params":
+                save_npz(os.path.join(d, name + ".chains.npz"), **parse_chains(ctmp))
+            live = a["reg_qe"] > a["reg_qb"]
+            w = dict(ALN2_DEFAULTS, **prm)["w"]
+            ws = sorted(set(a["reg_w"][live].tolist()))
+            manifest["sets"][name] = {"reads": rset + ".txt", "n_reads": len(read_sets[rset]), "harness_flags": flags, "aln_params": dict(ALN2_DEFAULTS, **prm),
+                                      "regions": int(live.size), "purged": int((~live).sum()), "after_dedup": int(z["reg_rb"].size), "merged": int((z["reg_n_comp"] > 1).sum()),
+                                      "w_of_live_regions": ws, "reference_leaves_no_2w": 2 * w not in ws, "max_score": int(a["reg_score"].max()),
+                                      "harness": r.stderr.strip().splitlines()[-1]}
+            assert set(ws) <= {w, 2 * w, 4 * w} and w in ws, (name, ws)
+            cov["per_read"] += np.diff(a["reg_off"].astype(np.int64)).tolist()
+            if prm:
+                cov["chain_n_nondefault"] += a["chain_n"].tolist()
+            for f in ("reg_rb", "reg_re"):
+                v = a[f][live]
+                for k, x in (("0", 0), ("join_fwd", join), ("l_pac", l_pac), ("join_rev", 2 * l_pac - join), ("2l_pac", 2 * l_pac)):
+                    cov["edges"][k] += int((v == x).sum())
+            cov["max_score"] = max(cov["max_score"], int(a["reg_score"].max()))
+        # the banded-SW calls behind params.w3d0, recorded from the reference's own program as bsw1's are (oracle/_ref/CompSeed.bswtrace, its -w 3 -d 0): the
+        # vectorised code's Z-drop test at zdrop 0, which ksw_extend2 switches off (tests/test_oracle_bsw.py, test_gpu_extend.py)
+        tr = os.path.join(td, "t.bin")
+        r = subprocess.run([os.path.join(REFBIN, "CompSeed.bswtrace"), "-t", "1", "-w", "3", "-d", "0", os.path.join(g1, "ref"), os.path.join(d, "params.txt")],
+                           env=dict(os.environ, CS_BSW_TRACE=tr), capture_output=True, cwd=td)
+        if r.returncode:
+            sys.exit(r.stderr.decode()[-2000:])
+        n_all, n_kept = save_bsw(os.path.join(d, "params.w3d0.bsw.npz"), *parse_bsw(tr), 1200, save=save_npz)
+        manifest["bsw"] = {"params.w3d0": {"pairs_extended": n_all, "pairs_kept": n_kept, "flags": ["-w", "3", "-d", "0"]}}
+    # the coverage the sets exist for (tests/test_dedup.py asserts the same on the committed files)
+    per_read, cn = np.array(cov["per_read"]), np.array(cov["chain_n_nondefault"])
+    manifest["coverage"] = {"reads_with_63_64_65_regions": [int((per_read == k).sum()) for k in (63, 64, 65)],
+                            "chains_of_8_and_9_seeds_nondefault": [int((cn == k).sum()) for k in (8, 9)],
+                            "live_regions_ending_at": cov["edges"], "max_score": cov["max_score"]}
+    print(json.dumps(manifest["coverage"]))
+    assert min(manifest["coverage"]["reads_with_63_64_65_regions"]) >= 5
+    assert min(manifest["coverage"]["chains_of_8_and_9_seeds_nondefault"]) >= 5
+    assert min(cov["edges"].values()) >= 5
+    assert cov["max_score"] > 255
+    no2w = [k for k, v in manifest["sets"].items() if k.startswith("params.") and v["reference_leaves_no_2w"]]
+    assert no2w == ["params.a2", "params.w3d0"], no2w          # a2 keeps w = 100, which no extension here outgrows; at w = 3 and zdrop = 0 the reference retries nothing
+    sizes = {fn: os.path.getsize(os.path.join(d, fn)) for fn in sorted(os.listdir(d)) if fn != "MANIFEST.json"}
+    assert max(sizes.values()) <= os.path.getsize(os.path.join(HERE, "ddp1", "gap3k.aln.npz")) and sum(sizes.values()) < 3 << 20, sizes
+    manifest["md5"] = {fn: md5(os.path.join(d, fn)) for fn in sizes}
+    json.dump(manifest, open(os.path.join(d, "MANIFEST.json"), "w"), indent=1, sort_keys=True)
+    print(json.dumps({k: v["harness"] for k, v in manifest["sets"].items()}, indent=1))
+    print("aln2: %d files, %d bytes" % (len(sizes), sum(sizes.values())))
+
+
 def main():
     if not os.path.exists(os.path.join(REFBIN, "ref_dump")):
         sys.exit("build the reference harness first: make -C oracle ref")
@@ -510,6 +649,8 @@ def main():
         return make_bsw()
     if len(sys.argv) > 1 and sys.argv[1] == "bigref":
         return make_bigref()
+    if len(sys.argv) > 1 and sys.argv[1] == "aln2":
+        return make_aln2()
     if len(sys.argv) > 1 and sys.argv[1] == "aln":
         return make_aln()
     rng = random.Random(20261003)

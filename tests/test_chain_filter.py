@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import _aln2
 import _data
 from test_chain import golden_chains
 
@@ -89,3 +90,19 @@ def test_long_reads_seed_test_is_the_references(threads):
     with pytest.raises(ca.CSError):
         c.filter(*_chains_in(zc), None, off)                           # the seed test needs the reads
     c.close()
+
+
+@pytest.mark.parametrize("name", _aln2.PARAM_SETS)
+def test_filtered_chains_under_other_scoring_are_the_references(name):
+    """tests/golden/aln2/params.*: the reference's two filters with a, b and the gap costs other than mem_opt_init's (mem_flt_chained_seeds
+    scores a seed's neighbourhood with them; the set's 3-kb reads are long enough for it).  The harness writes the scoring into mem_opt_t
+    as it is, so the filter's other fields keep mem_opt_init's values: FltParams' defaults (min_chain_weight 0, max_chain_extend 1 << 30)."""
+    import compseed_amd as ca
+    zc, z = _aln2.npz(name, "chains"), _aln2.npz(name, "aln")
+    bases, off = _aln2.reads(name)
+    p = _aln2.MANIFEST["sets"][name]["aln_params"]
+    c = ca.Chainer(_data.PREFIX)
+    got = c.filter(*_chains_in(zc), bases, off, params=ca.FltParams(**{k: p[k] for k in ("a", "b", "o_del", "e_del", "o_ins", "e_ins")}), threads=2)
+    c.close()
+    check_filtered(got, z)
+    assert got["chains"].size < zc["pos"].size and (z["cseed_score"] != z["cseed_len"]).sum() > 0

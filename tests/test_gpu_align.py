@@ -2,12 +2,14 @@
 mem_chain2aln_across_reads_V2 (mapping/comp_seed.cpp:1319-2237): tests/golden/aln1/ holds, for five read sets, the chains the reference fed
 into it (after its own mem_chain_flt / mem_flt_chained_seeds) and every alignment region it left -- rb re qb qe rid score truesc w seedcov
 seedlen0 frac_rep, the region's chain, purged regions (qb = qe = -1) included (oracle/ref_harness.cpp --aln, tests/golden/make_golden.py aln).
-The library must reproduce every field of every region, in the reference's order."""
+The library must reproduce every field of every region, in the reference's order.  tests/golden/aln2/ (make_golden.py aln2) holds the same for scoring, band
+and Z-drop other than mem_opt_init's, for reads at the ends of the contigs and across their join, and for reads of exactly 63, 64 and 65 regions."""
 import os
 
 import numpy as np
 import pytest
 
+import _aln2
 import _data
 
 pytestmark = pytest.mark.gpu
@@ -58,6 +60,51 @@ def test_alignment_regions_are_the_references(name, flags):
     assert np.array_equal(g["frac_rep"].view(np.uint32), z["reg_frac_rep"].view(np.uint32))
     assert st["regions"] == g.size and st["purged"] == int(purged.sum()) and st["pairs"] >= st["regions"] // 2
     assert g.size > 4000 and purged.sum() > 1000
+
+
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
+@pytest.mark.parametrize("name", _aln2.SETS)
+def test_aln2_regions_are_the_references(name, flags):
+    """tests/golden/aln2: every set with the cs_aln_params_t the reference ran with (a b o_del e_del o_ins e_ins pen_clip w zdrop: what affordable_gap,
+    window_kernel, emit_region, apply_kernel, the purge kernels, the retry band and the extender's matrix read), at the four flags of the test above.
+    ends: windows clipped at 0, at 2 * l_pac, between the strands and at the contigs' join on either strand; cap64: reads of exactly 63, 64 (purge_kernel's
+    all-lanes mask) and 65 regions (the first for purge_big_kernel); params.*: six scorings over 159 reads with retries, chains of 8 and 9 seeds and reads for
+    the LDS purge.  All twelve fields and reg_off as the reference left them, frac_rep bit for bit, and the purge's counter."""
+    import compseed_amd as ca
+    z = _aln2.npz(name, "aln")
+    bases, off = _aln2.reads(name)
+    chain_off, chains, cseed_off, cseeds, score = _aln2.chains_in(z)
+    al = ca.Aligner(_data.PREFIX, 0, _aln2.aln_params(name, flags=flags))
+    got = al.extend_chains(chain_off, chains, cseed_off, cseeds, bases, off, cseed_score=score)
+    st = al.stats()
+    al.close()
+    assert np.array_equal(got["reg_off"], z["reg_off"])
+    g = got["regs"]
+    purged = (z["reg_qb"] == -1) & (z["reg_qe"] == -1)
+    bad = {f: int((g[f] != z["reg_" + f]).sum()) for f in ("rb", "re", "qb", "qe", "rid", "score", "truesc", "w", "seedcov", "seedlen0", "chain")}
+    bad["frac_rep"] = int((g["frac_rep"].view(np.uint32) != z["reg_frac_rep"].view(np.uint32)).sum())
+    print("aln2 %s flags %d: %d regions, purged %d (reference %d), retries %d, fields that differ: %s" % (name, flags, g.size, st["purged"], int(purged.sum()), st["retries"],
+                                                                                                      {k: v for k, v in bad.items() if v} or "none"))
+    assert np.array_equal((g["qb"] == -1) & (g["qe"] == -1), purged), (name, int(((g["qb"] == -1) & (g["qe"] == -1)).sum()), int(purged.sum()))
+    for f in ("rb", "re", "qb", "qe", "rid", "score", "truesc", "w", "seedcov", "seedlen0", "chain"):
+        assert np.array_equal(g[f], z["reg_" + f]), (name, f, bad[f])
+    assert np.array_equal(g["frac_rep"].view(np.uint32), z["reg_frac_rep"].view(np.uint32))
+    assert st["regions"] == g.size and st["purged"] == int(purged.sum())
+    if not _aln2.MANIFEST["sets"][name]["reference_leaves_no_2w"] and name in _aln2.PARAM_SETS: assert st["retries"] > 0
+
+
+def test_unequal_clip_penalties_are_still_refused():
+    """one extender, one end bonus: pen_clip5 != pen_clip3 is CS_EINVAL from both entry points, before any array is looked at"""
+    import compseed_amd as ca
+    z = np.zeros
+    al = ca.Aligner(_data.PREFIX, 0, ca.AlnParams(pen_clip5=5, pen_clip3=7))
+    with pytest.raises(ca.CSError) as ei:
+        al.extend_chains(z(1, np.uint64), z(0, ca.CHAIN_DT), z(1, np.uint64), z(0, ca.SEED_DT), z(0, np.uint8), z(1, np.uint64))
+    assert ei.value.code == -1
+    with pytest.raises(ca.CSError) as ei:
+        al.extend_chains_device(dict(n_reads=0, n_chains=0, n_seeds=0, chain_off=None, chains=None, cseed_off=None, cseeds=None), None, None)
+    assert ei.value.code == -1
+    al.close()
 
 
 @pytest.mark.parametrize("name", ["sorted150", "indel150_400", "long90", "gap3k"])

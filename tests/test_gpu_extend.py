@@ -5,6 +5,8 @@
   * against the oracle (oracle/cs_bsw_oracle.c, itself pinned by the same fixtures) on fresh random pairs incl. queries of several hundred and
     several thousand bases (multi-chunk rows, the two-wave and one-wave LDS layouts, the HBM-scratch variant), and the device-pointer variant;
   * error behaviour: bad pairs are reported by code, the others are still delivered."""
+import os
+
 import numpy as np
 import pytest
 
@@ -49,6 +51,20 @@ def test_ksw_extend2_known_answers():
             got = _run_fixture(ca, fx, flags)
             for f in ca.EXT_RES_DT.names:
                 assert np.array_equal(got[f], fx["want"][f]), (tag, flags, f, int((got[f] != fx["want"][f]).sum()))
+
+
+@pytest.mark.parametrize("flags", [16, 16 | 2, 16 | 4, 16 | 8], ids=["lane per pair", "packed16 for all", "wave per pair only", "lane per pair, base in the cell"])
+@pytest.mark.parametrize("tag", ["indel150.asym", "params.w3d0", "indel150.default"])
+def test_vector_zdrop_gives_the_vectorised_codes_numbers(tag, flags):
+    """CS_EXT_VECTOR_ZDROP (what cs_extend_chains sets): the reference's getScores8 / getScores16 where they are not ksw_extend2 -- gap extensions
+    other than 1 (-O 5,8 -E 2,1 -d 40) and zdrop 0 (-w 3 -d 0: the extensions behind tests/golden/aln2/params.w3d0) -- and where they are (the
+    defaults), from every kernel: all six outputs of every recorded pair (tests/test_oracle_bsw.py has the oracle's side of it)"""
+    import compseed_amd as ca
+    assert ca.EXT_VECTOR_ZDROP == 16
+    fx = _oracle.bsw_fixture(tag, os.path.join(os.path.dirname(_oracle.BSW_DIR), "aln2") if tag.startswith("params.") else None)
+    got = _run_fixture(ca, fx, flags)
+    for f in ca.EXT_RES_DT.names:
+        assert np.array_equal(got[f], fx["want"][f]), (tag, f, int((got[f] != fx["want"][f]).sum()))
 
 
 def _random_pairs(rng, n, qlo, qhi, p_sub=0.03, p_gap=0.01):

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import _aln2
 import _data
 from test_gpu_align import DDP, _load
 from test_gpu_chain_device import ENGINE_RUNS, _cp
@@ -153,6 +154,31 @@ def test_uploaded_golden_chains_give_the_references_regions(eng, dev, name, afla
         assert r["n_regs"] == live.size == int((regs["qe"] > regs["qb"]).sum())
         _same_regs(got, new_off, live, name)
     assert {k: st[k] for k in COUNTERS} == want and st["regions"] == regs.size and st["purged"] == int((regs["qe"] <= regs["qb"]).sum())
+
+
+@gpu
+@pytest.mark.parametrize("dflags", DEV_FLAGS)
+@pytest.mark.parametrize("name", _aln2.SETS)
+def test_uploaded_aln2_chains_give_the_references_regions(eng, dev, name, dflags):
+    """tests/golden/aln2 (other scoring, band and Z-drop; the ends of the reference; reads of 63, 64 and 65 regions) through cs_extend_chains_device with the
+    set's cs_aln_params_t: the reference's regions byte for byte, the purged ones kept or left behind, and the purge's counter"""
+    import compseed_amd as ca
+    z = _aln2.npz(name, "aln")
+    bases, off = _aln2.reads(name)
+    batch = _aln2.chains_in(z)
+    reg_off, regs = _aln2.regions(z)
+    d = dev.chains(*batch[:4])
+    d_sc, d_b, d_o = dev.up(batch[4]), dev.up(bases), dev.up(off)
+    al = ca.Aligner(_data.PREFIX, 0, _aln2.aln_params(name))
+    r = al.extend_chains_device(d, d_b, d_o, d_cseed_score=d_sc, flags=dflags)
+    st = al.stats()
+    got = ca.download_regions(eng, r)
+    al.close()
+    assert r["n_reads"] == off.size - 1
+    want = (reg_off, regs) if dflags == 0 else _live(reg_off, regs)
+    assert r["n_regs"] == want[1].size
+    _same_regs(got, *want, name)
+    assert st["regions"] == regs.size and st["purged"] == int((regs["qe"] <= regs["qb"]).sum())
 
 
 @gpu
