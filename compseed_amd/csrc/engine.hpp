@@ -141,11 +141,13 @@ enum : int {
 enum : int {
 	CTR_TASK = 0,          // task dispenser of the fused kernel
 	CTR_FETCHED = 0,       // h_ctr only: where a single fetched word (a running total) lands
+	CTR_FETCHED2 = 1,      // h_ctr only: ... and the second of a pair (place_mems: the seed total beside the mem total)
 	CTR_QUERIES = 1,       // bwt_extend queries of the fused kernel
 	CTR_OVERFLOW = 2,      // reads with more than `cap` mems (fused path)
 	CTR_MAX_LEN = 3,       // longest read of the batch
 	CTR_BAD_OFFSETS = 4,   // offsets that do not tile [0, n_bases)
 	CTR_SAL_DISTINCT = 5,  // distinct SA slots per 512-read batch (engine option count_sal_merged)
+	CTR_SEED_RANGE = 6,    // raised by sort_expand16_kernel / sal_expand_heavy_kernel: a read's seeds did not fill its range of seed_off[] exactly
 	CTR_WORDS = 8
 };
 // What one seeding pass owns.  An engine has one or two of them: the tail of a pass (late iterations with a few thousand calls each,
@@ -161,11 +163,12 @@ struct PassCtx {
 	DevBuf<uint8_t> d_seq; DevBuf<uint4> d_seqp; const uint4 *seqp_cur = nullptr; const uint64_t *off_base = nullptr; // d_seqp: pack_reads_kernel's records for the batch whose offsets start at off_base
 	// SMEM stage
 	DevBuf<OutMem> d_out, d_out2; DevBuf<uint32_t> d_cnt, d_cnt2, d_ovf; DevBuf<uint4> d_spill;
+	DevBuf<uint32_t> d_scnt; // SA slots per read, counted beside d_cnt while the split kernels emit the mems (SplitArgs::out_scnt)
 	DevBuf<unsigned long long> d_ctr; // CTR_WORDS words: the CTR_* enum above for seed_pass.hip, anonymous scratch for inspect.hip
 	DevBuf<uint8_t> d_tmp, d_tmp2;
 	PinBuf<unsigned long long> h_ctr;
 	// results (device)
-	DevBuf<uint64_t> d_mem_off, d_seed_off, d_seed_of_mem; DevBuf<OutMem> d_mems; DevBuf<uint64_t> d_salcnt; DevBuf<OutSeed> d_seeds; // d_salcnt: SA slots per mem, written by the sort that makes d_mems
+	DevBuf<uint64_t> d_mem_off, d_seed_off, d_seed_of_mem; DevBuf<OutMem> d_mems; DevBuf<uint64_t> d_salcnt; DevBuf<OutSeed> d_seeds; // d_salcnt: SA slots per mem, written by the sort that makes d_mems; with d_seed_of_mem only where run_sal runs (seed_pass.hip)
 	// split (forward / cooperative backward) SMEM path
 	DevBuf<uint64_t> d_fqA, d_fqB, d_fqR; DevBuf<uint4> d_sst2; DevBuf<BTask> d_bq; DevBuf<uint4> d_lep; DevBuf<OvfRec> d_ovfrec;
 	DevBuf<uint32_t> d_okey, d_oidx, d_okey2, d_oidx2; DevBuf<uint64_t> d_okey64, d_okey64b; DevBuf<unsigned long long> d_sctr; PinBuf<unsigned long long> h_sctr;
@@ -178,7 +181,7 @@ struct PassCtx {
 	{
 		uint64_t b = 0;
 		auto add = [&b](const auto &...buf) { ((b += (uint64_t)buf.cap * sizeof(*buf.p)), ...); };
-		add(d_pending, d_cnt_snap, d_aux, d_seq, d_seqp, d_out, d_out2, d_cnt, d_cnt2, d_ovf, d_spill, d_ctr, d_tmp, d_tmp2);
+		add(d_pending, d_cnt_snap, d_aux, d_seq, d_seqp, d_out, d_out2, d_cnt, d_cnt2, d_scnt, d_ovf, d_spill, d_ctr, d_tmp, d_tmp2);
 		add(d_mem_off, d_seed_off, d_seed_of_mem, d_mems, d_salcnt, d_seeds, d_fqA, d_fqB, d_fqR, d_sst2, d_bq, d_lep, d_ovfrec);
 		add(d_okey, d_oidx, d_okey2, d_oidx2, d_okey64, d_okey64b, d_sctr, d_evc);
 		return b;

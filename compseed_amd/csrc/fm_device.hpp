@@ -151,6 +151,8 @@ __device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (u
 
 struct OutMem { uint64_t x0, x1, x2, info; };   // == cs_intv_t / bwtintv_t
 struct OutSeed { int64_t rbeg; int32_t qbeg, len; }; // == cs_seed_t
+// SA slots a mem with x2 occurrences asks for (comp_seed.cpp:2313-2325)
+__device__ __forceinline__ uint32_t sal_slots(uint64_t x2, uint32_t max_occ) { return x2 < max_occ ? (uint32_t)x2 : max_occ; }
 struct BTask { uint32_t r; uint16_t x, mi_kind, n, ret; uint32_t cls; };  // 16 bytes, stored at the forward task's slot;
                                                                            // cls = size class 0..3, 0xffffffff = no call
 struct OvfRec { OutMem m; uint32_t r, pad; };                              // a mem beyond a read's first `cap`

@@ -161,6 +161,25 @@ static int fetch_words(PinBuf<unsigned long long> &h, size_t at, const T *d_src,
 	return CS_OK;
 }
 
+// two words that do not lie side by side (the running totals of mems and seeds), the same way
+__global__ void fetch_pair_kernel(unsigned long long *dst_host, const unsigned long long *a, const unsigned long long *b)
+{
+	if (threadIdx.x == 0) dst_host[0] = *a;
+	if (threadIdx.x == 1) dst_host[1] = *b;
+	__threadfence_system();
+}
+static int fetch_pair(PinBuf<unsigned long long> &h, size_t at, const uint64_t *d_a, const uint64_t *d_b, hipStream_t s)
+{
+	if (h.dp) {
+		hipLaunchKernelGGL(fetch_pair_kernel, dim3(1), dim3(64), 0, s, h.dp + at, (const unsigned long long *)d_a, (const unsigned long long *)d_b);
+		HIP_TRY(hipGetLastError());
+	} else {
+		HIP_TRY(hipMemcpyAsync(h.p + at, d_a, 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(h.p + at + 1, d_b, 8, hipMemcpyDeviceToHost, s));
+	}
+	return CS_OK;
+}
+
 constexpr int SMEM_BLOCK = 256;
 // LEP entries kept in LDS per lane by the fused kernel: 20 x 16 B x 256 lanes = 80 KiB per workgroup => two workgroups (8 waves) per
 // CU; 10 => 40 KiB => four workgroups (16 waves) per CU, more of the list spilling to global memory (13 and 10 were measured: slower)
@@ -235,7 +254,7 @@ struct SplitRun {
 
 // The kernels' arguments for reads [0, nb) of d_off; the iterations set the queue fields (fq, n_f, fq_next, aux_next) per launch.
 static SplitArgs split_args(const cs_engine *e, PassCtx *c, const cs_params_t *par, const uint64_t *d_off, int64_t nb, uint32_t max_len, uint32_t dis,
-                            uint64_t fq_cap, uint64_t ovf_cap, bool r2text)
+                            uint64_t fq_cap, uint64_t ovf_cap, bool r2text, bool count_slots)
 {
 	unsigned long long *C = c->d_sctr.p;
 	SplitArgs A;
@@ -243,6 +262,7 @@ static SplitArgs split_args(const cs_engine *e, PassCtx *c, const cs_params_t *p
 	A.seqp = c->seqp_cur + (d_off - c->off_base); // record index = (off[r] >> 5) + r with r counted from the batch's first read
 	if (dis & CS_DISABLE_TEXT_MODE) A.ix.text2 = nullptr;
 	A.out = c->d_out.p; A.out_cnt = c->d_cnt.p; A.cap = e->cap;
+	A.out_scnt = count_slots ? c->d_scnt.p : nullptr; A.max_occ = (uint32_t)par->max_occ;
 	A.ovf = c->d_ovfrec.p; A.ovf_cnt = C + SC_OVF_MEMS; A.ovf_cap = ovf_cap;
 	A.min_seed_len = par->min_seed_len;
 	A.split_len = (int)(1.0 * par->min_seed_len * par->split_factor + .499); // comp_seed.cpp:2279 (double arithmetic)
@@ -390,7 +410,7 @@ static int run_split_iterations(const cs_engine *e, PassCtx *c, SplitRun &R, uin
 	return CS_OK;
 }
 
-static int run_smem_split_body(const cs_engine *e, PassCtx *c, const cs_params_t *par, const uint64_t *d_off, int64_t nb, uint32_t max_len, uint64_t *n_ovf_out)
+static int run_smem_split_body(const cs_engine *e, PassCtx *c, const cs_params_t *par, const uint64_t *d_off, int64_t nb, uint32_t max_len, bool count_slots, uint64_t *n_ovf_out)
 {
 	hipStream_t s = c->stream;
 	const uint32_t dis = par->sst_mode != 0 ? par->disable : ~0u; // sst_mode 0: the literal algorithm, every shortcut off
@@ -411,8 +431,9 @@ static int run_smem_split_body(const cs_engine *e, PassCtx *c, const cs_params_t
 	unsigned long long *C = c->d_sctr.p, *H = c->h_sctr.p;
 	HIP_TRY(hipMemsetAsync(C, 0, SC_WORDS * sizeof(unsigned long long), s));
 	HIP_TRY(hipMemsetAsync(c->d_cnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), s));
+	if (count_slots) HIP_TRY(hipMemsetAsync(c->d_scnt.p, 0, ((size_t)nb + 1) * sizeof(uint32_t), s));
 
-	R.A = split_args(e, c, par, d_off, nb, max_len, dis, R.fq_cap, R.ovf_cap, R.r2text);
+	R.A = split_args(e, c, par, d_off, nb, max_len, dis, R.fq_cap, R.ovf_cap, R.r2text, count_slots);
 	const SplitArgs &A = R.A;
 	HIP_TRY(hipEventRecord(c->ev[0], s));
 	hipLaunchKernelGGL(init_tasks_kernel, dim3(grid_for(nb, 256)), dim3(256), 0, s, A, c->d_fqA.p, c->d_fqR.p);
@@ -437,11 +458,11 @@ static int run_smem_split_body(const cs_engine *e, PassCtx *c, const cs_params_t
 	return CS_OK;
 }
 // Runs the three rounds for reads [0, nb) of d_off with the split kernels (smem_*.hpp).  On return d_cnt holds the number of
-// mems per read, d_out the first `cap` of each, d_ovfrec/*n_ovf the rest.  Returns 1 when a task queue overflowed (the caller then
-// falls back to the fused kernel for this sub-batch).
-static int run_smem_split(const cs_engine *e, PassCtx *c, const cs_params_t *par, const uint64_t *d_off, int64_t nb, uint32_t max_len, uint64_t *n_ovf_out)
+// mems per read, d_out the first `cap` of each, d_ovfrec/*n_ovf the rest; with count_slots, d_scnt the SA slots per read.  Returns 1 when
+// a task queue overflowed (the caller then falls back to the fused kernel for this sub-batch).
+static int run_smem_split(const cs_engine *e, PassCtx *c, const cs_params_t *par, const uint64_t *d_off, int64_t nb, uint32_t max_len, bool count_slots, uint64_t *n_ovf_out)
 {
-	const int rc = run_smem_split_body(e, c, par, d_off, nb, max_len, n_ovf_out);
+	const int rc = run_smem_split_body(e, c, par, d_off, nb, max_len, count_slots, n_ovf_out);
 	if (rc != CS_OK) { // every early exit: kernels on the side streams may still be appending to buffers the next call reuses
 		const std::string keep = g_err;
 		(void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->stream2); (void)hipStreamSynchronize(c->stream3); (void)hipStreamSynchronize(c->stream4);
@@ -514,21 +535,33 @@ static int prepare_reads(const cs_engine *e, PassCtx *c, PassReads &in)
 }
 
 // Offsets of the mems of reads [b0, b0 + nb), continuing the running total: scans d_cnt, fetches the new total and grows d_mems (and
-// d_salcnt, where the sort fills it) to it.
-static int place_mems(PassCtx *c, int64_t b0, int64_t nb, uint64_t total_mems, bool with_salcnt, uint64_t *new_total)
+// d_salcnt, where the sort fills it) to it.  total_seeds (the fused sort + SAL path): the same for the seeds in the same round trip --
+// d_scnt scanned into d_seed_off, the running seed total continued, d_seeds grown to it.  keep_salcnt false: d_salcnt only has to be large
+// enough for the sort to write into (after a sub-batch that did not fill it nothing reads it, and it may be shorter than total_mems).
+static int place_mems(PassCtx *c, int64_t b0, int64_t nb, uint64_t total_mems, bool with_salcnt, uint64_t *new_total, uint64_t *total_seeds = nullptr, bool keep_salcnt = true)
 {
 	hipStream_t s = c->stream;
 	CS_TRY(scan_counts(c, c->d_cnt.p, c->d_mem_off.p + b0, (size_t)nb, total_mems));
-	CS_TRY(fetch_words(c->h_ctr, CTR_FETCHED, c->d_mem_off.p + b0 + nb, 1, s));
+	if (total_seeds) {
+		CS_TRY(scan_counts(c, c->d_scnt.p, c->d_seed_off.p + b0, (size_t)nb, *total_seeds));
+		CS_TRY(fetch_pair(c->h_ctr, CTR_FETCHED, c->d_mem_off.p + b0 + nb, c->d_seed_off.p + b0 + nb, s));
+	} else CS_TRY(fetch_words(c->h_ctr, CTR_FETCHED, c->d_mem_off.p + b0 + nb, 1, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	*new_total = c->h_ctr.p[CTR_FETCHED];
 	CS_TRY(c->d_mems.reserve((size_t)*new_total + 16, true, s, (size_t)total_mems));
-	if (with_salcnt) CS_TRY(c->d_salcnt.reserve((size_t)*new_total + 16, true, s, (size_t)total_mems));
+	if (with_salcnt) CS_TRY(c->d_salcnt.reserve((size_t)*new_total + 16, keep_salcnt, s, keep_salcnt ? (size_t)total_mems : 0));
+	if (total_seeds) {
+		const uint64_t new_seeds = c->h_ctr.p[CTR_FETCHED2];
+		CS_TRY(c->d_seeds.reserve((size_t)new_seeds + 16, true, s, (size_t)*total_seeds));
+		*total_seeds = new_seeds;
+	}
 	return CS_OK;
 }
 
 // What follows run_smem_split for reads [b0, b0 + nb): the overflow records sorted by read, the offsets, the two sort kernels.
-static int finish_split_batch(const cs_engine *e, PassCtx *c, const cs_params_t *par, int64_t b0, int64_t nb, uint64_t n_ovf, uint64_t *total_mems)
+// total_seeds (the fused sort + SAL path, the stage has counted d_scnt): the seeds are written here as well -- sort_expand16_kernel for
+// the bulk, sal_expand_heavy_kernel behind sort_compact_wave_kernel for the rest (smem_sort.hpp) -- and run_sal does not run.
+static int finish_split_batch(const cs_engine *e, PassCtx *c, const cs_params_t *par, int64_t b0, int64_t nb, uint64_t n_ovf, uint64_t *total_mems, uint64_t *total_seeds, bool salcnt_ok)
 {
 	hipStream_t s = c->stream;
 	const uint32_t cap = e->cap;
@@ -541,8 +574,28 @@ static int finish_split_batch(const cs_engine *e, PassCtx *c, const cs_params_t 
 		}));
 	}
 	uint64_t new_total = 0;
-	CS_TRY(place_mems(c, b0, nb, *total_mems, true, &new_total));
 	const uint32_t mo = (uint32_t)par->max_occ;
+	if (total_seeds) {
+		CS_TRY(place_mems(c, b0, nb, *total_mems, false, &new_total, total_seeds));
+		unsigned long long *bad = c->d_ctr.p + CTR_SEED_RANGE;
+		HIP_TRY(hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
+		HIP_TRY(hipEventRecord(c->ev[0], s));
+		hipLaunchKernelGGL(sort_expand16_kernel, dim3(grid_for(nb * 16, 256)), dim3(256), 0, s, e->ix, c->d_out.p, c->d_cnt.p, cap, c->d_mem_off.p + b0,
+		                   c->d_seed_off.p + b0, nb, c->d_mems.p, c->d_seeds.p, mo, bad);
+		hipLaunchKernelGGL(sort_compact_wave_kernel, dim3(grid_for(nb, 256)), dim3(256), 0, s, c->d_out.p, c->d_cnt.p, cap, c->d_ovfrec.p,
+		                   c->d_okey2.p, c->d_oidx2.p, n_ovf, c->d_mem_off.p + b0, nb, c->d_mems.p, (uint64_t *)nullptr, mo);
+		hipLaunchKernelGGL(sal_expand_heavy_kernel, dim3(grid_for(nb, 256)), dim3(256), 0, s, e->ix, c->d_cnt.p, cap, c->d_mem_off.p + b0, c->d_seed_off.p + b0,
+		                   nb, (const OutMem *)c->d_mems.p, c->d_seeds.p, mo, bad);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(c->ev[1], s));
+		CS_TRY(fetch_words(c->h_ctr, CTR_SEED_RANGE, bad, 1, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if (c->h_ctr.p[CTR_SEED_RANGE]) return fail(CS_EDEVICE, "the SA slots counted while the mems were emitted do not match the sorted mems");
+		CS_TRY(add_event_ms(c->ev[0], c->ev[1], &c->st.sal_kernel_ms)); // (here: the sort and the expansion together)
+		*total_mems = new_total;
+		return CS_OK;
+	}
+	CS_TRY(place_mems(c, b0, nb, *total_mems, true, &new_total, nullptr, salcnt_ok));
 	// (up to 64 mems and none beyond `cap`: 16 lanes per read; all other reads: a wave each)
 	hipLaunchKernelGGL(sort_compact16_kernel, dim3(grid_for(nb * 16, 256)), dim3(256), 0, s, c->d_out.p, c->d_cnt.p, cap,
 	                   c->d_mem_off.p + b0, nb, c->d_mems.p, c->d_salcnt.p, mo);
@@ -700,25 +753,36 @@ static int seed_device_impl(const cs_engine *e, PassCtx *c, const cs_params_t *p
 	CS_TRY(c->d_out.reserve((size_t)per_launch * cap));
 	CS_TRY(c->d_cnt.reserve((size_t)per_launch + 1));
 	CS_TRY(c->d_ovf.reserve((size_t)per_launch));
-	CS_TRY(c->d_mems.reserve((size_t)n_reads * 10 + 1024)); CS_TRY(c->d_salcnt.reserve((size_t)n_reads * 10 + 1024));
+	// Sort and SAL in one pass over the mems (smem_sort.hpp) where the seeds are wanted as the gather from the full suffix array makes
+	// them; everything else takes the sort and then run_sal.  (sst_mode 0, the literal algorithm, switches every shortcut off.)
+	const uint32_t dis = par->sst_mode != 0 ? par->disable : ~0u;
+	bool fused_sal = e->smem_mode == 1 && par->want_sal && !e->opt.count_sal_merged && has_full_sa(e->ix) && !(dis & CS_DISABLE_FUSED_SAL);
+	// a read's slots are counted in 32 bits: fewer than 2^22 mems per read, max_occ slots each
+	if (fused_sal && (uint64_t)par->max_occ << 22 > (uint64_t)1 << 32) return fail(CS_ERANGE, "max_occ above 1024: a read's seed count may not fit 32 bits (CS_DISABLE_FUSED_SAL lifts the limit)");
+	CS_TRY(c->d_mems.reserve((size_t)n_reads * 10 + 1024));
+	if (fused_sal) { CS_TRY(c->d_scnt.reserve((size_t)per_launch + 1)); CS_TRY(c->d_seed_off.reserve((size_t)n_reads + 2)); }
+	else CS_TRY(c->d_salcnt.reserve((size_t)n_reads * 10 + 1024));
 	bool salcnt_ok = true; // every mem's slot count was written by a sort_compact*_kernel of the split path
 
-	uint64_t total_mems = 0;
+	uint64_t total_mems = 0, total_seeds = 0;
 	for (int64_t b0 = 0; b0 < n_reads; b0 += per_launch) {
 		int64_t nb = std::min<int64_t>(per_launch, n_reads - b0);
 		if (e->smem_mode == 1) {
 			uint64_t n_ovf2 = 0;
-			int rc = run_smem_split(e, c, par, d_off + b0, nb, in.max_len, &n_ovf2);
+			int rc = run_smem_split(e, c, par, d_off + b0, nb, in.max_len, fused_sal, &n_ovf2);
 			if (rc < 0) return rc;
-			if (rc == 0) { CS_TRY(finish_split_batch(e, c, par, b0, nb, n_ovf2, &total_mems)); continue; }
+			if (rc == 0) { CS_TRY(finish_split_batch(e, c, par, b0, nb, n_ovf2, &total_mems, fused_sal ? &total_seeds : nullptr, salcnt_ok)); continue; }
 			// rc == 1: a task queue overflowed -- redo this sub-batch with the fused kernel
 		}
-		salcnt_ok = false;
+		// run_sal then makes all seeds from the sorted mems: those of earlier sub-batches a second time, and sal_kernel_ms holds their
+		// sort-and-expand passes as well as run_sal's time (a queue overflow is rare: DESIGN 4.3)
+		salcnt_ok = false; fused_sal = false;
 		CS_TRY(run_fused_batch(e, c, par, in, b0, nb, &total_mems));
 	}
 	*n_mems_out = total_mems;
 
-	if (par->want_sal) CS_TRY(run_sal(e, c, par, n_reads, total_mems, salcnt_ok, n_seeds_out));
+	if (fused_sal) { *n_seeds_out = total_seeds; c->st.sal_queries += total_seeds; c->st.sal_calls += total_seeds; }
+	else if (par->want_sal) CS_TRY(run_sal(e, c, par, n_reads, total_mems, salcnt_ok, n_seeds_out));
 	HIP_TRY(hipEventRecord(c->ev[3], s));
 	HIP_TRY(hipStreamSynchronize(s));
 	CS_TRY(add_event_ms(c->ev[2], c->ev[3], &c->st.total_ms));

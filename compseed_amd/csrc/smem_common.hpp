@@ -52,6 +52,7 @@ struct SplitArgs {
 	const uint64_t *off;
 	int64_t   n_reads;
 	OutMem   *out; uint32_t *out_cnt; uint32_t cap;
+	uint32_t *out_scnt; uint32_t max_occ;             // SA slots per read, sum of min(x2, max_occ) over its mems, counted as they are emitted (null: not wanted)
 	OvfRec   *ovf; unsigned long long *ovf_cnt; uint64_t ovf_cap;
 	int32_t   min_seed_len, split_len;
 	uint32_t  split_width;
@@ -81,6 +82,7 @@ __device__ __forceinline__ void emit_mem(const SplitArgs &A, uint32_t r, const I
 {
 	OutMem m = {v.x0, v.x1, v.x2, (uint64_t)beg << 32 | end};
 	uint32_t k = atomicAdd(&A.out_cnt[r], 1u);
+	if (A.out_scnt) atomicAdd(&A.out_scnt[r], sal_slots(v.x2, A.max_occ)); // (nothing waits for it: no return value)
 	if (k < A.cap) A.out[(size_t)r * A.cap + k] = m;
 	else {
 		unsigned long long s = atomicAdd(A.ovf_cnt, 1ull);

@@ -264,6 +264,7 @@ __global__ void mark_pending_kernel(const uint64_t *fq, const unsigned long long
 //   * a `complete` read has no other writer of its mem list while this kernel runs, so its slots come from a lane-local counter that
 //     starts at the snapshot count, and out_cnt[r] is stored once at the end; other reads take their slots with atomics as before
 //     (the thin iterations beside the kernel may append to their lists).  One lane emits a read's seeds in order either way.
+//     The SA slots of the seeds (SplitArgs::out_scnt) add up in a register and go out as one add per read, beside the count.
 template <bool FUSED>
 __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArgs A, const uint32_t *cnt_snap, unsigned long long *n_text_seeds, const uint8_t *pending)
 {
@@ -314,7 +315,9 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 			if (complete) { const uint32_t k0 = next_slot; next_slot += n; return k0; }
 			return atomicAdd(&A.out_cnt[r], n);
 		};
+		uint32_t my_slots = 0; // SA slots of the seeds this lane emits for the read: one add where the count is stored
 		auto put = [&](uint32_t kk, const OutMem &m) {
+			my_slots += sal_slots(m.x2, A.max_occ);
 			if (kk < A.cap) A.out[(size_t)r * A.cap + kk] = m;
 			else {
 				unsigned long long sl = atomicAdd(A.ovf_cnt, 1ull);
@@ -458,6 +461,7 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 			x = nx;
 		}
 		if (complete && next_slot != cs) A.out_cnt[r] = next_slot;
+		if (A.out_scnt && my_slots) atomicAdd(&A.out_scnt[r], my_slots);
 	}
 	for (int o = 32; o > 0; o >>= 1) { my_q += __shfl_xor(my_q, o); my_hits += __shfl_xor(my_hits, o); my_text += __shfl_xor(my_text, o); }
 	if ((threadIdx.x & 63u) == 0) { atomicAdd(A.n_queries, my_q); if (my_hits) atomicAdd(A.n_sst_hits, my_hits); if (my_text) atomicAdd(n_text_seeds, my_text); }

@@ -75,6 +75,8 @@ typedef struct {
 #define CS_DISABLE_R3_TEXT      0x10u  /* round-3 seeds inside a mem taken from the text arrays                               */
 #define CS_DISABLE_KMER_FILTER  0x20u  /* k-mer filter in front of the window lanes                                           */
 #define CS_DISABLE_FWD0         0x40u  /* separate lean kernel for the calls at the first base of each read                   */
+#define CS_DISABLE_FUSED_SAL    0x80u  /* sort and SAL in one pass over the mems, a read's SA slots counted while its mems are
+                                        * emitted (max_occ <= 1024); off: the sort, a scan over the mems, then the SAL kernels   */
 
 /* engine construction options: which derived arrays are materialised in HBM and how the working buffers are sized.
  * cs_engine_options_default() fills the defaults (in brackets).  Everything optional is also skipped automatically when
@@ -133,7 +135,9 @@ typedef struct {
 	uint64_t overflow_mems;    /* mems beyond a read's first mem_cap (split kernels), or reads that needed the
 	                              large-capacity second pass (fused kernel)                                        */
 	double   seed_kernel_ms;   /* accumulated HIP-event time of the first-pass SMEM kernel launches         */
-	double   sal_kernel_ms;    /* ... of the SAL kernels                                                    */
+	double   sal_kernel_ms;    /* ... of the SAL kernels; where sort and SAL are one pass over the mems (the default
+	                              with a full suffix array, CS_DISABLE_FUSED_SAL), of that pass: the per-read sort,
+	                              which no field times otherwise, is then inside                            */
 	double   total_ms;         /* ... of whole seed calls, first launch to last                             */
 	uint64_t seed_kernel_launches;
 	double   overflow_kernel_ms;       /* ... of the second-pass SMEM launches over overflowed reads        */
