@@ -438,8 +438,14 @@ static int run_smem_split_body(const cs_engine *e, PassCtx *c, const cs_params_t
 	HIP_TRY(hipEventRecord(c->ev[0], s));
 	hipLaunchKernelGGL(init_tasks_kernel, dim3(grid_for(nb, 256)), dim3(256), 0, s, A, c->d_fqA.p, c->d_fqR.p);
 	// round 3 after rounds 1/2, mostly from the text (r3text_kernel).  Its text paths take "fewer than max_mem_intv occurrences" as
-	// "unique" and compare the 255-capped rep[] bytes with min_seed_len + 1, so -y 1 and -k >= 254 stay on the index (fwd_kernel)
-	R.r3_text = have_arrays && !(dis & CS_DISABLE_R3_TEXT) && A.max_mem_intv >= 2 && A.min_seed_len + 1 <= 254;
+	// "unique" and compare the 255-capped rep[] bytes with min_seed_len + 1, so -y 1 and -k >= 254 stay on the index (fwd_kernel).
+	// They also take every mem of rounds 1/2 for an occurrence of the read in the text, and a read none of whose mems covers a k-mer for
+	// one that does not hold it.  A call whose pivot is a base the text does not contain starts from an EMPTY interval (bwt_set_intv) and
+	// reports it as a mem of size 0 that runs to the read's end (bwt.c:303-320) -- no occurrence, and it hides the matches behind the
+	// pivot.  Only an index that lacks one of the four bases has such mems; its round 3 stays on the index.
+	bool every_base = true;
+	for (int b = 0; b < 4; ++b) every_base = every_base && A.ix.L2[b + 1] > A.ix.L2[b];
+	R.r3_text = have_arrays && !(dis & CS_DISABLE_R3_TEXT) && A.max_mem_intv >= 2 && A.min_seed_len + 1 <= 254 && every_base;
 	R.r3_async = A.max_mem_intv > 0 && !R.r3_text;
 	if (R.r3_async) CS_TRY(launch_r3_index(e, c, R));
 	if (R.r3_text) { CS_TRY(c->d_cnt_snap.reserve((size_t)nb + 1)); CS_TRY(c->d_pending.reserve((size_t)nb + 1)); }
