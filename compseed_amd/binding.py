@@ -804,15 +804,16 @@ class Engine:
     def submit_device(self, d_bases, d_offsets, n_reads, n_bases, params=None):
         """cs_engine_submit_device: queue a device-resident batch (up to two in flight, seeded on alternating pass contexts)"""
         params = params or Params()
-        self._dev_sal = getattr(self, "_dev_sal", [])
         _check(self._L.cs_engine_submit_device(self._h, C.byref(params), int(n_reads), C.c_void_p(d_bases), C.c_void_p(d_offsets), int(n_bases)))
-        self._dev_sal.append(bool(params.want_sal))
 
     def collect_device(self):
-        """cs_engine_collect_device: the oldest submitted device batch, as device pointers (valid until the second submit from now)"""
+        """cs_engine_collect_device: the oldest submitted device batch, as device pointers into the engine's spare result set: valid until
+        the second submit_device from now in every order of submits and collects (a batch whose collect raises does not count against an
+        earlier result), and until the next blocking seed call or submit() once the stream is drained.  seed_off / seeds are null for a
+        batch submitted with want_sal = 0."""
         res = CResult()
         _check(self._L.cs_engine_collect_device(self._h, C.byref(res)))
-        return Result(res, True, self._dev_sal.pop(0))
+        return Result(res, True, bool(res.seed_off))
 
     def result_digest(self):
         """(mem_off, mems, seed_off, seeds) digests of the result of the last seed call, computed on the device"""
@@ -860,7 +861,7 @@ class Engine:
 
     def memory(self):
         """cs_engine_memory: device bytes held, by group: {"occ_bwt", "sampled_sa", "full_sa", "isa", "text", "lcp_rep", "jump_table",
-        "kmer_filter", "pass_ctx": [ctx0, ctx1], "total", "sa_entry_bits": 32 | 40 | 64 | 0, "n_pass_ctx"}; host-only, legal while batches are in flight"""
+        "kmer_filter", "pass_ctx": [ctx0 + the spare result set of collect_device, ctx1], "total", "sa_entry_bits": 32 | 40 | 64 | 0, "n_pass_ctx"}; host-only, legal while batches are in flight"""
         m = Memory()
         _check(self._L.cs_engine_memory(self._h, C.byref(m)))
         d = {n: int(getattr(m, n)) for n, _ in Memory._fields_ if n != "pass_ctx"}

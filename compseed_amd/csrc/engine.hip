@@ -435,6 +435,7 @@ extern "C" int cs_engine_memory(const cs_engine_t *e, cs_memory_t *out)
 	out->total = out->occ_bwt + out->sampled_sa + out->full_sa + out->isa + out->text + out->lcp_rep + out->jump_table + out->kmer_filter;
 	for (int i = 0; i < 2; ++i) {
 		out->pass_ctx[i] = e->ctx_bytes[i].load(std::memory_order_relaxed);
+		if (i == 0) out->pass_ctx[0] += e->held_bytes.load(std::memory_order_relaxed); // the result set of cs_engine_collect_device belongs to no context
 		out->total += out->pass_ctx[i];
 		if (out->pass_ctx[i]) out->n_pass_ctx = i + 1;
 	}

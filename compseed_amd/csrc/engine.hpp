@@ -188,6 +188,14 @@ struct PassCtx {
 	}
 };
 
+// One result of a pass outside the pass contexts: the batch cs_engine_collect_device handed out last lives here (pipelines.hip).
+struct ResultSet {
+	DevBuf<uint64_t> mem_off, seed_off; DevBuf<OutMem> mems; DevBuf<OutSeed> seeds;
+	uint64_t device_bytes() const { return (uint64_t)mem_off.cap * 8 + (uint64_t)seed_off.cap * 8 + (uint64_t)mems.cap * sizeof(OutMem) + (uint64_t)seeds.cap * sizeof(OutSeed); }
+	bool empty() const { return !mem_off.p && !seed_off.p && !mems.p && !seeds.p; }
+	void release() { mem_off.release(); seed_off.release(); mems.release(); seeds.release(); }
+};
+
 constexpr int PIPE_DEPTH = 4; // batches in flight in the host pipeline (cs_engine_submit): one pinned result slot each
 struct cs_engine {
 	int device = 0;
@@ -212,9 +220,11 @@ struct cs_engine {
 	int bloom_tried_k = 0;                         // last min_seed_len the filter was (re)built or found not to fit for
 	std::unique_ptr<PassCtx> ctx[2];               // the second one is made on the first call that can use two passes at a time
 	PassCtx *last_ctx = nullptr;                   // which context holds the last whole-batch result (`last` lives in that one)
+	ResultSet held;                                // the device batch collected last (cs_engine_collect_device swaps it out of its context)
+	bool last_in_held = false;                     // the last result's arrays are `held`'s, not last_ctx's (its counts and streams still are)
 	// cs_engine_memory reads these and nothing a running pass writes: bytes of each pass context as of the end of its last pass (0: no
-	// such context), and of the k-mer filter
-	std::atomic<uint64_t> ctx_bytes[2] = {{0}, {0}}, bloom_bytes{0};
+	// such context), of `held` as of the last cs_engine_collect_device (reported within pass_ctx[0]), and of the k-mer filter
+	std::atomic<uint64_t> ctx_bytes[2] = {{0}, {0}}, held_bytes{0}, bloom_bytes{0};
 	// host variants (seed_host_pipelined): copy streams, three input slots, two pack slots, pinned packed results, expanded results
 	HipStream s_up, s_down; HipEvent hp_ev_pk[2], hp_ev_dn[4], hp_ev_done[PIPE_DEPTH];
 	PinBuf<uint4> hp_stage[3]; // records made by the host (host_pack.cpp), staged for the upload into hp_in[slot]
@@ -230,7 +240,24 @@ struct cs_engine {
 
 inline int n_pass_ctx(const cs_engine *e) { return e->ctx[1] ? 2 : 1; }
 inline void note_ctx_bytes(cs_engine *e, const PassCtx *c) { e->ctx_bytes[c->id].store(c->device_bytes(), std::memory_order_relaxed); }
-inline void invalidate_last(cs_engine *e) { for (auto &c : e->ctx) if (c) c->last.valid = false; e->last_ctx = nullptr; }
+inline void invalidate_last(cs_engine *e) { for (auto &c : e->ctx) if (c) c->last.valid = false; e->last_ctx = nullptr; e->last_in_held = false; }
+// the arrays of the last whole-batch result, whose counts are c->last (c = e->last_ctx): c's own, or the set a device collect handed out
+struct LastArrays { const uint64_t *mem_off, *seed_off; const OutMem *mems; const OutSeed *seeds; };
+inline LastArrays last_arrays(const cs_engine *e, const PassCtx *c)
+{
+	if (e->last_in_held) return {e->held.mem_off.p, e->held.seed_off.p, e->held.mems.p, e->held.seeds.p};
+	return {c->d_mem_off.p, c->d_seed_off.p, c->d_mems.p, c->d_seeds.p};
+}
+// A blocking seed call or a host batch, which need the device stream drained, end the validity of every collected device result: the
+// spare set's memory goes back (an engine that streams device batches gets it again at its next collect, by the swap).  Only a device
+// collect fills `held`, so a non-empty set means no host batch has been submitted since, and no other thread is in the engine.
+inline void drop_held(cs_engine *e)
+{
+	if (e->held.empty()) return;
+	if (e->last_in_held) invalidate_last(e);
+	e->held.release();
+	e->held_bytes.store(0, std::memory_order_relaxed);
+}
 
 // seed_pass.hip
 int add_pass_ctx(cs_engine *e);   // makes the engine's next pass context (the first at engine creation)

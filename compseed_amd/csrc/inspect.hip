@@ -29,11 +29,12 @@ extern "C" int cs_engine_result_digest(cs_engine_t *e, cs_digest_t *out)
 	HIP_TRY(hipMemsetAsync(c->d_ctr.p, 0, 4 * sizeof(unsigned long long), s));
 	const uint64_t n = (uint64_t)c->last.n_reads;
 	const unsigned g = (unsigned)e->n_cu * 8;
-	hipLaunchKernelGGL(digest_kernel, dim3(g), dim3(256), 0, s, (const uint64_t *)c->d_mem_off.p, n + 1, c->d_ctr.p + 0);
-	if (c->last.n_mems) hipLaunchKernelGGL(digest_kernel, dim3(g), dim3(256), 0, s, (const uint64_t *)c->d_mems.p, c->last.n_mems * 4, c->d_ctr.p + 1);
+	const LastArrays r = last_arrays(e, c);
+	hipLaunchKernelGGL(digest_kernel, dim3(g), dim3(256), 0, s, r.mem_off, n + 1, c->d_ctr.p + 0);
+	if (c->last.n_mems) hipLaunchKernelGGL(digest_kernel, dim3(g), dim3(256), 0, s, (const uint64_t *)r.mems, c->last.n_mems * 4, c->d_ctr.p + 1);
 	if (c->last.want_sal) {
-		hipLaunchKernelGGL(digest_kernel, dim3(g), dim3(256), 0, s, (const uint64_t *)c->d_seed_off.p, n + 1, c->d_ctr.p + 2);
-		if (c->last.n_seeds) hipLaunchKernelGGL(digest_kernel, dim3(g), dim3(256), 0, s, (const uint64_t *)c->d_seeds.p, c->last.n_seeds * 2, c->d_ctr.p + 3);
+		hipLaunchKernelGGL(digest_kernel, dim3(g), dim3(256), 0, s, r.seed_off, n + 1, c->d_ctr.p + 2);
+		if (c->last.n_seeds) hipLaunchKernelGGL(digest_kernel, dim3(g), dim3(256), 0, s, (const uint64_t *)r.seeds, c->last.n_seeds * 2, c->d_ctr.p + 3);
 	}
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(c->h_ctr.p, c->d_ctr.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -72,13 +73,14 @@ extern "C" int cs_engine_gather_reads(cs_engine_t *e, int64_t n_sel, const uint6
 	HIP_TRY(hipSetDevice(e->device));
 	hipStream_t s = c->stream;
 	const bool sal = c->last.want_sal != 0;
+	const LastArrays r = last_arrays(e, c);
 	CS_TRY(e->d_sel.reserve((size_t)n_sel + 1)); CS_TRY(e->d_sel_moff.reserve((size_t)n_sel + 2)); CS_TRY(e->d_sel_soff.reserve((size_t)n_sel + 2));
 	CS_TRY(c->d_tmp.reserve(((size_t)n_sel + 2) * 16 + 1024));
 	uint64_t *cm = (uint64_t *)c->d_tmp.p, *cs = cm + n_sel + 1;
 	if (n_sel) HIP_TRY(hipMemcpyAsync(e->d_sel.p, read_ids, (size_t)n_sel * 8, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemsetAsync(c->d_ctr.p + 4, 0, sizeof(unsigned long long), s));
 	hipLaunchKernelGGL(sel_counts_kernel, dim3(grid_for(n_sel + 1, 256)), dim3(256), 0, s, (const uint64_t *)e->d_sel.p, n_sel, (uint64_t)c->last.n_reads,
-	                   (const uint64_t *)c->d_mem_off.p, sal ? (const uint64_t *)c->d_seed_off.p : nullptr, cm, sal ? cs : nullptr, c->d_ctr.p + 4);
+	                   r.mem_off, sal ? r.seed_off : nullptr, cm, sal ? cs : nullptr, c->d_ctr.p + 4);
 	{
 		size_t tb = 0;
 		HIP_TRY(rocprim::exclusive_scan(nullptr, tb, cm, e->d_sel_moff.p, (uint64_t)0, (size_t)n_sel + 1, rocprim::plus<uint64_t>(), s));
@@ -95,8 +97,8 @@ extern "C" int cs_engine_gather_reads(cs_engine_t *e, int64_t n_sel, const uint6
 	const uint64_t nm = e->h_mem_off.p[n_sel], ns = sal ? e->h_seed_off.p[n_sel] : 0;
 	CS_TRY(e->d_sel_mems.reserve((size_t)nm + 1)); CS_TRY(e->h_mems.reserve((size_t)nm + 1));
 	if (sal) { CS_TRY(e->d_sel_seeds.reserve((size_t)ns + 1)); CS_TRY(e->h_seeds.reserve((size_t)ns + 1)); }
-	if (n_sel) hipLaunchKernelGGL(sel_copy_kernel, dim3(grid_for(n_sel * 16, 256)), dim3(256), 0, s, (const uint64_t *)e->d_sel.p, n_sel, (const uint64_t *)c->d_mem_off.p,
-	                              (const uint64_t *)c->d_seed_off.p, (const OutMem *)c->d_mems.p, sal ? (const OutSeed *)c->d_seeds.p : nullptr,
+	if (n_sel) hipLaunchKernelGGL(sel_copy_kernel, dim3(grid_for(n_sel * 16, 256)), dim3(256), 0, s, (const uint64_t *)e->d_sel.p, n_sel, r.mem_off,
+	                              r.seed_off, r.mems, sal ? r.seeds : nullptr,
 	                              (const uint64_t *)e->d_sel_moff.p, (const uint64_t *)e->d_sel_soff.p, e->d_sel_mems.p, e->d_sel_seeds.p);
 	HIP_TRY(hipGetLastError());
 	if (nm) HIP_TRY(hipMemcpyAsync(e->h_mems.p, e->d_sel_mems.p, (size_t)nm * sizeof(OutMem), hipMemcpyDeviceToHost, s));

@@ -336,6 +336,7 @@ static int pipe_submit(cs_engine *e, const cs_params_t *par, int64_t n_reads, co
 	if (par->min_seed_len < 1 || par->max_occ < 1 || par->split_width < 0) return fail(CS_EINVAL, "bad seeding parameters");
 	HIP_TRY(hipSetDevice(e->device));
 	if (dev_pipe_busy(e)) return fail(CS_EINVAL, "cs_engine_submit: device batches are in flight (cs_engine_submit_device), collect them first");
+	drop_held(e);
 	if (!e->hp) e->hp = new HostPipe();
 	HostPipe &hp = *e->hp;
 	if (hp.n_submitted.load() - hp.n_collected.load() >= (uint64_t)PIPE_DEPTH) return fail(CS_EINVAL, "cs_engine_submit: four batches are in flight already, collect one first");
@@ -484,7 +485,7 @@ static int pipe_collect(cs_engine *e, cs_packed_result_t *out)
 
 // ---- device batches, two in flight: cs_engine_submit_device / cs_engine_collect_device.  Batch n runs on pass context n & 1, on a thread
 // of its own, so the thin tail of one pass overlaps the dense start of the next; results come back in submission order as device
-// pointers into that context's buffers.
+// pointers into the engine's spare result set (cs_engine::held), which a collect exchanges with its context's result buffers.
 struct DevPipe {
 	std::thread th[2]; std::mutex mu; std::condition_variable cv; bool quit = false;
 	int n_ctx = 1;
@@ -558,19 +559,35 @@ extern "C" int cs_engine_collect_device(cs_engine_t *e, cs_result_t *out)
 		std::unique_lock<std::mutex> lk(dp.mu);
 		dp.cv.wait(lk, [&] { return dp.state[ci] == 3; });
 		rc = dp.rc[ci]; err = dp.err[ci]; nm = dp.nm[ci]; ns = dp.ns[ci]; sal = dp.job[ci].par.want_sal != 0; n = dp.job[ci].n;
+		if (rc == CS_OK) {
+			// The result leaves its context: the context's four result buffers are exchanged with the engine's one spare set (e->held), and
+			// the caller gets the spare set's pointers.  No pass runs on this context (its state is 3, the submit that could start one
+			// waits for n_col below, under this lock), so nothing reads or writes either set meanwhile.  One spare set is enough for "valid
+			// until the SECOND submit after its collect": r_n stays in `held` until collect(n+1) -- a failed batch hands nothing out and
+			// swaps nothing, so then until the next collect that succeeds -- which moves r_n's buffers into context (n+1) % n_ctx.
+			// That context has just been collected, so the next pass on it is batch n+1+n_ctx.  With two contexts at most n+1 had been
+			// submitted when n was collected (two in flight), so n+3 is at the earliest the second submit after collect(n); with one
+			// context, submit(n+1) came after collect(n) and n+2 is the second.  Drained orders (col n, col n+1, sub, sub) are the same
+			// count: the first of the two submits runs on the other context, or (one context) precedes collect(n+1).  A batch of
+			// want_sal = 0 leaves the seed buffers as it found them; they travel with the set all the same, only their capacity matters.
+			invalidate_last(e);
+			std::swap(c->d_mem_off, e->held.mem_off); std::swap(c->d_mems, e->held.mems);
+			std::swap(c->d_seed_off, e->held.seed_off); std::swap(c->d_seeds, e->held.seeds);
+			note_ctx_bytes(e, c);
+			e->held_bytes.store(e->held.device_bytes(), std::memory_order_relaxed);
+			// cs_engine_result_digest / cs_engine_gather_reads follow the arrays (a submit on another thread invalidates under the same lock)
+			c->last.n_reads = n; c->last.n_mems = nm; c->last.n_seeds = ns; c->last.want_sal = sal;
+			c->last.valid = dp.n_sub.load() == dp.n_col.load() + 1; // drained by this collect
+			e->last_ctx = c; e->last_in_held = true;
+		}
 		dp.state[ci] = 0;
 		dp.n_col++;
 	}
 	memset(out, 0, sizeof *out);
 	if (rc != CS_OK) return fail(rc, err);
-	{ // (a submit on another thread invalidates it under the same lock)
-		std::lock_guard<std::mutex> lk(dp.mu);
-		invalidate_last(e);
-		c->last.valid = !dev_pipe_busy(e); c->last.n_reads = n; c->last.n_mems = nm; c->last.n_seeds = ns; c->last.want_sal = sal; e->last_ctx = c;
-	}
 	out->n_reads = n; out->n_mems = nm; out->n_seeds = ns;
-	out->mem_off = c->d_mem_off.p; out->mems = (const cs_intv_t *)c->d_mems.p;
-	out->seed_off = sal ? c->d_seed_off.p : nullptr; out->seeds = sal ? (const cs_seed_t *)c->d_seeds.p : nullptr;
+	out->mem_off = e->held.mem_off.p; out->mems = (const cs_intv_t *)e->held.mems.p;
+	out->seed_off = sal ? e->held.seed_off.p : nullptr; out->seeds = sal ? (const cs_seed_t *)e->held.seeds.p : nullptr;
 	return CS_OK;
 }
 

@@ -847,6 +847,7 @@ extern "C" int cs_engine_seed_batch_device(cs_engine_t *e, const cs_params_t *pa
 	HIP_TRY(hipSetDevice(e->device));
 	uint64_t nm = 0, ns = 0;
 	invalidate_last(e);
+	drop_held(e);
 	PassCtx *c = e->ctx[0].get();
 	CS_TRY(run_pass(e, c, par, n_reads, d_bases, d_offsets, n_bases, &nm, &ns, nullptr));
 	c->last.valid = true; c->last.n_reads = n_reads; c->last.n_mems = nm; c->last.n_seeds = ns; c->last.want_sal = par->want_sal; e->last_ctx = c;

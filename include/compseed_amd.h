@@ -209,7 +209,15 @@ int  cs_engine_seed_batch_device(cs_engine_t *e, const cs_params_t *par, int64_t
  * sort, SAL, host round trips) runs beside the dense start of the next; this is how a worker that keeps its reads in HBM drives the engine
  * (the reference's kt_for over chunks of a batch, comp_seed.cpp:2541-2548, is the same overlap on CPU threads).  Inputs as for
  * cs_engine_seed_batch_device, and they must stay untouched until their batch has been collected.  Results come back in submission
- * order; the device pointers of a collected batch stay valid until the SECOND submit after its collect (the next batch on its context).
+ * order; the device pointers of a collected batch stay valid until the SECOND submit after its collect, whatever the order of submits
+ * and collects and for both values of passes_in_flight: a consumer may work on batch n while batch n+1 -- and, with two in flight,
+ * n+2 -- is being seeded.  The engine keeps ONE result set more than it has pass contexts for this: a collect exchanges the four result
+ * arrays of the batch's context with that spare set and hands out the spare set's pointers, so a collected batch is in no context until
+ * the next collect (cost: the result arrays of one more batch, 32 bytes per mem + 16 per seed + 16 per read at the size of the largest
+ * batch; cs_engine_memory counts it within pass_ctx[0]).  A batch whose collect returns an error hands nothing out and does not shorten
+ * the life of an earlier result.  A blocking seed call or a cs_engine_submit once the stream is drained ends the validity of every
+ * collected device result (the "until the next seed call" rule of cs_engine_seed_batch_device) and frees the spare set, which the
+ * next collect of a device stream fills again.
  * While device batches are in flight the other entry points that use the device return CS_EINVAL.  Threads: as for cs_engine_submit /
  * cs_engine_collect_packed -- one submitting thread, one collecting thread. */
 int  cs_engine_submit_device(cs_engine_t *e, const cs_params_t *par, int64_t n_reads,
@@ -512,7 +520,9 @@ void cs_engine_reset_stats(cs_engine_t *e);
  *      differences of free memory.  The index-side arrays are fixed once the engine exists (an array that did not fit, or was switched
  *      off, reports 0); kmer_filter changes when a call with another min_seed_len rebuilds the filter; pass_ctx[i] is the working set of
  *      pass context i (streams' buffers: reads, queues, LEP arena, raw mems, results) as of the end of its last pass -- it grows with the
- *      largest batch seen -- and 0 for a context that does not exist (the second one is made on first use).  total is the sum of the
+ *      largest batch seen -- and 0 for a context that does not exist (the second one is made on first use); pass_ctx[0] also holds the
+ *      spare result set of cs_engine_collect_device (as of the last collect: a collect only moves arrays between it and a context, so
+ *      the sum does not change).  total is the sum of the
  *      groups.  Not counted: the staging buffers of the host variants and of cs_engine_gather_reads, which are a few bytes per read of a
  *      sub-batch.  sa_entry_bits: the entry width of the full suffix array / inverse suffix array, 32, 40 or 64; 0 without a full suffix
  *      array.  Host-only: no device call is made, and it is legal while submitted batches are in flight. */
