@@ -935,6 +935,20 @@ class Extender:
         _check(self.last_rc)
         return out
 
+    def upload(self, qbuf, tbuf):
+        """cs_extender_upload: the two sequence buffers stay in the extender for extend_resident (extend leaves its own there as well)"""
+        qbuf = np.ascontiguousarray(qbuf, dtype=np.uint8); tbuf = np.ascontiguousarray(tbuf, dtype=np.uint8)
+        _check(self.L.cs_extender_upload(self.h, qbuf.ctypes.data if qbuf.size else None, qbuf.size, tbuf.ctypes.data if tbuf.size else None, tbuf.size))
+
+    def extend_resident(self, pairs, w=100):
+        """cs_extend_batch_resident: extend() against the sequences the extender holds"""
+        pairs = np.ascontiguousarray(pairs, dtype=EXT_PAIR_DT)
+        out = np.zeros(pairs.size, dtype=EXT_RES_DT)
+        self.last_rc = self.L.cs_extend_batch_resident(self.h, pairs.size, pairs.ctypes.data if pairs.size else None, int(w), out.ctypes.data if pairs.size else None)
+        self.last_out = out
+        _check(self.last_rc)
+        return out
+
     def extend_device(self, d_pairs, n, d_q, q_bytes, d_t, t_bytes, d_out, w=100):
         _check(self.L.cs_extend_batch_device(self.h, int(n), int(d_pairs), int(d_q), int(q_bytes), int(d_t), int(t_bytes), int(w), int(d_out)))
 

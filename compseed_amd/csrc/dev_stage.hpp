@@ -1,12 +1,14 @@
-// dev_stage.hpp -- the host half that the device stage units share (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip; extend.hip and
-// the engine's units take the error macro): the HIP error macro, a grow-only device buffer, the state every stage keeps (device, stream,
-// timing events, pinned counter words, buffers) with its creation, its release and the launch / upload / scan helpers, and the download
-// of a chain result.  Header-only; a stage keeps its own `enum { B_... }` of buffers and its kernels' Args, and derives its state from
-// cs_dev_stage<B_COUNT>.
+// dev_stage.hpp -- the host half that the device units share: the HIP error macro; the owning types (DevBuf, PinBuf, HipStream, HipEvent)
+// that the engine's units, the index builder (index_build.hip) and inspect.hip keep device memory, pinned memory, streams and events in;
+// and the stage layer of the units outside the engine (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip, extend.hip): a grow-only device
+// buffer that frees before it allocates, the state every stage keeps (device, stream, timing events, pinned counter words, buffers) with
+// its creation, its release and the launch / upload / scan helpers, and the download of a chain result.  Header-only; a stage keeps its
+// own `enum { B_... }` of buffers and its kernels' Args, and derives its state from cs_dev_stage<B_COUNT>.
 #pragma once
 #include "cs_internal.hpp"
 
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -22,6 +24,71 @@
 		}                                                                                           \
 	} while (0)
 
+// ---- owning buffers and handles: what the engine's units, the extender and the index builder keep their device state in
+// Grow-only buffers that free their memory when destroyed; move-only.
+template <typename T> struct DevBuf {
+	T *p = nullptr; size_t cap = 0;
+	DevBuf() = default;
+	DevBuf(const DevBuf &) = delete;
+	DevBuf &operator=(const DevBuf &) = delete;
+	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+	DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
+	~DevBuf() { release(); }
+	int reserve(size_t n, bool keep = false, hipStream_t s = nullptr, size_t keep_n = 0)
+	{
+		if (n <= cap) return CS_OK;
+		size_t want = std::max(n, cap + cap / 2);
+		T *q = nullptr;
+		HIP_TRY(hipMalloc((void **)&q, want * sizeof(T)));
+		if (keep && p && keep_n) {
+			hipError_t e = hipMemcpyAsync(q, p, keep_n * sizeof(T), hipMemcpyDeviceToDevice, s);
+			if (e == hipSuccess) e = hipStreamSynchronize(s);
+			if (e != hipSuccess) { (void)hipFree(q); return cs_fail_(CS_EDEVICE, hipGetErrorString(e)); }
+		}
+		if (p) (void)hipFree(p);
+		p = q; cap = want;
+		return CS_OK;
+	}
+	void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+};
+template <typename T> struct PinBuf {
+	T *p = nullptr, *dp = nullptr; size_t cap = 0; // dp: the same memory as the device addresses it (kernels may store into it)
+	PinBuf() = default;
+	PinBuf(const PinBuf &) = delete;
+	PinBuf &operator=(const PinBuf &) = delete;
+	PinBuf(PinBuf &&o) noexcept : p(o.p), dp(o.dp), cap(o.cap) { o.p = o.dp = nullptr; o.cap = 0; }
+	PinBuf &operator=(PinBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(dp, o.dp); std::swap(cap, o.cap); } return *this; }
+	~PinBuf() { release(); }
+	int reserve(size_t n, bool keep = false, size_t keep_n = 0)
+	{
+		if (n <= cap) return CS_OK;
+		size_t want = std::max(n, cap + cap / 2);
+		T *q = nullptr;
+		HIP_TRY(hipHostMalloc((void **)&q, want * sizeof(T), hipHostMallocDefault));
+		if (keep && p && keep_n) memcpy(q, p, keep_n * sizeof(T));
+		if (p) (void)hipHostFree(p);
+		p = q; cap = want; dp = nullptr;
+		void *d = nullptr;
+		if (hipHostGetDevicePointer(&d, p, 0) == hipSuccess) dp = (T *)d; else (void)hipGetLastError();
+		return CS_OK;
+	}
+	void release() { if (p) (void)hipHostFree(p); p = nullptr; dp = nullptr; cap = 0; }
+};
+// a stream or an event, destroyed with its holder; converts to the raw handle, so it is passed to the HIP calls as it is
+template <typename H, hipError_t (*Destroy)(H)> struct HipHandle {
+	H h = nullptr;
+	HipHandle() = default;
+	HipHandle(const HipHandle &) = delete;
+	HipHandle &operator=(const HipHandle &) = delete;
+	HipHandle(HipHandle &&o) noexcept : h(o.h) { o.h = nullptr; }
+	HipHandle &operator=(HipHandle &&o) noexcept { std::swap(h, o.h); return *this; }
+	~HipHandle() { if (h) (void)Destroy(h); }
+	operator H() const { return h; }
+};
+using HipStream = HipHandle<hipStream_t, hipStreamDestroy>;
+using HipEvent = HipHandle<hipEvent_t, hipEventDestroy>;
+
+// ---- the stage layer
 // grow-only device memory; a failed growth leaves the buffer empty (p == nullptr, cap == 0), never dangling
 struct cs_dev_buf { void *p = nullptr; size_t cap = 0; };
 inline int cs_dev_ensure(cs_dev_buf &b, size_t bytes)

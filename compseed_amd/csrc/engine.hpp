@@ -4,7 +4,8 @@
 //                  kernels of the default SMEM path, smem_common.hpp and smem_{reads,fwd,bwd,text,sort}.hpp
 //   pipelines.hip  the host pipeline (cs_engine_submit / collect, blocking host variants) and the device pipeline
 //   inspect.hip    digest and gather of the last result, index validation, primitives, the random-line probe
-//   dev_stage.hpp  HIP_TRY, and the host half shared by the stage units outside the engine (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip)
+//   dev_stage.hpp  HIP_TRY, the owning types the members below are made of (DevBuf, PinBuf, HipStream, HipEvent), and the stage layer of the
+//                  units outside the engine (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip, extend.hip)
 // Kernels are defined in the unit that launches them; the headers included by more than one unit hold types and __device__ functions.
 #pragma once
 #include "cs_internal.hpp"
@@ -30,33 +31,7 @@ inline int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)std::max<int64_t>(1, (n + block - 1) / block); }
 
-// ------------------------------------------------------------------------------------------------ owning buffers and handles
-// Grow-only buffers that free their memory when destroyed; move-only.
-template <typename T> struct DevBuf {
-	T *p = nullptr; size_t cap = 0;
-	DevBuf() = default;
-	DevBuf(const DevBuf &) = delete;
-	DevBuf &operator=(const DevBuf &) = delete;
-	DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-	DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
-	~DevBuf() { release(); }
-	int reserve(size_t n, bool keep = false, hipStream_t s = nullptr, size_t keep_n = 0)
-	{
-		if (n <= cap) return CS_OK;
-		size_t want = std::max(n, cap + cap / 2);
-		T *q = nullptr;
-		HIP_TRY(hipMalloc((void **)&q, want * sizeof(T)));
-		if (keep && p && keep_n) {
-			hipError_t e = hipMemcpyAsync(q, p, keep_n * sizeof(T), hipMemcpyDeviceToDevice, s);
-			if (e == hipSuccess) e = hipStreamSynchronize(s);
-			if (e != hipSuccess) { (void)hipFree(q); return fail(CS_EDEVICE, hipGetErrorString(e)); }
-		}
-		if (p) (void)hipFree(p);
-		p = q; cap = want;
-		return CS_OK;
-	}
-	void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
+// ------------------------------------------------------------------------------------------------ host buffers
 // grow-only plain host memory (the expanded results of cs_engine_seed_batch; `keep_n` elements survive a reallocation)
 template <typename T> struct HostBuf {
 	T *p = nullptr; size_t cap = 0;
@@ -79,42 +54,6 @@ template <typename T> struct HostBuf {
 	}
 	void release() { free(p); p = nullptr; cap = 0; }
 };
-template <typename T> struct PinBuf {
-	T *p = nullptr, *dp = nullptr; size_t cap = 0; // dp: the same memory as the device addresses it (kernels may store into it)
-	PinBuf() = default;
-	PinBuf(const PinBuf &) = delete;
-	PinBuf &operator=(const PinBuf &) = delete;
-	PinBuf(PinBuf &&o) noexcept : p(o.p), dp(o.dp), cap(o.cap) { o.p = o.dp = nullptr; o.cap = 0; }
-	PinBuf &operator=(PinBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(dp, o.dp); std::swap(cap, o.cap); } return *this; }
-	~PinBuf() { release(); }
-	int reserve(size_t n, bool keep = false, size_t keep_n = 0)
-	{
-		if (n <= cap) return CS_OK;
-		size_t want = std::max(n, cap + cap / 2);
-		T *q = nullptr;
-		HIP_TRY(hipHostMalloc((void **)&q, want * sizeof(T), hipHostMallocDefault));
-		if (keep && p && keep_n) memcpy(q, p, keep_n * sizeof(T));
-		if (p) (void)hipHostFree(p);
-		p = q; cap = want; dp = nullptr;
-		void *d = nullptr;
-		if (hipHostGetDevicePointer(&d, p, 0) == hipSuccess) dp = (T *)d; else (void)hipGetLastError();
-		return CS_OK;
-	}
-	void release() { if (p) (void)hipHostFree(p); p = nullptr; dp = nullptr; cap = 0; }
-};
-// a stream or an event, destroyed with its holder; converts to the raw handle, so it is passed to the HIP calls as it is
-template <typename H, hipError_t (*Destroy)(H)> struct HipHandle {
-	H h = nullptr;
-	HipHandle() = default;
-	HipHandle(const HipHandle &) = delete;
-	HipHandle &operator=(const HipHandle &) = delete;
-	HipHandle(HipHandle &&o) noexcept : h(o.h) { o.h = nullptr; }
-	HipHandle &operator=(HipHandle &&o) noexcept { std::swap(h, o.h); return *this; }
-	~HipHandle() { if (h) (void)Destroy(h); }
-	operator H() const { return h; }
-};
-using HipStream = HipHandle<hipStream_t, hipStreamDestroy>;
-using HipEvent = HipHandle<hipEvent_t, hipEventDestroy>;
 
 // ------------------------------------------------------------------------------------------------ engine
 // The words of PassCtx::d_sctr / h_sctr, the counters of the split SMEM stage.  seed_pass.hip hands the kernels pointers to them

@@ -507,33 +507,25 @@ __global__ void max_qlen_kernel(const cs_ext_pair_t *pairs, int64_t n, unsigned 
 
 } // namespace cse
 
-struct cs_extender {
-	int device = 0, n_cu = 256;
+namespace {
+enum { B_PAIRS, B_Q, B_T, B_OUT, B_SCRATCH,              // the host forms' pairs, sequences and results; the band state of queries too long for LDS
+       B_KEYS, B_KEYS2, B_IDX, B_IDX2, B_SORT,            // lane kernel: sort keys and pair indices, both with their sorted copies, rocPRIM's scratch
+       B_CTR, B_CLS,                                      // 8 words: [0] skipped pairs [1] cells [2] rows [3] longest query, [4..7] hold the matrix; 16 words: pairs per query-length class of the lane kernel
+       B_COUNT };
+} // namespace
+
+// the stage's ev[0] / ev[1] stand around a call's kernels (kernel_ms); its h_ctr receives the first four words of B_CTR
+struct cs_extender : cs_dev_stage<B_COUNT> {
 	cse::ExtParams P{};
 	bool packed16 = true;                 // the two-columns-per-lane int16 kernel may be used (parameters fit; not switched off)
 	int min_qlen16 = 64;
 	bool lanes = true;                    // short queries go through extend_lanes_kernel (one pair per lane)
 	bool qin = false;                     // ... with the query base inside the cell (CS_EXT_LANES_QIN: experiment)
-	void *d_keys = nullptr, *d_keys2 = nullptr, *d_idx = nullptr, *d_idx2 = nullptr, *d_sort = nullptr; size_t c_keys = 0, c_keys2 = 0, c_idx = 0, c_idx2 = 0, c_sort = 0;
-	unsigned long long *d_cls = nullptr, *h_cls = nullptr; // pairs per query-length class of the lane kernel
-	hipStream_t stream = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	hipStream_t side[2] = {nullptr, nullptr}; hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr}; // the lane kernel's class launches run side by side
-	void *d_pairs = nullptr, *d_q = nullptr, *d_t = nullptr, *d_out = nullptr, *d_scratch = nullptr; size_t c_pairs = 0, c_q = 0, c_t = 0, c_out = 0, c_scratch = 0;
-	uint64_t res_q = 0, res_t = 0;                         // bytes of the sequence buffers uploaded by cs_extender_upload
-	unsigned long long *d_ctr = nullptr, *h_ctr = nullptr; // device words: [0] skipped pairs [1] cells [2] rows [3] longest query; [4..7] hold the matrix
+	HipStream side[2]; HipEvent ev_fork, ev_join[2]; // the lane kernel's class launches run side by side
+	PinBuf<unsigned long long> h_cls;     // B_CLS as the host reads it
+	uint64_t res_q = 0, res_t = 0;        // bytes of the sequences resident in B_Q / B_T (the last host-form call's or cs_extender_upload's)
 	cs_ext_stats_t st{};
 };
-
-static int grow(void **p, size_t *cap, size_t need)
-{
-	if (need <= *cap) return CS_OK;
-	if (*p) (void)hipFree(*p);
-	*p = nullptr; *cap = 0;
-	const size_t want = need + need / 4 + 256;
-	HIP_TRY(hipMalloc(p, want));
-	*cap = want;
-	return CS_OK;
-}
 
 extern "C" void cs_ext_params_default(cs_ext_params_t *p)
 {
@@ -541,6 +533,19 @@ extern "C" void cs_ext_params_default(cs_ext_params_t *p)
 	// mem_opt_init (mapping/comp_seed.cpp:26-58): a = 1, b = 4, o_del = o_ins = 6, e_del = e_ins = 1, zdrop = 100, pen_clip5 = pen_clip3 = 5; bwa_fill_scmat (bwalib/bwa.c:17-29)
 	for (int i = 0, k = 0; i < 5; ++i) for (int j = 0; j < 5; ++j) p->mat[k++] = (int8_t)(i == 4 || j == 4 ? -1 : i == j ? 1 : -4);
 	p->o_del = p->o_ins = 6; p->e_del = p->e_ins = 1; p->zdrop = 100; p->end_bonus = 5; p->flags = 0;
+}
+
+// what cs_extender_create makes on the device; whatever this returns, cs_extender_destroy copes with it
+static int extender_init(cs_extender *x, int device, const int8_t *mat)
+{
+	if (int rc = x->init(device, true)) return rc;
+	for (int k = 0; k < 2; ++k) { HIP_TRY(hipStreamCreateWithFlags(&x->side[k].h, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&x->ev_join[k].h, hipEventDisableTiming)); }
+	HIP_TRY(hipEventCreateWithFlags(&x->ev_fork.h, hipEventDisableTiming));
+	if (int rc = x->ensure(B_CTR, 8 * sizeof(unsigned long long))) return rc;
+	if (int rc = x->ensure(B_CLS, 16 * sizeof(unsigned long long))) return rc;
+	if (int rc = x->h_cls.reserve(16)) return rc;
+	HIP_TRY(hipMemcpy(x->at<unsigned long long>(B_CTR) + 4, mat, 25, hipMemcpyHostToDevice));
+	return CS_OK;
 }
 
 extern "C" int cs_extender_create(int device, const cs_ext_params_t *par, cs_extender_t **out)
@@ -554,11 +559,7 @@ extern "C" int cs_extender_create(int device, const cs_ext_params_t *par, cs_ext
 	HIP_TRY(hipGetDeviceCount(&ndev));
 	if (ndev <= 0) return cs_fail_(CS_EDEVICE, "no HIP device: the extension kernel has no CPU path");
 	if (device < 0 || device >= ndev) return cs_fail_(CS_EINVAL, "device ordinal out of range");
-	HIP_TRY(hipSetDevice(device));
 	cs_extender *x = new cs_extender();
-	x->device = device;
-	hipDeviceProp_t prop;
-	if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) x->n_cu = prop.multiProcessorCount;
 	x->P.match = par->mat[0]; x->P.mismatch = par->mat[1];
 	x->P.o_del = par->o_del; x->P.e_del = par->e_del; x->P.o_ins = par->o_ins; x->P.e_ins = par->e_ins; x->P.zdrop = par->zdrop; x->P.end_bonus = par->end_bonus;
 	x->P.vec_zdrop = (par->flags & CS_EXT_VECTOR_ZDROP) ? 1 : 0;
@@ -569,19 +570,9 @@ extern "C" int cs_extender_create(int device, const cs_ext_params_t *par, cs_ext
 	x->min_qlen16 = (par->flags & CS_EXT_PACKED16_ALL) ? 0 : 64;
 	x->packed16 = (par->flags & (CS_EXT_PACKED16 | CS_EXT_PACKED16_ALL)) && par->e_ins <= 200 && par->e_del <= 200 && par->o_ins + par->e_ins < 16000 && par->o_del + par->e_del < 16000 &&
 	              par->mat[0] >= 0 && par->mat[0] <= 100 && par->mat[1] <= 0 && par->mat[1] >= -100;
-	hipError_t e = hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking);
-	if (e == hipSuccess) e = hipEventCreate(&x->ev0);
-	if (e == hipSuccess) e = hipEventCreate(&x->ev1);
-	for (int k = 0; k < 2 && e == hipSuccess; ++k) { e = hipStreamCreateWithFlags(&x->side[k], hipStreamNonBlocking); if (e == hipSuccess) e = hipEventCreateWithFlags(&x->ev_join[k], hipEventDisableTiming); }
-	if (e == hipSuccess) e = hipEventCreateWithFlags(&x->ev_fork, hipEventDisableTiming);
-	if (e == hipSuccess) e = hipMalloc((void **)&x->d_ctr, 8 * sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipHostMalloc((void **)&x->h_ctr, 8 * sizeof(unsigned long long), hipHostMallocDefault);
-	if (e == hipSuccess) e = hipMemcpy(x->d_ctr + 4, par->mat, 25, hipMemcpyHostToDevice);
-	if (e == hipSuccess) e = hipMalloc((void **)&x->d_cls, 16 * sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipHostMalloc((void **)&x->h_cls, 16 * sizeof(unsigned long long), hipHostMallocDefault);
 	x->lanes = !x->packed16 && !(par->flags & CS_EXT_NO_LANES);
 	x->qin = (par->flags & CS_EXT_LANES_QIN) != 0;
-	if (e != hipSuccess) { (void)hipGetLastError(); cs_extender_destroy(x); return cs_fail_(CS_EDEVICE, std::string("cs_extender_create: ") + hipGetErrorString(e)); }
+	if (int rc = extender_init(x, device, par->mat)) { cs_extender_destroy(x); return rc; }
 	*out = x;
 	return CS_OK;
 }
@@ -590,80 +581,58 @@ extern "C" void cs_extender_destroy(cs_extender_t *x)
 {
 	if (!x) return;
 	(void)hipSetDevice(x->device);
-	if (x->stream) (void)hipStreamSynchronize(x->stream);
-	for (void *p : {x->d_pairs, x->d_q, x->d_t, x->d_out, x->d_scratch, (void *)x->d_ctr, x->d_keys, x->d_keys2, x->d_idx, x->d_idx2, x->d_sort, (void *)x->d_cls}) if (p) (void)hipFree(p);
-	if (x->h_ctr) (void)hipHostFree(x->h_ctr);
-	if (x->h_cls) (void)hipHostFree(x->h_cls);
-	if (x->ev0) (void)hipEventDestroy(x->ev0);
-	if (x->ev1) (void)hipEventDestroy(x->ev1);
-	for (int k = 0; k < 2; ++k) { if (x->ev_join[k]) (void)hipEventDestroy(x->ev_join[k]); if (x->side[k]) { (void)hipStreamSynchronize(x->side[k]); (void)hipStreamDestroy(x->side[k]); } }
-	if (x->ev_fork) (void)hipEventDestroy(x->ev_fork);
-	if (x->stream) (void)hipStreamDestroy(x->stream);
+	for (const HipStream &t : x->side) if (t) (void)hipStreamSynchronize(t);
+	x->release();
 	delete x;
 }
 
-// the launch: pairs, sequences and results are device memory here
-static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs, const uint8_t *d_q, uint64_t q_bytes, const uint8_t *d_t, uint64_t t_bytes,
-                         int32_t w, cs_ext_result_t *d_out)
+// The kernels of a call, from the first timing event to the wait for the main stream.  The lane kernel's class launches fork onto the two
+// side streams and join the main stream again; a failure in here may return with kernels running on any of the three (extend_device waits).
+static int extend_launches(cs_extender *x, cse::ExtArgs &A, size_t sort_bytes)
 {
-	hipStream_t s = x->stream;
-	HIP_TRY(hipMemsetAsync(x->d_ctr, 0, 4 * sizeof(unsigned long long), s));
-	hipLaunchKernelGGL(cse::max_qlen_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)x->n_cu * 8)), dim3(256), 0, s, d_pairs, n, x->d_ctr + 3);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(x->h_ctr, x->d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipStreamSynchronize(s));
-	const int64_t max_q = (int64_t)x->h_ctr[3];
-	if (max_q > 65535) return cs_fail_(CS_ERANGE, "cs_extend_batch: a query is longer than 65535 bases (MAX_READ_LEN, mapping/comp_seed.h:39)");
-	if ((int64_t)x->P.best * max_q > (1 << 29)) return cs_fail_(CS_ERANGE, "cs_extend_batch: scores would not fit the kernel's 30-bit range");
-	cse::ExtArgs A;
-	A.pairs = d_pairs; A.n = n; A.qbuf = d_q; A.tbuf = d_t; A.q_bytes = q_bytes; A.t_bytes = t_bytes; A.out = d_out; A.w = w; A.max_qlen = (int32_t)std::max<int64_t>(max_q, 1);
-	A.P = x->P; A.mat = (const int8_t *)(x->d_ctr + 4); A.scratch = nullptr; A.err = x->d_ctr; A.stat = x->d_ctr + 1;
+	hipStream_t s = x->s;
+	const int64_t n = A.n;
+	unsigned long long *d_ctr = x->at<unsigned long long>(B_CTR), *d_cls = x->at<unsigned long long>(B_CLS), *h_cls = x->h_cls.p;
 	const size_t per_wave = ((size_t)2 * (A.max_qlen + 2) + ((A.max_qlen + 3) >> 2)) * 4; // bytes of LDS per wave
-	HIP_TRY(hipEventRecord(x->ev0, s));
+	HIP_TRY(hipEventRecord(x->ev[0], s));
 	A.packed16 = 0; A.min_qlen16 = x->min_qlen16;
 	int64_t n_lanes = 0;
 	if (x->lanes && n < (1ll << 32)) { // short queries: one pair per lane, pairs sorted by (query-length class, target length, query length)
-		if (int rc = grow(&x->d_keys, &x->c_keys, (size_t)n * 4)) return rc;
-		if (int rc = grow(&x->d_keys2, &x->c_keys2, (size_t)n * 4)) return rc;
-		if (int rc = grow(&x->d_idx, &x->c_idx, (size_t)n * 4)) return rc;
-		if (int rc = grow(&x->d_idx2, &x->c_idx2, (size_t)n * 4)) return rc;
-		HIP_TRY(hipMemsetAsync(x->d_cls, 0, 16 * sizeof(unsigned long long), s));
-		hipLaunchKernelGGL(cse::lanes_keys_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)x->n_cu * 8)), dim3(256), 0, s, A, (uint32_t *)x->d_keys, (uint32_t *)x->d_idx, x->d_cls);
+		uint32_t *keys = x->at<uint32_t>(B_KEYS), *keys2 = x->at<uint32_t>(B_KEYS2), *idx = x->at<uint32_t>(B_IDX), *idx2 = x->at<uint32_t>(B_IDX2);
+		HIP_TRY(hipMemsetAsync(d_cls, 0, 16 * sizeof(unsigned long long), s));
+		hipLaunchKernelGGL(cse::lanes_keys_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)x->n_cu * 8)), dim3(256), 0, s, A, keys, idx, d_cls);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(x->h_cls, x->d_cls, 2 * cse::LANES_NCLASS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-		size_t tb = 0;
-		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)x->d_keys, (uint32_t *)x->d_keys2, (uint32_t *)x->d_idx, (uint32_t *)x->d_idx2, (size_t)n, 0u, 32u, s));
-		if (int rc = grow(&x->d_sort, &x->c_sort, tb + 16)) return rc;
-		HIP_TRY(rocprim::radix_sort_pairs(x->d_sort, tb, (uint32_t *)x->d_keys, (uint32_t *)x->d_keys2, (uint32_t *)x->d_idx, (uint32_t *)x->d_idx2, (size_t)n, 0u, 32u, s));
+		HIP_TRY(hipMemcpyAsync(h_cls, d_cls, 2 * cse::LANES_NCLASS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+		HIP_TRY(rocprim::radix_sort_pairs(x->b[B_SORT].p, sort_bytes, keys, keys2, idx, idx2, (size_t)n, 0u, 32u, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		int64_t first = 0;
 		// one launch per class (its LDS size), the largest first, spread over three streams: the tail of one class is filled by the next
 		HIP_TRY(hipEventRecord(x->ev_fork, s));
 		for (int k = 0; k < 2; ++k) HIP_TRY(hipStreamWaitEvent(x->side[k], x->ev_fork, 0));
 		int64_t start[2 * cse::LANES_NCLASS]; int by_size[2 * cse::LANES_NCLASS];
-		for (int c = 0; c < 2 * cse::LANES_NCLASS; ++c) { start[c] = first; first += (int64_t)x->h_cls[c]; by_size[c] = c; }
-		std::sort(by_size, by_size + 2 * cse::LANES_NCLASS, [&](int a, int b) { return x->h_cls[a] > x->h_cls[b]; });
+		for (int c = 0; c < 2 * cse::LANES_NCLASS; ++c) { start[c] = first; first += (int64_t)h_cls[c]; by_size[c] = c; }
+		std::sort(by_size, by_size + 2 * cse::LANES_NCLASS, [&](int a, int b) { return h_cls[a] > h_cls[b]; });
 		int nl = 0;
 		for (int o = 0; o < 2 * cse::LANES_NCLASS; ++o) {
 			const int c = by_size[o];
-			const int64_t cnt = (int64_t)x->h_cls[c];
+			const int64_t cnt = (int64_t)h_cls[c];
 			if (cnt <= 0) continue;
 			const bool narrow = c < cse::LANES_NCLASS;
 			const int qmax = cse::LANES_QCLASS[c % cse::LANES_NCLASS];
 			const bool qin = narrow && x->qin;
 			const size_t lds = qin ? (size_t)(qmax + 3) * 256 : (size_t)(qmax + 2) * 64 * (narrow ? 2 : 4) + (size_t)(qmax + 1) * 64;   // (+ 1 query row: the loop fetches one column ahead)
-			hipStream_t ls = nl % 3 == 0 ? s : x->side[nl % 3 - 1]; ++nl;
-			if (qin) hipLaunchKernelGGL((cse::extend_lanes_kernel<uint32_t, true>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)x->d_idx2, start[c], cnt, qmax);
-			else if (narrow) hipLaunchKernelGGL((cse::extend_lanes_kernel<uint16_t, false>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)x->d_idx2, start[c], cnt, qmax);
-			else hipLaunchKernelGGL((cse::extend_lanes_kernel<uint32_t, false>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)x->d_idx2, start[c], cnt, qmax);
+			hipStream_t ls = nl % 3 == 0 ? s : (hipStream_t)x->side[nl % 3 - 1]; ++nl;
+			if (qin) hipLaunchKernelGGL((cse::extend_lanes_kernel<uint32_t, true>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)idx2, start[c], cnt, qmax);
+			else if (narrow) hipLaunchKernelGGL((cse::extend_lanes_kernel<uint16_t, false>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)idx2, start[c], cnt, qmax);
+			else hipLaunchKernelGGL((cse::extend_lanes_kernel<uint32_t, false>), dim3((unsigned)((cnt + 63) / 64)), dim3(64), lds, ls, A, (const uint32_t *)idx2, start[c], cnt, qmax);
 			HIP_TRY(hipGetLastError());
 		}
 		for (int k = 0; k < 2; ++k) { HIP_TRY(hipEventRecord(x->ev_join[k], x->side[k])); HIP_TRY(hipStreamWaitEvent(s, x->ev_join[k], 0)); }
 		n_lanes = first;
 		A.packed16 = 1;                    // extend_kernel below takes only what the key kernel marked DECLINED
 	}
-	if (n_lanes == n) goto done;          // (nothing left for the wave-per-pair kernels)
-	{ // the pairs of the 16-bit class first, two columns per lane (declines what does not fit: those get DECLINED as their score) ...
+	if (n_lanes != n) {                   // (else nothing is left for the wave-per-pair kernels)
+		// the pairs of the 16-bit class first, two columns per lane (declines what does not fit: those get DECLINED as their score) ...
 		const size_t per_wave16 = (size_t)3 * ((A.max_qlen + 4) >> 1) * 4;
 		if (x->packed16 && per_wave16 <= 60 * 1024) {
 			const int wpb = per_wave16 <= 15 * 1024 ? 4 : per_wave16 <= 30 * 1024 ? 2 : 1;
@@ -672,25 +641,60 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
 			HIP_TRY(hipGetLastError());
 			A.packed16 = 1;
 		}
+		// ... then everything else (and every pair, where the packed kernel is off) one column per lane
+		if (per_wave <= 60 * 1024) {
+			const int wpb = per_wave <= 15 * 1024 ? 4 : per_wave <= 30 * 1024 ? 2 : 1;
+			const int64_t blocks = std::min<int64_t>((n + wpb - 1) / wpb, (int64_t)x->n_cu * (wpb == 4 ? 8 : wpb == 2 ? 4 : 2));
+			hipLaunchKernelGGL(cse::extend_kernel<true>, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(64 * wpb), per_wave * wpb, s, A);
+		} else { // long queries: the band state in HBM
+			const int64_t blocks = std::min<int64_t>((n + 3) / 4, (int64_t)x->n_cu * 4);
+			A.scratch = x->at<int32_t>(B_SCRATCH);
+			hipLaunchKernelGGL(cse::extend_kernel<false>, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, s, A);
+		}
+		HIP_TRY(hipGetLastError());
 	}
-	// ... then everything else (and every pair, where the packed kernel is off) one column per lane
-	if (per_wave <= 60 * 1024) {
-		const int wpb = per_wave <= 15 * 1024 ? 4 : per_wave <= 30 * 1024 ? 2 : 1;
-		const int64_t blocks = std::min<int64_t>((n + wpb - 1) / wpb, (int64_t)x->n_cu * (wpb == 4 ? 8 : wpb == 2 ? 4 : 2));
-		hipLaunchKernelGGL(cse::extend_kernel<true>, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(64 * wpb), per_wave * wpb, s, A);
-	} else { // long queries: the band state in HBM
-		const int64_t blocks = std::min<int64_t>((n + 3) / 4, (int64_t)x->n_cu * 4);
-		if (int rc = grow(&x->d_scratch, &x->c_scratch, (size_t)std::max<int64_t>(blocks, 1) * 4 * 2 * (A.max_qlen + 2) * sizeof(int32_t))) return rc;
-		A.scratch = (int32_t *)x->d_scratch;
-		hipLaunchKernelGGL(cse::extend_kernel<false>, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, s, A);
-	}
-	HIP_TRY(hipGetLastError());
-done:
-	HIP_TRY(hipEventRecord(x->ev1, s));
-	HIP_TRY(hipMemcpyAsync(x->h_ctr, x->d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipEventRecord(x->ev[1], s));
+	HIP_TRY(hipMemcpyAsync(x->h_ctr, d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
+	return CS_OK;
+}
+
+// the launch: pairs, sequences and results are device memory here.  Every buffer grows before the kernels that use it are launched, at a
+// point where nothing of the extender is in flight (growing frees the old memory): the lane kernel's arrays and rocPRIM's scratch before
+// the call's first launch, the HBM band state once the longest query is known and the stream has been waited for.
+static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs, const uint8_t *d_q, uint64_t q_bytes, const uint8_t *d_t, uint64_t t_bytes,
+                         int32_t w, cs_ext_result_t *d_out)
+{
+	hipStream_t s = x->s;
+	unsigned long long *d_ctr = x->at<unsigned long long>(B_CTR);
+	size_t sort_bytes = 0;
+	if (x->lanes && n < (1ll << 32)) {
+		for (int which : {B_KEYS, B_KEYS2, B_IDX, B_IDX2}) if (int rc = x->ensure(which, (size_t)n * 4)) return rc;
+		HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, x->at<uint32_t>(B_KEYS), x->at<uint32_t>(B_KEYS2), x->at<uint32_t>(B_IDX), x->at<uint32_t>(B_IDX2), (size_t)n, 0u, 32u, s));
+		if (int rc = x->ensure(B_SORT, sort_bytes + 16)) return rc;
+	}
+	HIP_TRY(hipMemsetAsync(d_ctr, 0, 4 * sizeof(unsigned long long), s));
+	hipLaunchKernelGGL(cse::max_qlen_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)x->n_cu * 8)), dim3(256), 0, s, d_pairs, n, d_ctr + 3);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(x->h_ctr, d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	const int64_t max_q = (int64_t)x->h_ctr[3];
+	if (max_q > 65535) return cs_fail_(CS_ERANGE, "cs_extend_batch: a query is longer than 65535 bases (MAX_READ_LEN, mapping/comp_seed.h:39)");
+	if ((int64_t)x->P.best * max_q > (1 << 29)) return cs_fail_(CS_ERANGE, "cs_extend_batch: scores would not fit the kernel's 30-bit range");
+	cse::ExtArgs A;
+	A.pairs = d_pairs; A.n = n; A.qbuf = d_q; A.tbuf = d_t; A.q_bytes = q_bytes; A.t_bytes = t_bytes; A.out = d_out; A.w = w; A.max_qlen = (int32_t)std::max<int64_t>(max_q, 1);
+	A.P = x->P; A.mat = (const int8_t *)(d_ctr + 4); A.scratch = nullptr; A.err = d_ctr; A.stat = d_ctr + 1;
+	if (((size_t)2 * (A.max_qlen + 2) + ((A.max_qlen + 3) >> 2)) * 4 > 60 * 1024) { // too long for LDS: extend_kernel<false>'s band state, per wave of its grid
+		const int64_t blocks = std::min<int64_t>((n + 3) / 4, (int64_t)x->n_cu * 4);
+		if (int rc = x->ensure(B_SCRATCH, (size_t)std::max<int64_t>(blocks, 1) * 4 * 2 * (A.max_qlen + 2) * sizeof(int32_t))) return rc;
+	}
+	if (int rc = extend_launches(x, A, sort_bytes)) { // nothing of a failed call stays in flight: the next call clears B_CTR and may free what these kernels use
+		for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(x->side[k]);
+		(void)hipStreamSynchronize(s);
+		return rc;
+	}
 	float ms = 0.f;
-	HIP_TRY(hipEventElapsedTime(&ms, x->ev0, x->ev1));
+	HIP_TRY(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
 	x->st.pairs += (uint64_t)n; x->st.cells += x->h_ctr[1]; x->st.rows += x->h_ctr[2]; x->st.kernel_ms += ms; x->st.launches++;
 	if (x->h_ctr[0]) return cs_fail_(CS_EINVAL, "cs_extend_batch: " + std::to_string(x->h_ctr[0]) + " pair(s) with qlen < 1, tlen < 0 or offsets outside the sequence buffers (their results are zero)");
 	return CS_OK;
@@ -705,43 +709,50 @@ extern "C" int cs_extend_batch_device(cs_extender_t *x, int64_t n_pairs, const c
 	return extend_device(x, n_pairs, d_pairs, d_qbuf, q_bytes, d_tbuf, t_bytes, w, d_out);
 }
 
-extern "C" int cs_extend_batch(cs_extender_t *x, int64_t n_pairs, const cs_ext_pair_t *pairs, const uint8_t *qbuf, uint64_t q_bytes,
-                               const uint8_t *tbuf, uint64_t t_bytes, int32_t w, cs_ext_result_t *out)
+// The three host forms.  The band retries of the reference extend the SAME sequences again with another pair list (comp_seed.cpp:1717-1776):
+// the two buffers go up once and stay resident in the extender; every try then moves only its pairs in and its results out.
+// sequences up, no wait: the caller's buffers stay alive until the stream has been waited for
+static int seqs_up(cs_extender *x, const uint8_t *qbuf, uint64_t q_bytes, const uint8_t *tbuf, uint64_t t_bytes)
 {
-	if (!x || n_pairs < 0 || w < 0 || (n_pairs > 0 && (!pairs || !out)) || (q_bytes && !qbuf) || (t_bytes && !tbuf)) return cs_fail_(CS_EINVAL, "cs_extend_batch: bad argument");
-	if (n_pairs == 0) return CS_OK;
-	HIP_TRY(hipSetDevice(x->device));
-	if (int rc = grow(&x->d_pairs, &x->c_pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t))) return rc;
-	if (int rc = grow(&x->d_out, &x->c_out, (size_t)n_pairs * sizeof(cs_ext_result_t))) return rc;
-	if (int rc = grow(&x->d_q, &x->c_q, (size_t)q_bytes + 64)) return rc;
-	if (int rc = grow(&x->d_t, &x->c_t, (size_t)t_bytes + 64)) return rc;
-	hipStream_t s = x->stream;
-	HIP_TRY(hipMemcpyAsync(x->d_pairs, pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t), hipMemcpyHostToDevice, s));
-	if (q_bytes) HIP_TRY(hipMemcpyAsync(x->d_q, qbuf, (size_t)q_bytes, hipMemcpyHostToDevice, s));
-	if (t_bytes) HIP_TRY(hipMemcpyAsync(x->d_t, tbuf, (size_t)t_bytes, hipMemcpyHostToDevice, s));
-	const int rc = extend_device(x, n_pairs, (const cs_ext_pair_t *)x->d_pairs, (const uint8_t *)x->d_q, q_bytes, (const uint8_t *)x->d_t, t_bytes, w, (cs_ext_result_t *)x->d_out);
+	x->res_q = x->res_t = 0;              // (a growth that fails leaves its buffer empty)
+	int rc = x->up(B_Q, qbuf, (size_t)q_bytes);
+	if (!rc) rc = x->up(B_T, tbuf, (size_t)t_bytes);
+	if (rc) { (void)hipStreamSynchronize(x->s); return rc; }   // (the first copy may be on its way)
+	x->res_q = q_bytes; x->res_t = t_bytes;
+	return CS_OK;
+}
+// pairs up, the kernels over the resident sequences, results down; what the kernels reported is raised again behind the download
+static int extend_resident(cs_extender *x, int64_t n_pairs, const cs_ext_pair_t *pairs, int32_t w, cs_ext_result_t *out)
+{
+	int rc = x->ensure(B_OUT, (size_t)n_pairs * sizeof(cs_ext_result_t));
+	if (!rc) rc = x->up(B_PAIRS, pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t));
+	if (rc) { (void)hipStreamSynchronize(x->s); return rc; }   // (cs_extend_batch's sequences may be on their way)
+	rc = extend_device(x, n_pairs, x->at<cs_ext_pair_t>(B_PAIRS), x->at<uint8_t>(B_Q), x->res_q, x->at<uint8_t>(B_T), x->res_t, w, x->at<cs_ext_result_t>(B_OUT));
 	const std::string keep = rc != CS_OK ? std::string(cs_last_error()) : std::string();
 	if (rc == CS_OK || rc == CS_EINVAL) { // (CS_EINVAL from skipped pairs: the other results are valid and are delivered)
-		hipError_t e = hipMemcpyAsync(out, x->d_out, (size_t)n_pairs * sizeof(cs_ext_result_t), hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess) e = hipStreamSynchronize(s);
+		hipError_t e = hipMemcpyAsync(out, x->b[B_OUT].p, (size_t)n_pairs * sizeof(cs_ext_result_t), hipMemcpyDeviceToHost, x->s);
+		if (e == hipSuccess) e = hipStreamSynchronize(x->s);
 		if (e != hipSuccess) { (void)hipGetLastError(); return cs_fail_(CS_EDEVICE, hipGetErrorString(e)); }
 	}
 	if (rc != CS_OK) return cs_fail_(rc, keep);
 	return CS_OK;
 }
 
-// The band retries of the reference extend the SAME sequences again with another pair list (comp_seed.cpp:1717-1776): the two buffers
-// are uploaded once and stay resident in the extender; every try then moves only its pairs in and its results out.
+extern "C" int cs_extend_batch(cs_extender_t *x, int64_t n_pairs, const cs_ext_pair_t *pairs, const uint8_t *qbuf, uint64_t q_bytes,
+                               const uint8_t *tbuf, uint64_t t_bytes, int32_t w, cs_ext_result_t *out)
+{
+	if (!x || n_pairs < 0 || w < 0 || (n_pairs > 0 && (!pairs || !out)) || (q_bytes && !qbuf) || (t_bytes && !tbuf)) return cs_fail_(CS_EINVAL, "cs_extend_batch: bad argument");
+	if (n_pairs == 0) return CS_OK;
+	HIP_TRY(hipSetDevice(x->device));
+	if (int rc = seqs_up(x, qbuf, q_bytes, tbuf, t_bytes)) return rc;
+	return extend_resident(x, n_pairs, pairs, w, out);
+}
 extern "C" int cs_extender_upload(cs_extender_t *x, const uint8_t *qbuf, uint64_t q_bytes, const uint8_t *tbuf, uint64_t t_bytes)
 {
 	if (!x || (q_bytes && !qbuf) || (t_bytes && !tbuf)) return cs_fail_(CS_EINVAL, "cs_extender_upload: bad argument");
 	HIP_TRY(hipSetDevice(x->device));
-	if (int rc = grow(&x->d_q, &x->c_q, (size_t)q_bytes + 64)) return rc;
-	if (int rc = grow(&x->d_t, &x->c_t, (size_t)t_bytes + 64)) return rc;
-	if (q_bytes) HIP_TRY(hipMemcpyAsync(x->d_q, qbuf, (size_t)q_bytes, hipMemcpyHostToDevice, x->stream));
-	if (t_bytes) HIP_TRY(hipMemcpyAsync(x->d_t, tbuf, (size_t)t_bytes, hipMemcpyHostToDevice, x->stream));
-	HIP_TRY(hipStreamSynchronize(x->stream));
-	x->res_q = q_bytes; x->res_t = t_bytes;
+	if (int rc = seqs_up(x, qbuf, q_bytes, tbuf, t_bytes)) return rc;
+	HIP_TRY(hipStreamSynchronize(x->s));
 	return CS_OK;
 }
 extern "C" int cs_extend_batch_resident(cs_extender_t *x, int64_t n_pairs, const cs_ext_pair_t *pairs, int32_t w, cs_ext_result_t *out)
@@ -749,19 +760,7 @@ extern "C" int cs_extend_batch_resident(cs_extender_t *x, int64_t n_pairs, const
 	if (!x || n_pairs < 0 || w < 0 || (n_pairs > 0 && (!pairs || !out))) return cs_fail_(CS_EINVAL, "cs_extend_batch_resident: bad argument");
 	if (n_pairs == 0) return CS_OK;
 	HIP_TRY(hipSetDevice(x->device));
-	if (int rc = grow(&x->d_pairs, &x->c_pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t))) return rc;
-	if (int rc = grow(&x->d_out, &x->c_out, (size_t)n_pairs * sizeof(cs_ext_result_t))) return rc;
-	hipStream_t s = x->stream;
-	HIP_TRY(hipMemcpyAsync(x->d_pairs, pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t), hipMemcpyHostToDevice, s));
-	const int rc = extend_device(x, n_pairs, (const cs_ext_pair_t *)x->d_pairs, (const uint8_t *)x->d_q, x->res_q, (const uint8_t *)x->d_t, x->res_t, w, (cs_ext_result_t *)x->d_out);
-	const std::string keep = rc != CS_OK ? std::string(cs_last_error()) : std::string();
-	if (rc == CS_OK || rc == CS_EINVAL) {
-		hipError_t e = hipMemcpyAsync(out, x->d_out, (size_t)n_pairs * sizeof(cs_ext_result_t), hipMemcpyDeviceToHost, s);
-		if (e == hipSuccess) e = hipStreamSynchronize(s);
-		if (e != hipSuccess) { (void)hipGetLastError(); return cs_fail_(CS_EDEVICE, hipGetErrorString(e)); }
-	}
-	if (rc != CS_OK) return cs_fail_(rc, keep);
-	return CS_OK;
+	return extend_resident(x, n_pairs, pairs, w, out);
 }
 
 extern "C" int cs_extender_stats(const cs_extender_t *x, cs_ext_stats_t *st)

@@ -12,12 +12,13 @@
 // suffixes inside long repeats; those stay in "unresolved" groups that are re-sorted by the rank of the suffix h
 // symbols further on (h = 29, 58, 116, ...) until every group is a singleton.  Only unresolved suffixes are touched
 // after the first pass, so a genome with few long repeats costs ~one 64-bit radix sort of N keys.
-#include "cs_internal.hpp"
+#include "dev_stage.hpp"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -25,16 +26,6 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
-
-#define HIPB(expr)                                                                                         \
-	do {                                                                                                   \
-		hipError_t e__ = (expr);                                                                           \
-		if (e__ != hipSuccess) {                                                                           \
-			(void)hipGetLastError();                                                                       \
-			rc = cs_fail_(e__ == hipErrorOutOfMemory ? CS_ENOMEM : CS_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-			goto done;                                                                                     \
-		}                                                                                                  \
-	} while (0)
 
 namespace {
 
@@ -234,81 +225,69 @@ template <typename idx_t> __global__ void carry_max_kernel(idx_t *p) { if (p[-1]
 template <typename idx_t>
 static int build_impl(const uint8_t *fwd_nt4, uint64_t l_pac, int device, bool verbose, cs_index_t **out)
 {
-	int rc = CS_OK;
 	const uint64_t n = 2 * l_pac, m = n + 1; // m rows including the $ row
 
-	hipStream_t s = nullptr;
-	uint8_t *d_fwd = nullptr, *d_T = nullptr; void *d_tmp = nullptr; size_t tmp_cap = 0;
-	uint64_t *d_key = nullptr, *d_key2 = nullptr, *d_pos = nullptr;
-	idx_t *d_sfx = nullptr, *d_sfx2 = nullptr, *d_head = nullptr, *d_rank = nullptr;
-	uint8_t *d_flag = nullptr;
-	idx_t *slot = nullptr, *isfx = nullptr, *grp = nullptr, *slot2 = nullptr, *isfx2 = nullptr, *grp2 = nullptr, *isfx_s = nullptr;
-	unsigned long long *d_prim = nullptr; unsigned long long h_prim = 0;
-	uint32_t *d_words = nullptr, *d_bwt = nullptr; uint64_t *d_cnt = nullptr, *d_occ = nullptr, *d_sa = nullptr;
+	// every device array frees itself on any return; the stream goes last.  A buffer that a later step recycles is moved or swapped whole.
+	HipStream s;
+	DevBuf<uint8_t> d_fwd, d_T, d_tmp, d_flag;
+	DevBuf<uint64_t> d_key, d_key2, d_pos;
+	DevBuf<idx_t> d_sfx, d_sfx2, d_head, d_rank;
+	DevBuf<idx_t> slot, isfx, grp, slot2, isfx2, grp2, isfx_s;
+	DevBuf<unsigned long long> d_prim; unsigned long long h_prim = 0;
+	DevBuf<uint32_t> d_words, d_bwt; DevBuf<uint64_t> d_cnt, d_occ, d_sa;
 	uint64_t u = 0, hstep = K0;
-	cs_index *ix = nullptr;
 	uint64_t n_words = (n + 15) >> 4, n_blocks = (n + 127) >> 7, bwt_size = n_words + (n_blocks + 1) * 8, n_sa = (n + 32) / 32;
 	uint64_t last = 0;
-	idx_t *d_sa32 = nullptr;
 
-	auto need_tmp = [&](size_t bytes) -> hipError_t {
-		if (bytes <= tmp_cap) return hipSuccess;
-		if (d_tmp) (void)hipFree(d_tmp);
-		d_tmp = nullptr; tmp_cap = 0;
-		hipError_t e = hipMalloc(&d_tmp, bytes + 256);
-		if (e == hipSuccess) tmp_cap = bytes + 256;
-		return e;
-	};
 	// rocPRIM 4.2's device scans truncate their size to 32 bits (measured: a 5e9-element scan stops after 705 M elements),
 	// so every scan that can exceed 2^32 rows runs in 2^30-element pieces with the running value carried between them.
+	// Every buffer is reserved from empty, so its size is exactly what is asked for; d_tmp, rocPRIM's scratch, is the one that is reserved
+	// again while it holds memory and may then get DevBuf's half on top (it is small: released after the first sort, kilobytes later).
 	const uint64_t PIECE = 1ull << 30;
-	auto scan_flags = [&](const uint8_t *flag, uint64_t *pos, uint64_t cnt, bool inclusive) -> hipError_t {
+	auto scan_flags = [&](const uint8_t *flag, uint64_t *pos, uint64_t cnt, bool inclusive) -> int {
 		uint64_t carry = 0;
 		for (uint64_t o = 0; o < cnt; o += PIECE) {
 			uint64_t c = std::min<uint64_t>(PIECE, cnt - o);
 			auto in = rocprim::make_transform_iterator(flag + o, U8ToU64());
 			size_t tb = 0;
-			hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, pos + o, carry, (size_t)c, rocprim::plus<uint64_t>(), s);
-			if (e != hipSuccess) return e;
-			if ((e = need_tmp(tb)) != hipSuccess) return e;
-			if ((e = rocprim::exclusive_scan(d_tmp, tb, in, pos + o, carry, (size_t)c, rocprim::plus<uint64_t>(), s)) != hipSuccess) return e;
+			HIP_TRY(rocprim::exclusive_scan(nullptr, tb, in, pos + o, carry, (size_t)c, rocprim::plus<uint64_t>(), s));
+			if (int rc = d_tmp.reserve(tb + 256)) return rc;
+			HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, in, pos + o, carry, (size_t)c, rocprim::plus<uint64_t>(), s));
 			if (o + c < cnt || inclusive) { // carry = exclusive value of the last element + its flag
 				uint64_t lastv = 0; uint8_t lastf = 0;
-				if ((e = hipMemcpyAsync(&lastv, pos + o + c - 1, 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-				if ((e = hipMemcpyAsync(&lastf, flag + o + c - 1, 1, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-				if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+				HIP_TRY(hipMemcpyAsync(&lastv, pos + o + c - 1, 8, hipMemcpyDeviceToHost, s));
+				HIP_TRY(hipMemcpyAsync(&lastf, flag + o + c - 1, 1, hipMemcpyDeviceToHost, s));
+				HIP_TRY(hipStreamSynchronize(s));
 				carry = lastv + lastf;
 			}
 		}
 		if (inclusive) hipLaunchKernelGGL(add_flag_kernel, dim3(gridof(cnt)), dim3(256), 0, s, flag, pos, cnt); // exclusive -> inclusive
-		return hipGetLastError();
+		HIP_TRY(hipGetLastError());
+		return CS_OK;
 	};
-	auto scan_max = [&](idx_t *io, uint64_t cnt) -> hipError_t {
+	auto scan_max = [&](idx_t *io, uint64_t cnt) -> int {
 		for (uint64_t o = 0; o < cnt; o += PIECE) {
 			uint64_t c = std::min<uint64_t>(PIECE, cnt - o);
 			if (o) hipLaunchKernelGGL((carry_max_kernel<idx_t>), dim3(1), dim3(1), 0, s, io + o); // io[o] = max(io[o], io[o-1])
 			size_t tb = 0;
-			hipError_t e = rocprim::inclusive_scan(nullptr, tb, io + o, io + o, (size_t)c, MaxOp<idx_t>(), s);
-			if (e != hipSuccess) return e;
-			if ((e = need_tmp(tb)) != hipSuccess) return e;
-			if ((e = rocprim::inclusive_scan(d_tmp, tb, io + o, io + o, (size_t)c, MaxOp<idx_t>(), s)) != hipSuccess) return e;
+			HIP_TRY(rocprim::inclusive_scan(nullptr, tb, io + o, io + o, (size_t)c, MaxOp<idx_t>(), s));
+			if (int rc = d_tmp.reserve(tb + 256)) return rc;
+			HIP_TRY(rocprim::inclusive_scan(d_tmp.p, tb, io + o, io + o, (size_t)c, MaxOp<idx_t>(), s));
 		}
-		return hipSuccess;
+		return CS_OK;
 	};
-	// sorts (k0,v0) using (k1,v1) as the ping-pong partner; on return k0/v0 point at the sorted data and k1/v1 at the
+	// sorts (k0,v0) using (k1,v1) as the ping-pong partner; on return k0/v0 hold the sorted data and k1/v1 the
 	// scratch copy (rocPRIM's double_buffer form: no hidden third buffer, which matters at 50 GB per array)
-	auto sort_pairs = [&](uint64_t *&k0, uint64_t *&k1, idx_t *&v0, idx_t *&v1, uint64_t cnt, unsigned bits) -> hipError_t {
-		rocprim::double_buffer<uint64_t> kb(k0, k1);
-		rocprim::double_buffer<idx_t> vb(v0, v1);
+	auto sort_pairs = [&](DevBuf<uint64_t> &k0, DevBuf<uint64_t> &k1, DevBuf<idx_t> &v0, DevBuf<idx_t> &v1, uint64_t cnt, unsigned bits) -> int {
+		rocprim::double_buffer<uint64_t> kb(k0.p, k1.p);
+		rocprim::double_buffer<idx_t> vb(v0.p, v1.p);
 		size_t tb = 0;
-		hipError_t e = rocprim::radix_sort_pairs(nullptr, tb, kb, vb, (size_t)cnt, 0u, bits, s);
-		if (e != hipSuccess) return e;
-		if ((e = need_tmp(tb)) != hipSuccess) return e;
-		e = rocprim::radix_sort_pairs(d_tmp, tb, kb, vb, (size_t)cnt, 0u, bits, s);
-		if (e != hipSuccess) return e;
-		if (kb.current() != k0) std::swap(k0, k1);
-		if (vb.current() != v0) std::swap(v0, v1);
-		return hipSuccess;
+		HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, kb, vb, (size_t)cnt, 0u, bits, s));
+		if (int rc = d_tmp.reserve(tb + 256)) return rc;
+		HIP_TRY(rocprim::radix_sort_pairs(d_tmp.p, tb, kb, vb, (size_t)cnt, 0u, bits, s));
+		if (kb.current() != k0.p) std::swap(k0, k1);
+		if (vb.current() != v0.p) std::swap(v0, v1);
+		return CS_OK;
 	};
 
 	auto stage = [&](const char *what) {
@@ -316,143 +295,135 @@ static int build_impl(const uint8_t *fwd_nt4, uint64_t l_pac, int device, bool v
 		size_t fr = 0, to = 0; (void)hipMemGetInfo(&fr, &to);
 		fprintf(stderr, "[cs_index_build] %s (idx %zu B, rows %llu, free %.1f GB)\n", what, sizeof(idx_t), (unsigned long long)m, fr / 1e9); fflush(stderr);
 	};
-	HIPB(hipSetDevice(device));
-	HIPB(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+	HIP_TRY(hipSetDevice(device));
+	HIP_TRY(hipStreamCreateWithFlags(&s.h, hipStreamNonBlocking));
 	stage("start");
-	HIPB(hipMalloc((void **)&d_fwd, l_pac));
-	HIPB(hipMalloc((void **)&d_T, n + 64));
-	HIPB(hipMemcpyAsync(d_fwd, fwd_nt4, l_pac, hipMemcpyHostToDevice, s));
-	hipLaunchKernelGGL(make_text_kernel, dim3(gridof(n)), dim3(256), 0, s, d_fwd, l_pac, d_T);
-	HIPB(hipStreamSynchronize(s));
-	(void)hipFree(d_fwd); d_fwd = nullptr;
+	if (int rc = d_fwd.reserve(l_pac)) return rc;
+	if (int rc = d_T.reserve(n + 64)) return rc;
+	HIP_TRY(hipMemcpyAsync(d_fwd.p, fwd_nt4, l_pac, hipMemcpyHostToDevice, s));
+	hipLaunchKernelGGL(make_text_kernel, dim3(gridof(n)), dim3(256), 0, s, d_fwd.p, l_pac, d_T.p);
+	HIP_TRY(hipStreamSynchronize(s));
+	d_fwd.release();
 
 	stage("text ready");
 	// ---- first pass: sort all m suffixes by their 29-symbol key
-	HIPB(hipMalloc((void **)&d_key, m * 8)); HIPB(hipMalloc((void **)&d_key2, m * 8));
-	HIPB(hipMalloc((void **)&d_sfx, m * sizeof(idx_t))); HIPB(hipMalloc((void **)&d_sfx2, m * sizeof(idx_t)));
-	hipLaunchKernelGGL((make_keys_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_T, n, d_key, d_sfx);
+	for (auto *b : {&d_key, &d_key2}) if (int rc = b->reserve(m)) return rc;
+	for (auto *b : {&d_sfx, &d_sfx2}) if (int rc = b->reserve(m)) return rc;
+	hipLaunchKernelGGL((make_keys_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_T.p, n, d_key.p, d_sfx.p);
 	stage("keys made");
-	HIPB(sort_pairs(d_key, d_key2, d_sfx, d_sfx2, m, 64));
-	HIPB(hipStreamSynchronize(s));
+	if (int rc = sort_pairs(d_key, d_key2, d_sfx, d_sfx2, m, 64)) return rc;
+	HIP_TRY(hipStreamSynchronize(s));
 	stage("first sort done");
-	if (d_tmp) { (void)hipFree(d_tmp); d_tmp = nullptr; tmp_cap = 0; }
+	d_tmp.release();
 	std::swap(d_key, d_key2); std::swap(d_sfx, d_sfx2);
 	// d_key2 / d_sfx2 now hold the sorted keys and the provisional suffix array.  Memory matters at hg19 scale (6.2e9
 	// rows x 8 B = 50 GB per array), so the scratch copies are recycled: d_sfx becomes the group-head array and d_key the
 	// prefix-sum array, and the sorted keys are dropped as soon as the group heads are known.
-	d_head = d_sfx; d_sfx = nullptr;
-	d_pos = d_key; d_key = nullptr;
-	hipLaunchKernelGGL((heads_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_key2, m, d_head);
-	HIPB(scan_max(d_head, m));
-	HIPB(hipStreamSynchronize(s));
+	d_head = std::move(d_sfx);
+	d_pos = std::move(d_key);
+	hipLaunchKernelGGL((heads_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_key2.p, m, d_head.p);
+	if (int rc = scan_max(d_head.p, m)) return rc;
+	HIP_TRY(hipStreamSynchronize(s));
 	stage("group heads done");
-	(void)hipFree(d_key2); d_key2 = nullptr;
-	HIPB(hipMalloc((void **)&d_rank, (m + 1) * sizeof(idx_t)));
-	HIPB(hipMalloc((void **)&d_flag, m + 16));
-	hipLaunchKernelGGL((first_ranks_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_sfx2, d_head, m, d_rank, d_flag);
-	HIPB(scan_flags(d_flag, d_pos, m, false));
-	HIPB(hipMemcpyAsync(&last, d_pos + (m - 1), 8, hipMemcpyDeviceToHost, s));
-	{ uint8_t lf = 0; HIPB(hipMemcpyAsync(&lf, d_flag + (m - 1), 1, hipMemcpyDeviceToHost, s)); HIPB(hipStreamSynchronize(s)); u = last + lf; }
+	d_key2.release();
+	if (int rc = d_rank.reserve(m + 1)) return rc;
+	if (int rc = d_flag.reserve(m + 16)) return rc;
+	hipLaunchKernelGGL((first_ranks_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_sfx2.p, d_head.p, m, d_rank.p, d_flag.p);
+	if (int rc = scan_flags(d_flag.p, d_pos.p, m, false)) return rc;
+	HIP_TRY(hipMemcpyAsync(&last, d_pos.p + (m - 1), 8, hipMemcpyDeviceToHost, s));
+	{ uint8_t lf = 0; HIP_TRY(hipMemcpyAsync(&lf, d_flag.p + (m - 1), 1, hipMemcpyDeviceToHost, s)); HIP_TRY(hipStreamSynchronize(s)); u = last + lf; }
 	if (verbose) fprintf(stderr, "[cs_index_build] unresolved suffixes after the first pass: %llu\n", (unsigned long long)u);
 	stage("ranks done");
 	if (u) {
-		HIPB(hipMalloc((void **)&slot, u * sizeof(idx_t))); HIPB(hipMalloc((void **)&isfx, u * sizeof(idx_t))); HIPB(hipMalloc((void **)&grp, u * sizeof(idx_t)));
-		hipLaunchKernelGGL((compact_first_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_flag, d_pos, d_sfx2, d_head, m, slot, isfx, grp);
+		for (auto *b : {&slot, &isfx, &grp}) if (int rc = b->reserve(u)) return rc;
+		hipLaunchKernelGGL((compact_first_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_flag.p, d_pos.p, d_sfx2.p, d_head.p, m, slot.p, isfx.p, grp.p);
 	}
-	HIPB(hipStreamSynchronize(s));
-	(void)hipFree(d_head); d_head = nullptr; (void)hipFree(d_pos); d_pos = nullptr; // 2 x 50 GB back before the item arrays
+	HIP_TRY(hipStreamSynchronize(s));
+	d_head.release(); d_pos.release(); // 2 x 50 GB back before the item arrays
 	if (u) { // item-space work arrays
-		HIPB(hipMalloc((void **)&slot2, u * sizeof(idx_t))); HIPB(hipMalloc((void **)&isfx2, u * sizeof(idx_t))); HIPB(hipMalloc((void **)&grp2, u * sizeof(idx_t)));
-		HIPB(hipMalloc((void **)&isfx_s, u * sizeof(idx_t)));
-		HIPB(hipMalloc((void **)&d_pos, (u + 1) * 8));
-		HIPB(hipMalloc((void **)&d_key, u * 8)); HIPB(hipMalloc((void **)&d_key2, u * 8)); HIPB(hipMalloc((void **)&d_head, u * sizeof(idx_t)));
+		for (auto *b : {&slot2, &isfx2, &grp2, &isfx_s, &d_head}) if (int rc = b->reserve(u)) return rc;
+		if (int rc = d_pos.reserve(u + 1)) return rc;
+		for (auto *b : {&d_key, &d_key2}) if (int rc = b->reserve(u)) return rc;
 	}
 	// ---- doubling rounds over the unresolved items only
 	for (int round = 0; u > 0; ++round) {
-		if (round > 40) { rc = cs_fail_(CS_EDEVICE, "cs_index_build: prefix doubling did not converge"); goto done; }
-		hipLaunchKernelGGL((group_flag_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, grp, u, d_flag);
-		HIPB(scan_flags(d_flag, d_pos, u, true));
-		hipLaunchKernelGGL((round_keys_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, isfx, d_pos, d_rank, u, hstep, d_key);
-		HIPB(sort_pairs(d_key, d_key2, isfx, isfx_s, u, 64));
+		if (round > 40) return cs_fail_(CS_EDEVICE, "cs_index_build: prefix doubling did not converge");
+		hipLaunchKernelGGL((group_flag_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, grp.p, u, d_flag.p);
+		if (int rc = scan_flags(d_flag.p, d_pos.p, u, true)) return rc;
+		hipLaunchKernelGGL((round_keys_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, isfx.p, d_pos.p, d_rank.p, u, hstep, d_key.p);
+		if (int rc = sort_pairs(d_key, d_key2, isfx, isfx_s, u, 64)) return rc;
 		std::swap(d_key, d_key2); std::swap(isfx, isfx_s); // sorted keys / suffixes are now d_key2 / isfx_s as below
-		hipLaunchKernelGGL((round_heads_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, d_key2, u, d_head);
-		HIPB(scan_max(d_head, u));
-		hipLaunchKernelGGL((round_update_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, d_key2, slot, isfx_s, d_head, u, d_sfx2, d_rank, grp, d_flag);
-		HIPB(scan_flags(d_flag, d_pos, u, false));
+		hipLaunchKernelGGL((round_heads_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, d_key2.p, u, d_head.p);
+		if (int rc = scan_max(d_head.p, u)) return rc;
+		hipLaunchKernelGGL((round_update_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, d_key2.p, slot.p, isfx_s.p, d_head.p, u, d_sfx2.p, d_rank.p, grp.p, d_flag.p);
+		if (int rc = scan_flags(d_flag.p, d_pos.p, u, false)) return rc;
 		uint8_t lf = 0;
-		HIPB(hipMemcpyAsync(&last, d_pos + (u - 1), 8, hipMemcpyDeviceToHost, s));
-		HIPB(hipMemcpyAsync(&lf, d_flag + (u - 1), 1, hipMemcpyDeviceToHost, s));
-		HIPB(hipStreamSynchronize(s));
+		HIP_TRY(hipMemcpyAsync(&last, d_pos.p + (u - 1), 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(&lf, d_flag.p + (u - 1), 1, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
 		uint64_t u2 = last + lf;
-		if (u2) hipLaunchKernelGGL((compact_round_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, d_flag, d_pos, slot, isfx_s, grp, u, slot2, isfx2, grp2);
-		HIPB(hipStreamSynchronize(s));
+		if (u2) hipLaunchKernelGGL((compact_round_kernel<idx_t>), dim3(gridof(u)), dim3(256), 0, s, d_flag.p, d_pos.p, slot.p, isfx_s.p, grp.p, u, slot2.p, isfx2.p, grp2.p);
+		HIP_TRY(hipStreamSynchronize(s));
 		std::swap(slot, slot2); std::swap(isfx, isfx2); std::swap(grp, grp2);
 		u = u2; hstep <<= 1;
 		if (verbose) { fprintf(stderr, "[cs_index_build] round %d done, h = %llu, unresolved %llu\n", round, (unsigned long long)hstep, (unsigned long long)u); fflush(stderr); }
 	}
-	d_sa32 = d_sfx2;
-	for (void *p : {(void *)d_key, (void *)d_key2, (void *)d_head, (void *)d_rank, (void *)d_flag, (void *)d_pos, (void *)slot, (void *)isfx, (void *)grp,
-	                (void *)slot2, (void *)isfx2, (void *)grp2, (void *)isfx_s}) if (p) (void)hipFree(p);
-	d_key = d_key2 = d_pos = nullptr; d_head = d_rank = nullptr; d_flag = nullptr; slot = isfx = grp = slot2 = isfx2 = grp2 = isfx_s = nullptr;
+	// the suffix array is complete in d_sfx2; everything the doubling used goes back before BWT / Occ
+	const idx_t *d_sa32 = d_sfx2.p;
+	for (auto *b : {&d_key, &d_key2, &d_pos}) b->release();
+	for (auto *b : {&d_head, &d_rank, &slot, &isfx, &grp, &slot2, &isfx2, &grp2, &isfx_s}) b->release();
+	d_flag.release();
 
 	stage("suffix array complete");
 	// ---- BWT, Occ, SA samples
-	HIPB(hipMalloc((void **)&d_prim, 8));
-	hipLaunchKernelGGL((find_primary_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_sa32, m, d_prim);
-	HIPB(hipMemcpyAsync(&h_prim, d_prim, 8, hipMemcpyDeviceToHost, s));
-	HIPB(hipStreamSynchronize(s));
-	HIPB(hipMalloc((void **)&d_words, (n_words + 8) * 4));
-	hipLaunchKernelGGL((bwt_words_kernel<idx_t>), dim3(gridof(n_words)), dim3(256), 0, s, d_sa32, d_T, n, (uint64_t)h_prim, n_words, d_words);
-	HIPB(hipMalloc((void **)&d_cnt, 4 * (n_blocks + 1) * 8)); HIPB(hipMalloc((void **)&d_occ, 4 * (n_blocks + 1) * 8));
-	HIPB(hipMemsetAsync(d_cnt, 0, 4 * (n_blocks + 1) * 8, s));
-	hipLaunchKernelGGL(block_counts_kernel, dim3(gridof(n_blocks)), dim3(256), 0, s, d_words, n, n_blocks, d_cnt, d_cnt + (n_blocks + 1),
-	                   d_cnt + 2 * (n_blocks + 1), d_cnt + 3 * (n_blocks + 1));
+	if (int rc = d_prim.reserve(1)) return rc;
+	hipLaunchKernelGGL((find_primary_kernel<idx_t>), dim3(gridof(m)), dim3(256), 0, s, d_sa32, m, d_prim.p);
+	HIP_TRY(hipMemcpyAsync(&h_prim, d_prim.p, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	if (int rc = d_words.reserve(n_words + 8)) return rc;
+	hipLaunchKernelGGL((bwt_words_kernel<idx_t>), dim3(gridof(n_words)), dim3(256), 0, s, d_sa32, d_T.p, n, (uint64_t)h_prim, n_words, d_words.p);
+	for (auto *b : {&d_cnt, &d_occ}) if (int rc = b->reserve(4 * (n_blocks + 1))) return rc;
+	HIP_TRY(hipMemsetAsync(d_cnt.p, 0, 4 * (n_blocks + 1) * 8, s));
+	hipLaunchKernelGGL(block_counts_kernel, dim3(gridof(n_blocks)), dim3(256), 0, s, d_words.p, n, n_blocks, d_cnt.p, d_cnt.p + (n_blocks + 1),
+	                   d_cnt.p + 2 * (n_blocks + 1), d_cnt.p + 3 * (n_blocks + 1));
 	for (int c = 0; c < 4; ++c) {
 		size_t tb = 0;
-		uint64_t *in = d_cnt + c * (n_blocks + 1), *o = d_occ + c * (n_blocks + 1);
-		HIPB(rocprim::exclusive_scan(nullptr, tb, in, o, (uint64_t)0, (size_t)n_blocks + 1, rocprim::plus<uint64_t>(), s));
-		HIPB(need_tmp(tb));
-		HIPB(rocprim::exclusive_scan(d_tmp, tb, in, o, (uint64_t)0, (size_t)n_blocks + 1, rocprim::plus<uint64_t>(), s));
+		uint64_t *in = d_cnt.p + c * (n_blocks + 1), *o = d_occ.p + c * (n_blocks + 1);
+		HIP_TRY(rocprim::exclusive_scan(nullptr, tb, in, o, (uint64_t)0, (size_t)n_blocks + 1, rocprim::plus<uint64_t>(), s));
+		if (int rc = d_tmp.reserve(tb + 256)) return rc;
+		HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, in, o, (uint64_t)0, (size_t)n_blocks + 1, rocprim::plus<uint64_t>(), s));
 	}
-	HIPB(hipMalloc((void **)&d_bwt, (bwt_size + 16) * 4));
-	HIPB(hipMemsetAsync(d_bwt, 0, (bwt_size + 16) * 4, s));
+	if (int rc = d_bwt.reserve(bwt_size + 16)) return rc;
+	HIP_TRY(hipMemsetAsync(d_bwt.p, 0, (bwt_size + 16) * 4, s));
 	// note: a partial last block is followed immediately by the trailing record in the reference layout, so the
 	// record of block n_blocks starts at word n_words + 8*n_blocks, not at 16*n_blocks
-	hipLaunchKernelGGL(interleave_kernel, dim3(gridof(n_blocks + 1)), dim3(256), 0, s, d_words, n_words, n_blocks, d_occ, d_occ + (n_blocks + 1),
-	                   d_occ + 2 * (n_blocks + 1), d_occ + 3 * (n_blocks + 1), d_bwt);
-	HIPB(hipMalloc((void **)&d_sa, n_sa * 8));
-	hipLaunchKernelGGL((sa_sample_kernel<idx_t>), dim3(gridof(n_sa)), dim3(256), 0, s, d_sa32, m, 5u, n_sa, d_sa);
-	HIPB(hipGetLastError());
+	hipLaunchKernelGGL(interleave_kernel, dim3(gridof(n_blocks + 1)), dim3(256), 0, s, d_words.p, n_words, n_blocks, d_occ.p, d_occ.p + (n_blocks + 1),
+	                   d_occ.p + 2 * (n_blocks + 1), d_occ.p + 3 * (n_blocks + 1), d_bwt.p);
+	if (int rc = d_sa.reserve(n_sa)) return rc;
+	hipLaunchKernelGGL((sa_sample_kernel<idx_t>), dim3(gridof(n_sa)), dim3(256), 0, s, d_sa32, m, 5u, n_sa, d_sa.p);
+	HIP_TRY(hipGetLastError());
 
-	HIPB(hipStreamSynchronize(s));
+	HIP_TRY(hipStreamSynchronize(s));
 	stage("bwt/occ/sa kernels done");
-	ix = new cs_index();
+	std::unique_ptr<cs_index> ix(new cs_index());
 	memset(&ix->v, 0, sizeof ix->v);
 	ix->bwt.resize(bwt_size); ix->sa.resize(n_sa);
-	{
-		uint64_t tot[4];
-		for (int c = 0; c < 4; ++c) HIPB(hipMemcpyAsync(&tot[c], d_occ + c * (n_blocks + 1) + n_blocks, 8, hipMemcpyDeviceToHost, s));
-		// the trailing record sits right behind the last (possibly partial) block
-		uint64_t full_words = n_blocks * 16; // where interleave_kernel put it
-		HIPB(hipMemcpyAsync(ix->bwt.data(), d_bwt, std::min<uint64_t>(bwt_size, full_words) * 4, hipMemcpyDeviceToHost, s));
-		HIPB(hipMemcpyAsync(ix->sa.data(), d_sa, n_sa * 8, hipMemcpyDeviceToHost, s));
-		HIPB(hipStreamSynchronize(s));
-		uint64_t rec_at = n_words + 8 * n_blocks; // == bwt_size - 8
-		for (int c = 0; c < 4; ++c) { ix->bwt[rec_at + 2 * c] = (uint32_t)tot[c]; ix->bwt[rec_at + 2 * c + 1] = (uint32_t)(tot[c] >> 32); }
-		cs_index_view_t &v = ix->v;
-		v.primary = h_prim; v.L2[0] = 0;
-		for (int c = 0; c < 4; ++c) v.L2[c + 1] = v.L2[c] + tot[c];
-		v.seq_len = n; v.bwt_size = bwt_size; v.bwt = ix->bwt.data(); v.sa_intv = 32; v.n_sa = n_sa; v.sa = ix->sa.data();
-		if (v.L2[4] != n) { rc = cs_fail_(CS_EDEVICE, "cs_index_build: base counts do not add up"); goto done; }
-	}
-	*out = ix; ix = nullptr;
-done:
-	for (void *p : {(void *)d_fwd, (void *)d_T, d_tmp, (void *)d_key, (void *)d_key2, (void *)d_pos, (void *)d_sfx, (void *)d_sfx2, (void *)d_head,
-	                (void *)d_rank, (void *)d_flag, (void *)slot, (void *)isfx, (void *)grp, (void *)slot2, (void *)isfx2, (void *)grp2, (void *)isfx_s,
-	                (void *)d_prim, (void *)d_words, (void *)d_bwt, (void *)d_cnt, (void *)d_occ, (void *)d_sa}) if (p) (void)hipFree(p);
-	if (s) (void)hipStreamDestroy(s);
-	delete ix;
-	return rc;
+	uint64_t tot[4];
+	for (int c = 0; c < 4; ++c) HIP_TRY(hipMemcpyAsync(&tot[c], d_occ.p + c * (n_blocks + 1) + n_blocks, 8, hipMemcpyDeviceToHost, s));
+	// the trailing record sits right behind the last (possibly partial) block
+	uint64_t full_words = n_blocks * 16; // where interleave_kernel put it
+	HIP_TRY(hipMemcpyAsync(ix->bwt.data(), d_bwt.p, std::min<uint64_t>(bwt_size, full_words) * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(ix->sa.data(), d_sa.p, n_sa * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	uint64_t rec_at = n_words + 8 * n_blocks; // == bwt_size - 8
+	for (int c = 0; c < 4; ++c) { ix->bwt[rec_at + 2 * c] = (uint32_t)tot[c]; ix->bwt[rec_at + 2 * c + 1] = (uint32_t)(tot[c] >> 32); }
+	cs_index_view_t &v = ix->v;
+	v.primary = h_prim; v.L2[0] = 0;
+	for (int c = 0; c < 4; ++c) v.L2[c + 1] = v.L2[c] + tot[c];
+	v.seq_len = n; v.bwt_size = bwt_size; v.bwt = ix->bwt.data(); v.sa_intv = 32; v.n_sa = n_sa; v.sa = ix->sa.data();
+	if (v.L2[4] != n) return cs_fail_(CS_EDEVICE, "cs_index_build: base counts do not add up");
+	*out = ix.release();
+	return CS_OK;
 }
 
 extern "C" int cs_index_build(const uint8_t *fwd_nt4, uint64_t l_pac, int device, cs_index_t **out)

@@ -230,16 +230,15 @@ static int run_prim(cs_engine *e, int64_t n, const In *h_in, size_t in_per, Out 
 	if (!e || n < 0 || (n > 0 && (!h_in || !h_out))) return fail(CS_EINVAL, "bad argument");
 	if (n == 0) return CS_OK;
 	HIP_TRY(hipSetDevice(e->device));
-	In *d_in = nullptr; Out *d_out = nullptr; uint8_t *d_flag = nullptr;
-	HIP_TRY(hipMalloc((void **)&d_in, (size_t)n * in_per * sizeof(In)));
-	HIP_TRY(hipMalloc((void **)&d_out, (size_t)n * out_per * sizeof(Out)));
-	if (h_flag) { HIP_TRY(hipMalloc((void **)&d_flag, (size_t)n)); HIP_TRY(hipMemcpy(d_flag, h_flag, (size_t)n, hipMemcpyHostToDevice)); }
-	HIP_TRY(hipMemcpy(d_in, h_in, (size_t)n * in_per * sizeof(In), hipMemcpyHostToDevice));
-	launch(d_in, d_flag, d_out);
+	DevBuf<In> d_in; DevBuf<Out> d_out; DevBuf<uint8_t> d_flag;
+	CS_TRY(d_in.reserve((size_t)n * in_per));
+	CS_TRY(d_out.reserve((size_t)n * out_per));
+	if (h_flag) { CS_TRY(d_flag.reserve((size_t)n)); HIP_TRY(hipMemcpy(d_flag.p, h_flag, (size_t)n, hipMemcpyHostToDevice)); }
+	HIP_TRY(hipMemcpy(d_in.p, h_in, (size_t)n * in_per * sizeof(In), hipMemcpyHostToDevice));
+	launch(d_in.p, d_flag.p, d_out.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipStreamSynchronize(e->ctx[0]->stream));
-	HIP_TRY(hipMemcpy(h_out, d_out, (size_t)n * out_per * sizeof(Out), hipMemcpyDeviceToHost));
-	(void)hipFree(d_in); (void)hipFree(d_out); if (d_flag) (void)hipFree(d_flag);
+	HIP_TRY(hipMemcpy(h_out, d_out.p, (size_t)n * out_per * sizeof(Out), hipMemcpyDeviceToHost));
 	return CS_OK;
 }
 

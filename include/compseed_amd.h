@@ -418,7 +418,8 @@ int  cs_extend_batch(cs_extender_t *x, int64_t n_pairs, const cs_ext_pair_t *pai
 int  cs_extend_batch_device(cs_extender_t *x, int64_t n_pairs, const cs_ext_pair_t *d_pairs, const uint8_t *d_qbuf, uint64_t q_bytes,
                             const uint8_t *d_tbuf, uint64_t t_bytes, int32_t w, cs_ext_result_t *d_out);
 int  cs_extender_stats(const cs_extender_t *x, cs_ext_stats_t *st);
-/* the band retries extend the same sequences again with another pair list: upload the two buffers once, then run pair lists against them */
+/* the band retries extend the same sequences again with another pair list: upload the two buffers once, then run pair lists against them.
+ * cs_extend_batch leaves its own two buffers resident in the same way, so a resident call always runs against the sequences of the last host-form call. */
 int  cs_extender_upload(cs_extender_t *x, const uint8_t *qbuf, uint64_t q_bytes, const uint8_t *tbuf, uint64_t t_bytes);
 int  cs_extend_batch_resident(cs_extender_t *x, int64_t n_pairs, const cs_ext_pair_t *pairs, int32_t w, cs_ext_result_t *out);
 

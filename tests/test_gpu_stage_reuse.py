@@ -3,15 +3,18 @@ grow), an empty batch, the smallest run, a call the checking kernels refuse with
 (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip) keep their state -- stream, events, pinned counters, grow-only buffers -- in one shared
 layer (compseed_amd/csrc/dev_stage.hpp); after every step each stage's result must be, byte for byte, what freshly created handles return
 for the same input and what the host calls cs_chain_batch / cs_chain_filter return, for the host-array forms and for the *_device forms
-chained on the device.  Then the handles close, and so does a chainer whose filter state was never made."""
+chained on the device.  Then the handles close, and so does a chainer whose filter state was never made.  The fourth stage on that layer,
+the Extender (extend.hip), goes through a sequence of its own: its three host forms and the device form on one handle."""
 import functools
 
 import numpy as np
 import pytest
 
 import _data
+import _oracle
 from test_chain import golden_chains
 from test_gpu_chain_device import _cp, _golden_in
+from test_gpu_extend import TRACES, _random_pairs
 from test_gpu_extend_chains_device import Dev, _same_regs
 
 pytestmark = pytest.mark.gpu
@@ -186,4 +189,109 @@ def test_a_chainer_without_filter_state_closes():
     chainer.close()
     assert not chainer._h
     never_used = ca.Chainer(_data.PREFIX, device=0)
+    never_used.close()
+
+
+EXT_BIG, EXT_OTHER = "indel150.default", "sorted150.default"   # the recorded run with the most pairs and the most sequence bytes; one with other buffer sizes
+
+
+def _ext_pairs(pairs):
+    import compseed_amd as ca
+    pr = np.zeros(pairs.size, dtype=ca.EXT_PAIR_DT)
+    for f in ("q_off", "t_off", "qlen", "tlen", "h0"):
+        pr[f] = pairs[f]
+    return pr
+
+
+def _ext_oracle(pairs, qbuf, tbuf, w):
+    """the oracle under mem_opt_init's scoring (what Extender(0) computes) at band w"""
+    import compseed_amd as ca
+    P = ca.ExtParams()
+    meta = np.tile(np.array([[0, w, P.zdrop, P.end_bonus, P.o_del, P.e_del, P.o_ins, P.e_ins] + [0] * 9], dtype=np.int32), (pairs.size, 1))
+    fx = dict(mat=np.array(list(P.mat), dtype=np.int8), pairs=pairs, qbuf=qbuf, tbuf=tbuf, meta=meta)
+    return _oracle.bsw_extend(fx, threads=8).astype(ca.EXT_RES_DT)
+
+
+def _mixed_batch():
+    """40 pairs of 1..300 columns (either side of the 160 columns the lane kernel takes) and three of 9,000..12,000 (beyond what the
+    wave-per-pair kernel keeps in LDS: the band state goes to HBM)"""
+    rng = np.random.default_rng(20)
+    p0, q0, t0 = _random_pairs(rng, 40, 1, 300)
+    p1, q1, t1 = _random_pairs(rng, 3, 9000, 12000)
+    p1["q_off"] += q0.size; p1["t_off"] += t0.size
+    pairs = np.concatenate([p0, p1])
+    assert (pairs["qlen"] <= 160).any() and ((pairs["qlen"] > 160) & (pairs["qlen"] <= 300)).any() and (pairs["qlen"] >= 9000).sum() == 3
+    return pairs, np.concatenate([q0, q1]), np.concatenate([t0, t1])
+
+
+def test_the_extender_on_a_reused_handle(eng):
+    """One Extender through: the biggest recorded run (the buffers grow), an empty batch, a small mixed batch whose three long queries bring
+    the HBM band state onto a used handle, a batch with four bad pairs (CS_EINVAL, the others delivered, the bad ones zero), an upload and
+    three resident pair lists (all pairs at w = 100, fifty at w = 13, all again), another run through extend() and then extend_resident()
+    with NO upload in between, the device form, close.  Every result is, byte for byte, what a fresh Extender's extend() returns for the same
+    input and what the recorded run or the oracle says.  The resident call without an upload pins the rule that a host-form call leaves
+    its sequences resident (include/compseed_amd.h): it must run against the second run's buffers and their sizes, not the uploaded ones."""
+    import compseed_amd as ca
+    big, other = _oracle.bsw_fixture(EXT_BIG), _oracle.bsw_fixture(EXT_OTHER)
+    assert all(big[k].size > _oracle.bsw_fixture(tag)[k].size for tag in TRACES if tag != EXT_BIG for k in ("pairs", "qbuf", "tbuf"))
+    pr_big, pr_other = _ext_pairs(big["pairs"]), _ext_pairs(other["pairs"])
+    want_big, want_other = big["want"].astype(ca.EXT_RES_DT), other["want"].astype(ca.EXT_RES_DT)
+    x = ca.Extender(0)
+    delivered = 0
+
+    def step(what, call, args, want, fresh_args=None):
+        """call(handle, *args) on the reused handle against extend(*fresh_args or args) on a fresh one, and against `want`"""
+        nonlocal delivered
+        got = call(x, *args)
+        fresh = ca.Extender(0)
+        ref = fresh.extend(*(fresh_args or args))
+        fresh.close()
+        assert got.dtype == ref.dtype and got.tobytes() == ref.tobytes(), (what, "reused handle against a fresh one")
+        assert np.array_equal(got, want), (what, int((got != want).sum()))
+        delivered += got.size
+
+    host = ca.Extender.extend
+    resident = ca.Extender.extend_resident
+    step("big host batch", host, (pr_big, big["qbuf"], big["tbuf"], 100), want_big)
+    step("empty batch", host, (pr_big[:0], big["qbuf"], big["tbuf"], 100), want_big[:0])
+    mixed, mq, mt = _mixed_batch()
+    step("small mixed batch", host, (_ext_pairs(mixed), mq, mt, 100), _ext_oracle(mixed, mq, mt, 100))
+    # the refused call of test_gpu_extend.test_device_variant_and_errors
+    bad = pr_other[:50].copy()
+    bad["q_off"][3] = other["qbuf"].size; bad["qlen"][7] = 0; bad["tlen"][11] = -1; bad["t_off"][13] = 2**40
+    ok = np.ones(50, bool); ok[[3, 7, 11, 13]] = False
+    fresh, outs = ca.Extender(0), []
+    for h in (x, fresh):
+        with pytest.raises(ca.CSError) as ei:
+            h.extend(bad, other["qbuf"], other["tbuf"], 100)
+        assert ei.value.code == -1 and "4 pair(s)" in str(ei.value)
+        outs.append(h.last_out)
+    fresh.close()
+    assert outs[0].tobytes() == outs[1].tobytes(), "refused batch: reused handle against a fresh one"
+    assert np.array_equal(outs[0][ok], want_other[:50][ok]) and (outs[0][~ok].view(np.int32) == 0).all()
+    delivered += 50
+    # upload, then three pair lists against the resident sequences
+    x.upload(big["qbuf"], big["tbuf"])
+    sub = np.arange(7, pr_big.size, pr_big.size // 50)[:50]
+    want_sub = _ext_oracle(big["pairs"][sub], big["qbuf"], big["tbuf"], 13)
+    step("resident, all pairs", resident, (pr_big, 100), want_big, (pr_big, big["qbuf"], big["tbuf"], 100))
+    step("resident, 50 pairs at w = 13", resident, (pr_big[sub], 13), want_sub, (pr_big[sub], big["qbuf"], big["tbuf"], 13))
+    step("resident, all pairs again", resident, (pr_big, 100), want_big, (pr_big, big["qbuf"], big["tbuf"], 100))
+    # another run through the host form, then resident without an upload: the host form's sequences are the resident ones
+    step("other host batch", host, (pr_other, other["qbuf"], other["tbuf"], 100), want_other)
+    step("resident after a host batch, no upload", resident, (pr_other, 100), want_other, (pr_other, other["qbuf"], other["tbuf"], 100))
+    # the device form on the same handle, the caller's arrays
+    n = pr_big.size
+    d_p, d_q, d_t, d_o = eng.alloc(pr_big.nbytes), eng.alloc(big["qbuf"].size), eng.alloc(big["tbuf"].size), eng.alloc(n * 24)
+    eng.upload(d_p, pr_big); eng.upload(d_q, big["qbuf"]); eng.upload(d_t, big["tbuf"])
+    x.extend_device(d_p, n, d_q, big["qbuf"].size, d_t, big["tbuf"].size, d_o, 100)
+    got = eng.download(d_o, ca.EXT_RES_DT, n)
+    for d in (d_p, d_q, d_t, d_o):
+        eng.free(d)
+    assert np.array_equal(got, want_big), "device form"
+    delivered += n
+    assert x.stats()["pairs"] == delivered == 4 * pr_big.size + 2 * pr_other.size + 43 + 50 + 50   # (the refused batch counts: its other results were delivered)
+    x.close()
+    assert not x.h
+    never_used = ca.Extender(0)
     never_used.close()
