@@ -153,6 +153,14 @@ struct OutMem { uint64_t x0, x1, x2, info; };   // == cs_intv_t / bwtintv_t
 struct OutSeed { int64_t rbeg; int32_t qbeg, len; }; // == cs_seed_t
 // SA slots a mem with x2 occurrences asks for (comp_seed.cpp:2313-2325)
 __device__ __forceinline__ uint32_t sal_slots(uint64_t x2, uint32_t max_occ) { return x2 < max_occ ? (uint32_t)x2 : max_occ; }
+// A RAW mem (the per-read lists the SMEM stage appends to, PassCtx::d_out, and the overflow records) may carry its text position where a
+// sorted mem carries x2: a mem with x2 == 1 needs one bit of that word, and the kernel that emits it often holds P = SA[x0] in a register.
+// Bit 63 set: x2 is 1 and bits 0..39 are P (counts and positions are below 2^37: engine creation refuses a longer index).  The tag is an
+// optimisation only -- an untagged unique mem is as good everywhere -- and it never leaves the sort: every reader of raw records
+// decodes, and mems[] holds a plain x2 = 1.
+constexpr uint64_t MEM_POS_TAG = 1ull << 63, MEM_POS_MASK = (1ull << 40) - 1ull;
+__device__ __forceinline__ uint64_t mem_x2(uint64_t w) { return (w & MEM_POS_TAG) ? 1ull : w; }   // x2 of a raw x2 word
+__device__ __forceinline__ uint64_t mem_pos(uint64_t w) { return w & MEM_POS_MASK; }             // P of a tagged one
 struct BTask { uint32_t r; uint16_t x, mi_kind, n, ret; uint32_t cls; };  // 16 bytes, stored at the forward task's slot;
                                                                            // cls = size class 0..3, 0xffffffff = no call
 struct OvfRec { OutMem m; uint32_t r, pad; };                              // a mem beyond a read's first `cap`

@@ -273,7 +273,7 @@ static SplitArgs split_args(const cs_engine *e, PassCtx *c, const cs_params_t *p
 	A.jump = e->jump_k ? e->d_jump.p : nullptr; A.jump_k = e->jump_k;
 	A.evc = c->d_evc.p; A.seq = c->d_seq.p; A.sst2 = c->d_sst2.p;
 	A.fq_cap = fq_cap; A.n_f_next = C + SC_NEXT_N; A.n_btasks = C + SC_BTASKS; A.n_text_sweeps = C + SC_TEXT_SWEEPS; A.n_r2_quick = C + SC_R2_TEXT;
-	A.text_sweep = (dis & CS_DISABLE_TEXT_SWEEP) ? 0 : 1;
+	A.text_sweep = ((dis & CS_DISABLE_TEXT_SWEEP) ? 0 : TS_SWEEP) | ((dis & CS_DISABLE_MEM_POS) ? 0 : TS_MEM_POS); // (sst_mode 0: dis = ~0, both off)
 	// window scheme for the backward sweeps (smem_bwd.hpp, bwd_win_run): needs the jump table and jump_k <= min_seed_len <= jump_k + 4
 	A.win = !(dis & CS_DISABLE_WINDOW) && par->sst_mode != 0 && A.jump && A.jump_k <= A.min_seed_len && A.min_seed_len - 1 <= WIN_LANES ? 1 : 0;
 	A.bloom = nullptr; A.bloom_bits = 0;

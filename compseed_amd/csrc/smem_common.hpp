@@ -63,7 +63,8 @@ struct SplitArgs {
 	unsigned long long *n_r2_quick;                   // re-seeding calls settled by fwd0_kernel itself (counted with r2text_kernel's)
 	const uint64_t *bloom; uint32_t bloom_bits;       // k-mer filter of the text for k = min_seed_len (kmer_filter_*), or null
 	int32_t   win;                                    // window scheme for the backward sweeps (bwd_win_run) is on
-	int32_t   text_sweep;                             // that shortcut is enabled (CS_TEXT_SWEEP, default on)
+	int32_t   text_sweep;                             // bit 0 (TS_SWEEP): that shortcut is enabled (CS_DISABLE_TEXT_SWEEP off); bit 1 (TS_MEM_POS): unique mems
+	                                                  // and re-seeding side words carry the text position (CS_DISABLE_MEM_POS off).  One field: DESIGN.md 4.3
 	unsigned long long *n_btasks;                     // backward calls created by this forward launch (0: the backward kernels return at once)
 	uint64_t *aux_next;                               // side word of fq_next[slot] for re-seeding calls (r2text_kernel), or null
 	BTask    *bq;                                     // backward task of forward task t: bq[t] (no atomics: 1:1)
@@ -78,9 +79,18 @@ struct SplitArgs {
 	unsigned long long *evc;                          // byte-model event counters [N_KID][N_EV] (fm_device.hpp), or null
 };
 
-__device__ __forceinline__ void emit_mem(const SplitArgs &A, uint32_t r, const Intv &v, uint32_t beg, uint32_t end)
+constexpr int32_t TS_SWEEP = 1, TS_MEM_POS = 2; // SplitArgs::text_sweep
+constexpr uint64_t FTASK_NONE = ~0ull; // kind bits = TK_NOP
+constexpr uint64_t AUX_NONE = ~0ull, POS_NONE = ~0ull;
+// side word of a re-seeding call (emit_smem): bit 54 set = bits 0..36 hold the SMEM's text position, not its x0
+constexpr uint64_t AUX_POS = 1ull << 54, AUX_LOW = (1ull << 37) - 1ull;
+// Appends a mem to read r's raw list.  pos: the text position of the mem's first base where the caller holds it (it must be SA[v.x0]
+// exactly), else POS_NONE.  A unique mem with a position is stored tagged (fm_device.hpp, MEM_POS_TAG): the sort and r3text_kernel then take
+// P from the record instead of reading the suffix array again.  The slot count is that of x2 = 1 either way.
+__device__ __forceinline__ void emit_mem(const SplitArgs &A, uint32_t r, const Intv &v, uint32_t beg, uint32_t end, uint64_t pos = POS_NONE)
 {
 	OutMem m = {v.x0, v.x1, v.x2, (uint64_t)beg << 32 | end};
+	if (v.x2 == 1 && pos != POS_NONE && (A.text_sweep & TS_MEM_POS)) m.x2 = MEM_POS_TAG | pos;
 	uint32_t k = atomicAdd(&A.out_cnt[r], 1u);
 	if (A.out_scnt) atomicAdd(&A.out_scnt[r], sal_slots(v.x2, A.max_occ)); // (nothing waits for it: no return value)
 	if (k < A.cap) A.out[(size_t)r * A.cap + k] = m;
@@ -94,19 +104,22 @@ __device__ __forceinline__ void push_ftask(const SplitArgs &A, uint64_t t, uint6
 	unsigned long long s = atomicAdd(A.n_f_next, 1ull);
 	if (s < A.fq_cap) { A.fq_next[s] = t; if (aux != ~0ull) A.aux_next[s] = aux; } else atomicMax(A.err, 2ull);
 }
-constexpr uint64_t FTASK_NONE = ~0ull; // kind bits = TK_NOP
-constexpr uint64_t AUX_NONE = ~0ull, POS_NONE = ~0ull;
 // an SMEM of a round-1/2 call: length filter (bwamem.c:232,246); returns the re-seeding call a round-1 SMEM triggers
 // (bwamem.c:241-249) or FTASK_NONE.  aux: for the re-seeding call of a UNIQUE SMEM (min_intv 2), what r2text_kernel needs
-// to find the SMEM in the text: x0 | beg << 37 | parity(beg + end) << 53.
-__device__ __forceinline__ uint64_t emit_smem(const SplitArgs &A, uint32_t r, uint32_t kind, const Intv &v, int beg, uint32_t end, uint64_t &aux)
+// to find the SMEM in the text: x0 | beg << 37 | parity(beg + end) << 53 -- or, where the caller holds the SMEM's text position
+// (pos, as for emit_mem), that position in the place of x0 and AUX_POS set: r2text_kernel then starts without its suffix-array read.
+// (Bits 55..63 stay clear, so no side word equals AUX_NONE.)
+__device__ __forceinline__ uint64_t emit_smem(const SplitArgs &A, uint32_t r, uint32_t kind, const Intv &v, int beg, uint32_t end, uint64_t &aux, uint64_t pos = POS_NONE)
 {
 	int len = (int)end - beg;
 	aux = AUX_NONE;
 	if (len < A.min_seed_len) return FTASK_NONE;
-	emit_mem(A, r, v, (uint32_t)beg, end);
+	emit_mem(A, r, v, (uint32_t)beg, end, pos);
 	if (kind == TK_ROUND1 && len >= A.split_len && v.x2 <= A.split_width) {
-		if (v.x2 == 1 && A.aux_next) aux = v.x0 | (uint64_t)beg << 37 | (uint64_t)(((uint32_t)beg + end) & 1u) << 53;
+		if (v.x2 == 1 && A.aux_next) {
+			const bool have = pos != POS_NONE && (A.text_sweep & TS_MEM_POS);
+			aux = (have ? pos | AUX_POS : v.x0) | (uint64_t)beg << 37 | (uint64_t)(((uint32_t)beg + end) & 1u) << 53;
+		}
 		return ftask_pack(r, (uint32_t)(beg + (int)end) >> 1, (uint32_t)v.x2 + 1, TK_ROUND2);
 	}
 	return FTASK_NONE;

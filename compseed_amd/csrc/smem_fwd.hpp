@@ -97,20 +97,22 @@ __global__ __launch_bounds__(BLOCK, 6) void fwd_kernel(const SplitArgs A)
 		uint64_t push0 = FTASK_NONE, push1 = FTASK_NONE, aux0 = AUX_NONE; // forward tasks this lane spawns in this step
 		if (active) {
 			bool fin = false; // the forward pass of an SMEM call ends in this iteration with ik = [x, i)
+			uint64_t fpos = POS_NONE; // text position of read base x, where the match ended in text mode (as in fwd0_kernel)
 			if (kind == TK_TEXT) {
 				uint64_t tpos = ik.x1;
 				fin = text_step(ix, rd, i, tpos, my_q, my_hits, W);        // up to 32 bases against the text
 				ik.x1 = tpos;
 				if (fin) {
+					fpos = tpos - (uint64_t)(i - x);
 					ik.x1 = isa_direct(ix, ix.seq_len - tpos); kind = TK_ROUND1; // rank of the reverse complement of [x, i)
 					wc_add(W, EV_ISA);
 					// The sweep of this call cannot pass the previous pivot x - dprev (chain_round1), and while the unique
 					// match keeps agreeing with the text in front of it, it stays the longest survivor and nothing else is
 					// reported (bwt.c:328-336).  So if the dprev - 1 bases between the pivots agree, the whole sweep reports
 					// exactly one SMEM, [x - dprev + 1, i), and its bi-interval comes from the inverse suffix array.
-					if (dprev > 0 && A.text_sweep) {
+					if (dprev > 0 && (A.text_sweep & TS_SWEEP)) {
 						const int nb = (int)dprev - 1;
-						const uint64_t px = tpos - (uint64_t)(i - x); // text position of read base x
+						const uint64_t px = fpos;
 						bool same = px >= (uint64_t)nb;
 						for (int done = 0; same && done < nb;) { // read [x - nb, x) against the text in front of px, a record at a time
 							const int p = x - nb + done;
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(BLOCK, 6) void fwd_kernel(const SplitArgs A)
 						}
 						if (same) {
 							Intv m = {isa_direct(ix, px - (uint64_t)nb), ik.x1, 1}; wc_add(W, EV_ISA);
-							push0 = emit_smem(A, r, TK_ROUND1, m, x - nb, (uint32_t)i, aux0);
+							push0 = emit_smem(A, r, TK_ROUND1, m, x - nb, (uint32_t)i, aux0, px - (uint64_t)nb); // (m.x0 is the rank of that position)
 							push1 = chain_round1(rd, r, len, i, x);
 							++my_sw; active = false; fin = false;
 						}
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(BLOCK, 6) void fwd_kernel(const SplitArgs A)
 				// A call at pivot 0 has a trivial backward sweep (bwt.c:325 starts at i = -1): its only SMEM is the longest
 				// forward match, so it needs no LEP list, no backward task, and finishes right here.
 				if (x == 0) {
-					push0 = emit_smem(A, r, kind, ik, 0, (uint32_t)i, aux0);
+					push0 = emit_smem(A, r, kind, ik, 0, (uint32_t)i, aux0, fpos); // (fpos: a call that ended in text mode; ik.x0 has not moved since SA[ik.x0] was read)
 					if (kind == TK_ROUND1) push1 = chain_round1(rd, r, len, i, x);
 				} else { // hand the list to the backward kernel of its size class; ret = end of the longest match = next pivot
 					if (!A.win || i - x >= A.min_seed_len) { lep[n++] = pack_lep(ik, (uint32_t)i); wc_add(W, EV_LEP); }
@@ -262,7 +264,7 @@ __global__ __launch_bounds__(BLOCK, 8) void fwd0_kernel(const SplitArgs A, uint6
 				}
 			}
 			if (fin) { // the call's only SMEM is its longest forward match (bwt.c:325 starts the sweep at -1)
-				push0 = emit_smem(A, r, TK_ROUND1, ik, 0, (uint32_t)i, aux0);
+				push0 = emit_smem(A, r, TK_ROUND1, ik, 0, (uint32_t)i, aux0, fpos);
 				if (push0 != FTASK_NONE && aux0 != AUX_NONE && fpos != POS_NONE && ix.rep) { // its re-seeding call, if rep[] settles it right here
 					uint32_t nw = 0; const int pv = i >> 1;                                    // (emit_smem: pivot = (beg + end) / 2, beg = 0)
 					if (A.min_seed_len >= 2 && fpos + (uint64_t)i <= ix.seq_len && pv <= 4096 && r2_quick_rep(ix, fpos, i, pv, A.min_seed_len, nw) == 0) { push0 = FTASK_NONE; ++my_r2; }

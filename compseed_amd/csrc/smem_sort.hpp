@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void sort_compact_wave_kernel(const OutMem *ra
 		for (uint32_t a0 = 0; a0 < n; a0 += 64) {
 			const uint32_t a = a0 + lane;
 			OutMem ma = {0, 0, 0, ~0ull};
-			if (a < n) ma = mem_at(src, cap, ovf, ovf_idx, olo, a);
+			if (a < n) { ma = mem_at(src, cap, ovf, ovf_idx, olo, a); ma.x2 = mem_x2(ma.x2); } // (a raw record may be tagged: fm_device.hpp)
 			uint32_t rank = 0;
 			for (uint32_t b0 = 0; b0 < n; b0 += 64) {
 				const uint32_t b = b0 + lane;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void sort_compact16_kernel(const OutMem *raw, 
 	for (int s = 0; s < 4; ++s) {
 		uint32_t e = a + 16u * s;
 		key[s] = ~0ull;
-		if (e < n) { m[s] = src[e]; key[s] = m[s].info; }
+		if (e < n) { m[s] = src[e]; m[s].x2 = mem_x2(m[s].x2); key[s] = m[s].info; } // (a raw record may be tagged: fm_device.hpp)
 	}
 	const int rounds = n > 48 ? 4 : n > 32 ? 3 : n > 16 ? 2 : 1; // group-uniform
 	for (int sb = 0; sb < rounds; ++sb) {
@@ -106,6 +106,14 @@ __device__ __forceinline__ void put_seed(const DevIndex &ix, OutSeed *seeds, uin
 	OutSeed s = {(int64_t)sa_direct(ix, slot), qb, ln};
 	seeds[at] = s;
 }
+// The seed of a unique mem whose raw record carried its text position (fm_device.hpp, MEM_POS_TAG): the emitting kernel held P = SA[x0], so
+// the seed's rbeg is written from the record and the random 8-byte gather above -- what this kernel's time is made of -- does not happen.
+__device__ __forceinline__ void put_seed_pos(OutSeed *seeds, uint64_t at, uint64_t end, uint64_t pos, int32_t qb, int32_t ln)
+{
+	if (at >= end) return;
+	OutSeed s = {(int64_t)pos, qb, ln};
+	seeds[at] = s;
+}
 
 // x / d for x < 2^48 and d <= 2^16, by long division in 16-bit limbs: three 32-bit divisions where the 64-bit one costs the kernels
 // below twenty registers.  (An occurrence count is below 2^37: engine creation refuses a longer index; max_occ <= 1024 on this path.)
@@ -121,6 +129,8 @@ __device__ __forceinline__ uint64_t div48_16(uint64_t x, uint32_t d)
 // which is min(x2, max_occ) for either value of `step`) to their ranks in a 64-entry LDS strip per 16-lane group, where lane a sums entries
 // 4a .. 4a+3 and a 16-lane shuffle scan makes the exclusive prefix in rank order; every mem expanded at seed_off[r] + prefix with
 // sal_expand_kernel's arithmetic.  Up to SAL_LIGHT slots: by the lane that holds the mem; more: by the 16 lanes of the group, 16 slots per step.
+// m[s].x2 stays the RAW word from the load to the expansion (fm_device.hpp, MEM_POS_TAG): everything that wants x2 (sal_slots, step, the
+// `bad` check through the slot counts, mems[]) sees mem_x2() of it, and a tagged mem's one seed is put_seed_pos, not put_seed.
 __global__ __launch_bounds__(256, 8) void sort_expand16_kernel(const DevIndex ix, const OutMem *raw, const uint32_t *cnt, uint32_t cap, const uint64_t *mem_off,
                                                             const uint64_t *seed_off, int64_t n_reads, OutMem *mems, OutSeed *seeds, uint32_t max_occ, unsigned long long *bad)
 {
@@ -150,11 +160,11 @@ __global__ __launch_bounds__(256, 8) void sort_expand16_kernel(const DevIndex ix
 	}
 	uint32_t *my = reinterpret_cast<uint32_t *>(strip[threadIdx.x >> 4]);
 #pragma unroll
-	for (int s = 0; s < 4; ++s) if (a + 16u * s < n) my[rank[s]] = sal_slots(m[s].x2, max_occ); // (a read's ranks are a permutation of 0 .. n-1)
+	for (int s = 0; s < 4; ++s) if (a + 16u * s < n) my[rank[s]] = sal_slots(mem_x2(m[s].x2), max_occ); // (a read's ranks are a permutation of 0 .. n-1)
 	if (n) {
 		OutMem *dst = mems + mem_off[r];
 #pragma unroll
-		for (int s = 0; s < 4; ++s) if (a + 16u * s < n) dst[rank[s]] = m[s];
+		for (int s = 0; s < 4; ++s) if (a + 16u * s < n) { OutMem o = m[s]; o.x2 = mem_x2(o.x2); dst[rank[s]] = o; } // (no tag leaves the sort)
 	}
 	__syncthreads(); // (every thread of the block gets here: nothing above returns)
 	uint32_t total;
@@ -179,12 +189,13 @@ __global__ __launch_bounds__(256, 8) void sort_expand16_kernel(const DevIndex ix
 #pragma unroll 1
 	for (int s = 0; s < rounds; ++s) { // group-uniform
 		const bool have = a + 16u * s < n;
-		const uint64_t x2 = m[0].x2;
+		const uint64_t x2w = m[0].x2, x2 = mem_x2(x2w); // (m[].x2 holds the raw word through the sort: no register beside it)
 		const uint32_t cv = have ? sal_slots(x2, max_occ) : 0;
 		const uint64_t step = x2 > max_occ ? div48_16(x2, max_occ) : 1; // comp_seed.cpp:2313-2325: slots x0 + k * step
 		const uint64_t first = sbase + (have ? my[rank[0]] : 0u);
 		const int32_t qb = (int32_t)(m[0].info >> 32), ln = (int32_t)(uint32_t)m[0].info - qb;
-		if (cv <= SAL_LIGHT)
+		if (x2w & MEM_POS_TAG) { if (cv) put_seed_pos(seeds, first, send, mem_pos(x2w), qb, ln); } // its one seed, without the gather
+		else if (cv <= SAL_LIGHT)
 			for (uint32_t c = 0; c < cv; ++c) put_seed(ix, seeds, first + c, send, m[0].x0 + (uint64_t)c * step, qb, ln);
 		uint32_t heavy = (uint32_t)(__ballot(cv > SAL_LIGHT) >> gbase) & 0xffffu; // this group's lanes
 		while (heavy) { // group-uniform; the shuffles stay inside the group

@@ -65,13 +65,15 @@ __device__ __forceinline__ bool text_interval(const DevIndex &ix, uint64_t pos, 
 	return true;
 }
 // (r2_quick_rep, smem_common.hpp, is the test on rep[] itself: fwd0_kernel asks it too.)  0: answered; 1: needs the sweep; 2: the text cannot tell.
-__device__ __forceinline__ int r2_quick(const SplitArgs &A, uint64_t x0, int beg, int end, int pivot, uint64_t &P, LaneCtr &C)
+// a: the call's side word (emit_smem).  With AUX_POS its low bits ARE the SMEM's text position and the chain task -> aux -> rep[] has no
+// suffix-array read in it; otherwise they are x0 and P = SA[x0] as before.
+__device__ __forceinline__ int r2_quick(const SplitArgs &A, uint64_t a, int beg, int end, int pivot, uint64_t &P, LaneCtr &C)
 {
 	const DevIndex &ix = A.ix;
 	const int len = end - beg, po = pivot - beg, k = A.min_seed_len;
 	if (k < 2 || po > 4096) return 2;
-	P = sa_direct(ix, x0);
-	++C.sa;
+	if (a & AUX_POS) P = a & AUX_LOW;
+	else { P = sa_direct(ix, a & AUX_LOW); ++C.sa; }
 	if (P >= ix.seq_len || P + (uint64_t)len > ix.seq_len) return 2; // (an SMEM lies inside the text)
 	uint32_t nw = 0;
 	const int q = r2_quick_rep(ix, P, len, po, k, nw);
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(256, CS_R2_WAVES) void r2text_kernel(const SplitArg
 				const uint64_t a = aux[t];
 				const int pivot = (int)((task[j] >> 32) & 0xffffu);
 				const int beg = (int)((a >> 37) & 0xffffu), end = 2 * pivot + (int)((a >> 53) & 1u) - beg;
-				const int q = r2_quick(A, a & ((1ull << 37) - 1ull), beg, end, pivot, P, C);
+				const int q = r2_quick(A, a, beg, end, pivot, P, C);
 				if (q == 0) { task[j] = FTASK_NONE; ++done; } else if (q == 1) slow = true; else ++left;
 			}
 			const uint64_t sm = __ballot(slow);
@@ -287,9 +289,13 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 			if (a < nm0) { const uint64_t info = mine[a].info; mreg[a] = (uint32_t)(info >> 32) << 16 | ((uint32_t)info & 0xffffu); }
 		}
 		C.mem += nm0 < R3_REG ? nm0 : R3_REG;
-		auto pos_of = [&](int best) -> uint64_t { // text position of mem `best`
+		// text position of mem `best`.  Its x2 word is loaded with x0, two loads in one round trip: a tagged mem (fm_device.hpp, MEM_POS_TAG)
+		// brings the position, and only an untagged one costs the dependent trip mem record -> x0 -> SA
+		auto pos_of = [&](int best) -> uint64_t {
+			const uint64_t x0 = mine[best].x0, w = mine[best].x2;
+			if (w & MEM_POS_TAG) return mem_pos(w);
 			++C.sa;
-			return sa_direct(ix, mine[best].x0);
+			return sa_direct(ix, x0);
 		};
 		uint32_t next_slot = cs; // complete reads: the next free slot of the read's list
 		int cb = 0, ce = 0; uint64_t cp = 0; // the mem the cursor is in: [cb, ce) at text position cp
@@ -316,8 +322,10 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 			return atomicAdd(&A.out_cnt[r], n);
 		};
 		uint32_t my_slots = 0; // SA slots of the seeds this lane emits for the read: one add where the count is stored
-		auto put = [&](uint32_t kk, const OutMem &m) {
+		// pos: the seed's text position where it is unique and was taken from the text (it is SA[m.x0]: m.x0 is that position's rank), as for emit_mem
+		auto put = [&](uint32_t kk, OutMem m, uint64_t pos = POS_NONE) {
 			my_slots += sal_slots(m.x2, A.max_occ);
+			if (m.x2 == 1 && pos != POS_NONE && (A.text_sweep & TS_MEM_POS)) m.x2 = MEM_POS_TAG | pos;
 			if (kk < A.cap) A.out[(size_t)r * A.cap + kk] = m;
 			else {
 				unsigned long long sl = atomicAdd(A.ovf_cnt, 1ull);
@@ -383,7 +391,7 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 					for (int j = 0; j < SPEC; ++j) {
 						if (j < nu) {
 							OutMem m = {a0[j], a1[j], 1, (uint64_t)(uint32_t)(x + j * k1) << 32 | (uint32_t)(x + (j + 1) * k1)};
-							put(k0 + (uint32_t)j, m);
+							put(k0 + (uint32_t)j, m, p + (uint64_t)(j * k1));
 						}
 					}
 					my_q += (unsigned)(nu * (k1 - 1)); my_hits += (unsigned)(nu * (k1 - 1)); my_text += (unsigned)nu;

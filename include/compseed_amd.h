@@ -77,6 +77,9 @@ typedef struct {
 #define CS_DISABLE_FWD0         0x40u  /* separate lean kernel for the calls at the first base of each read                   */
 #define CS_DISABLE_FUSED_SAL    0x80u  /* sort and SAL in one pass over the mems, a read's SA slots counted while its mems are
                                         * emitted (max_occ <= 1024); off: the sort, a scan over the mems, then the SAL kernels   */
+#define CS_DISABLE_MEM_POS      0x100u /* a unique mem's text position kept in the spare bits of its raw record, and in the side
+                                        * word of its re-seeding call, where the emitting kernel holds it; off: the suffix array
+                                        * is read again for it (sst_mode 0 implies it)                                           */
 
 /* engine construction options: which derived arrays are materialised in HBM and how the working buffers are sized.
  * cs_engine_options_default() fills the defaults (in brackets).  Everything optional is also skipped automatically when
