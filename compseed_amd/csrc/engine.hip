@@ -224,20 +224,7 @@ static int engine_init(cs_engine *e, const cs_index_view_t *v)
 	if (verbose) { fprintf(stderr, "[cs_engine] creating engine on device %d, seq_len %llu\n", e->device, (unsigned long long)v->seq_len); fflush(stderr); }
 	CS_TRY(add_pass_ctx(e));
 	PassCtx &c = *e->ctx[0];
-	{
-		int lo = 0, hi = 0;
-		(void)hipDeviceGetStreamPriorityRange(&lo, &hi); // lo = least urgent
-		// The runtime multiplexes the normal-priority streams of a process onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by
-		// default), and a stream that shares its queue with a 30-ms download stands still for 30 ms -- measured: the seeding kernels
-		// of a sub-batch took 65 instead of 45 ms beside the download of the previous one.  So the engine keeps to three normal
-		// streams (main and two side streams; with the process's default stream that makes four); round 3 runs at low priority and
-		// the two copy streams at high priority, which have queues of their own.
-		HIP_TRY(hipStreamCreateWithPriority(&e->s_up.h, hipStreamNonBlocking, hi));
-		HIP_TRY(hipStreamCreateWithPriority(&e->s_down.h, hipStreamNonBlocking, hi));
-		for (auto &ev : e->hp_ev_pk) HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
-		for (auto &ev : e->hp_ev_dn) HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
-		for (auto &ev : e->hp_ev_done) HIP_TRY(hipEventCreateWithFlags(&ev.h, hipEventDisableTiming));
-	}
+	CS_TRY(host_pipe_create(e)); // here, before the index upload: its copy streams are the next streams made after the context's
 
 	if (v->seq_len == 0 || v->seq_len != v->L2[4] || v->L2[0] != 0) return fail(CS_EINVAL, "index view: L2 / seq_len inconsistent");
 	if (v->seq_len >> 37) return fail(CS_ERANGE, "index longer than 2^37 symbols does not fit the packed LEP entries");
@@ -398,11 +385,16 @@ extern "C" void cs_engine_destroy(cs_engine_t *e)
 {
 	if (!e) return;
 	(void)hipSetDevice(e->device);
-	pipe_stop(e); // the threads end before anything is freed,
-	dev_pipe_stop(e);
-	for (auto &c : e->ctx) // then what they queued drains; the members free their memory
+	// The teardown order, also for an engine whose creation failed half-way (any of these may not exist yet):
+	//   1. both pipes' threads are stopped and joined: nothing queues work any more;
+	//   2. every pass context's four streams are drained: the seeding thread queued pack kernels on the context's stream, and those
+	//      write the host pipeline's pack slots;
+	//   3. the copy streams are drained: the downloads read the pack slots and write the pinned result slots;
+	//   4. only then is any pipeline buffer freed (the members' destructors, whoever owns them).
+	pipes_stop(e);
+	for (auto &c : e->ctx)
 		if (c) for (hipStream_t s : {c->stream.h, c->stream2.h, c->stream3.h, c->stream4.h}) if (s) (void)hipStreamSynchronize(s);
-	for (hipStream_t s : {e->s_up.h, e->s_down.h}) if (s) (void)hipStreamSynchronize(s);
+	host_pipe_drain(e);
 	delete e;
 }
 

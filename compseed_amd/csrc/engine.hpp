@@ -2,7 +2,9 @@
 //   engine.hip     ABI lifecycle, options, index load / residency, statistics, device memory helpers
 //   seed_pass.hip  one seeding pass on a pass context: SMEM stage, sort, SAL; the k-mer filter.  The only unit that includes the
 //                  kernels of the default SMEM path, smem_common.hpp and smem_{reads,fwd,bwd,text,sort}.hpp
-//   pipelines.hip  the host pipeline (cs_engine_submit / collect, blocking host variants) and the device pipeline
+//   pipelines.hip  the host pipeline (cs_engine_submit / collect, blocking host variants) and the device pipeline, each with all the state
+//                  only it uses (HostPipe, DevPipe: the engine holds an owning pointer to either); host_parts.hpp: the offset check and the
+//                  cut into parts of a host submit, plain C++
 //   inspect.hip    digest and gather of the last result, index validation, primitives, the random-line probe
 //   dev_stage.hpp  HIP_TRY, the owning types the members below are made of (DevBuf, PinBuf, HipStream, HipEvent), and the stage layer of the
 //                  units outside the engine (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip, extend.hip)
@@ -30,30 +32,6 @@ inline int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #define CS_TRY(expr) do { int rc__ = (expr); if (rc__ != CS_OK) return rc__; } while (0)
 
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)std::max<int64_t>(1, (n + block - 1) / block); }
-
-// ------------------------------------------------------------------------------------------------ host buffers
-// grow-only plain host memory (the expanded results of cs_engine_seed_batch; `keep_n` elements survive a reallocation)
-template <typename T> struct HostBuf {
-	T *p = nullptr; size_t cap = 0;
-	HostBuf() = default;
-	HostBuf(const HostBuf &) = delete;
-	HostBuf &operator=(const HostBuf &) = delete;
-	HostBuf(HostBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-	HostBuf &operator=(HostBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
-	~HostBuf() { release(); }
-	int reserve(size_t n, size_t keep_n = 0)
-	{
-		if (n <= cap) return 0;
-		size_t want = std::max(n, cap + cap / 4);
-		T *q = (T *)malloc(want * sizeof(T));
-		if (!q) return 1;
-		if (p && keep_n) memcpy(q, p, keep_n * sizeof(T));
-		free(p);
-		p = q; cap = want;
-		return 0;
-	}
-	void release() { free(p); p = nullptr; cap = 0; }
-};
 
 // ------------------------------------------------------------------------------------------------ engine
 // The words of PassCtx::d_sctr / h_sctr, the counters of the split SMEM stage.  seed_pass.hip hands the kernels pointers to them
@@ -136,6 +114,9 @@ struct ResultSet {
 };
 
 constexpr int PIPE_DEPTH = 4; // batches in flight in the host pipeline (cs_engine_submit): one pinned result slot each
+// the two pipelines and everything only they use are private to pipelines.hip
+struct HostPipe; struct DevPipe;
+struct PipeDelete { void operator()(HostPipe *) const; void operator()(DevPipe *) const; };
 struct cs_engine {
 	int device = 0;
 	int n_cu = 256;
@@ -164,14 +145,8 @@ struct cs_engine {
 	// cs_engine_memory reads these and nothing a running pass writes: bytes of each pass context as of the end of its last pass (0: no
 	// such context), of `held` as of the last cs_engine_collect_device (reported within pass_ctx[0]), and of the k-mer filter
 	std::atomic<uint64_t> ctx_bytes[2] = {{0}, {0}}, held_bytes{0}, bloom_bytes{0};
-	// host variants (seed_host_pipelined): copy streams, three input slots, two pack slots, pinned packed results, expanded results
-	HipStream s_up, s_down; HipEvent hp_ev_pk[2], hp_ev_dn[4], hp_ev_done[PIPE_DEPTH];
-	PinBuf<uint4> hp_stage[3]; // records made by the host (host_pack.cpp), staged for the upload into hp_in[slot]
-	DevBuf<uint8_t> hp_in[3], hp_pk_mems[2]; DevBuf<uint64_t> hp_inoff[3], hp_pk_moff[2], hp_pk_soff[2]; DevBuf<uint32_t> hp_pk_rlo[2]; DevBuf<uint8_t> hp_pk_rhi[2]; // seeds: low words and fifth bytes of rbeg
-	PinBuf<uint64_t> hp_moff[PIPE_DEPTH], hp_soff[PIPE_DEPTH]; PinBuf<uint8_t> hp_mems[PIPE_DEPTH]; PinBuf<uint32_t> hp_rlo[PIPE_DEPTH]; PinBuf<uint8_t> hp_rhi[PIPE_DEPTH]; // pinned result slots (slot = batch % PIPE_DEPTH)
-	struct HostPipe *hp = nullptr;
-	HostBuf<cs_intv_t> x_mems; HostBuf<cs_seed_t> x_seeds;
-	struct DevPipe *dp = nullptr;                  // cs_engine_submit_device / cs_engine_collect_device
+	std::unique_ptr<HostPipe, PipeDelete> hp;      // host variants: copy streams, slots, threads, expanded results (made by engine_init)
+	std::unique_ptr<DevPipe, PipeDelete> dp;       // cs_engine_submit_device / cs_engine_collect_device (made by the first submit)
 	// cs_engine_gather_reads
 	DevBuf<uint64_t> d_sel, d_sel_moff, d_sel_soff; DevBuf<OutMem> d_sel_mems; DevBuf<OutSeed> d_sel_seeds;
 	PinBuf<uint64_t> h_mem_off, h_seed_off; PinBuf<OutMem> h_mems; PinBuf<OutSeed> h_seeds;
@@ -206,6 +181,7 @@ int seed_pass_init(cs_engine *e); // occupancy of the split kernels, the k-mer f
 int run_pass(cs_engine *e, PassCtx *c, const cs_params_t *par, int64_t n_reads, const uint8_t *d_bases, const uint64_t *d_off,
              uint64_t n_bases, uint64_t *nm, uint64_t *ns, const uint4 *d_recs);
 // pipelines.hip
-void pipe_stop(cs_engine *e);
-void dev_pipe_stop(cs_engine *e);
+int host_pipe_create(cs_engine *e);   // the copy streams and events of the host pipeline; its buffers grow on first use, its threads start on the first submit
+void pipes_stop(cs_engine *e);        // stops and joins the threads of both pipelines
+void host_pipe_drain(cs_engine *e);   // waits for the two copy streams
 bool pipe_busy(const cs_engine *e);

@@ -699,8 +699,8 @@ def test_device_batches_in_flight_on_two_pass_contexts(passes):
 
 
 def test_stream_of_host_batches_with_changing_parameters():
-    """cs_engine_submit / collect: all golden runs through the host pipeline, three in flight, whole and cut into parts that are packed in
-    order; consecutive batches differ in -k, so the k-mer filter is rebuilt between passes (under the lock the pass contexts share)"""
+    """cs_engine_submit / collect: all golden runs through the host pipeline, three in flight, whole and cut into parts that the seeding
+    thread takes in order; consecutive batches differ in -k, so the k-mer filter is rebuilt between passes (under the lock the pass contexts share)"""
     import compseed_amd as ca
     ix = ca.Index.load(_data.PREFIX)
     for pr in (700, 0):
@@ -723,3 +723,31 @@ def test_stream_of_host_batches_with_changing_parameters():
                 e.submit(data[i + 3][2], data[i + 3][3], ca.Params(**data[i + 3][1]))
         e.close()
     ix.close()
+
+
+@pytest.mark.parametrize("pipeline_reads", [350, 0])
+def test_failed_batch_between_good_ones_in_a_host_stream(pipeline_reads):
+    """A batch whose pass is refused inside the seeding thread (max_occ 1025: CS_ERANGE, an error code and no device fault) while its
+    neighbours are in flight, cut into parts and whole: its collect raises, the batches around it and after it are the golden's."""
+    import compseed_amd as ca
+    ix = ca.Index.load(_data.PREFIX)
+    e = ca.Engine(ix, 0, pipeline_reads=pipeline_reads)
+    z, _ = _data.load_golden("main100", "default")
+    bases, off = _data.load_reads("main100")
+
+    def check_packed(p):
+        mems, seeds = _expand_packed(p)
+        assert np.array_equal(p["mem_off"], z["mem_off"]) and np.array_equal(np.stack([mems["x0"], mems["x1"], mems["x2"], mems["info"]], axis=1), z["mems"])
+        assert np.array_equal(seeds["rbeg"], z["seed_rbeg"]) and np.array_equal(p["seed_off"], z["seed_off"])
+    e.submit(bases, off, ca.Params())
+    e.submit(bases, off, ca.Params(c=1025))
+    e.submit(bases, off, ca.Params())
+    check_packed(e.collect_packed())
+    with pytest.raises(ca.CSError) as err:
+        e.collect_packed()
+    assert err.value.code == -5                                  # CS_ERANGE
+    check_packed(e.collect_packed())
+    e.submit(bases, off, ca.Params())
+    check_packed(e.collect_packed())
+    _check_against_golden(e.seed_batch(bases, off, ca.Params()), z)
+    e.close(); ix.close()
