@@ -14,6 +14,7 @@
 //   seedcov_kernel, purge_kernel   comp_seed.cpp:1758-1766 and :2141-2232 (one thread per read walks its regions in extension order)
 // Same results as the host driver it replaces, field by field (tests/test_gpu_align.py against the reference's own regions).
 #include "dev_stage.hpp"
+#include "compact.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -446,28 +447,8 @@ __global__ void reg_off_kernel(const DevIn D, uint64_t *reg_off) // a read's reg
 {
 	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= D.n_reads; r += (int64_t)gridDim.x * blockDim.x) reg_off[r] = D.cseed_off[D.chain_off[r]];
 }
-// CS_ALN_DEV_COMPACT: the regions the purge marked (qe <= qb: what comp_seed.cpp:2387-2393 drops) stay behind.  live[g], an exclusive scan
-// over n_seeds + 1 flags (the last one 0: the total), then the live regions move as 8-byte words, a word per lane -- 7 words a region, so
-// a wave reads 512 contiguous bytes and writes runs of them -- into a buffer of their own, and reg_off[r] becomes scan[reg_off[r]].
-constexpr int REG_WORDS = (int)(sizeof(cs_alnreg_t) / 8);
-static_assert(sizeof(cs_alnreg_t) == 56 && REG_WORDS * 8 == (int)sizeof(cs_alnreg_t), "cs_alnreg_t is seven 8-byte words");
-__global__ void live_kernel(const cs_alnreg_t *regs, uint64_t n, uint32_t *live)
-{
-	for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= n; g += (uint64_t)gridDim.x * blockDim.x) live[g] = g < n && regs[g].qe > regs[g].qb ? 1u : 0u;
-}
-__global__ void scatter_kernel(const uint64_t *in, uint64_t n, const uint32_t *live, const uint32_t *scan, uint64_t *out)
-{
-	const uint64_t n_words = n * REG_WORDS;
-	for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_words; t += (uint64_t)gridDim.x * blockDim.x) {
-		const uint64_t g = t / REG_WORDS;
-		if (live[g]) out[(uint64_t)scan[g] * REG_WORDS + (t - g * REG_WORDS)] = in[t];
-	}
-}
-__global__ void reg_off_live_kernel(uint64_t *reg_off, int64_t n_reads, const uint32_t *scan, uint64_t n, unsigned long long *n_live) // in place: a lane reads and writes its own entry
-{
-	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r <= n_reads; r += (int64_t)gridDim.x * blockDim.x) reg_off[r] = scan[reg_off[r]];
-	if (blockIdx.x == 0 && threadIdx.x == 0) *n_live = scan[n];
-}
+// CS_ALN_DEV_COMPACT: the regions the purge marked (qe <= qb: what comp_seed.cpp:2387-2393 drops) stay behind.  live_kernel, an exclusive
+// scan, scatter_kernel and reg_off_live_kernel are compact.hpp's (a device de-duplication would compact its survivors the same way: dedup_pass.hpp).
 } // namespace csa
 
 namespace {
