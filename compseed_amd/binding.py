@@ -39,10 +39,14 @@ class Params(C.Structure):
     """cs_params_t; defaults = mem_opt_init (mapping/comp_seed.cpp:26-58)."""
     _fields_ = [("min_seed_len", C.c_int32), ("split_factor", C.c_float), ("split_width", C.c_int32),
                 ("max_occ", C.c_int32), ("max_mem_intv", C.c_uint64), ("want_sal", C.c_int32), ("sst_mode", C.c_int32),
-                ("disable", C.c_uint32), ("count_traffic", C.c_uint32)]
+                ("disable", C.c_uint32), ("count_traffic", C.c_uint32), ("result_flags", C.c_uint32), ("reserved", C.c_uint32)]
 
-    def __init__(self, k=19, r=1.5, s=10, c=500, y=20, want_sal=1, sst_mode=1, disable=0, count_traffic=0):
-        super().__init__(k, r, s, c, y, want_sal, sst_mode, disable, count_traffic)
+    def __init__(self, k=19, r=1.5, s=10, c=500, y=20, want_sal=1, sst_mode=1, disable=0, count_traffic=0, result_flags=0):
+        super().__init__(k, r, s, c, y, want_sal, sst_mode, disable, count_traffic, result_flags, 0)
+
+
+RESULT_LEAN = 1   # CS_RESULT_LEAN (cs_params_t.result_flags): the caller reads no x0 / x1 of the mems; x1 = 0 everywhere, packed mems as MEM8_DT
+MEM_FULL32, MEM_PACKED16, MEM_LEAN8 = 0, 1, 2   # cs_packed_result_t.mem_format
 
 
 # cs_params_t.disable bits (include/compseed_amd.h CS_DISABLE_*)
@@ -135,6 +139,24 @@ def unpack_mems16(p):
     out["x2"] = (p["w0"] >> np.uint64(33)) | ((p["w1"] >> np.uint64(63)) << np.uint64(31))
     out["info"] = (((p["w1"] >> np.uint64(33)) & np.uint64(0x7fff)) << np.uint64(32)) | ((p["w1"] >> np.uint64(48)) & np.uint64(0x7fff))
     return out
+
+
+MEM8_DT = np.dtype([("w", "<u8")])   # cs_mem8_t
+
+
+def unpack_mems8(p):
+    """numpy restatement of cs_unpack_mem for CS_MEM_LEAN8 records -> INTV_DT array (x0 = x1 = 0)"""
+    out = np.zeros(p.size, dtype=INTV_DT)
+    w = p["w"]
+    out["x2"] = w & np.uint64((1 << 34) - 1)
+    out["info"] = (((w >> np.uint64(34)) & np.uint64(0x7fff)) << np.uint64(32)) | ((w >> np.uint64(49)) & np.uint64(0x7fff))
+    return out
+
+
+def unpack_mems(p):
+    """the mems of a packed result dict (Engine.seed_batch_packed / collect_packed) as an INTV_DT array, whatever their format"""
+    f = p["mem_format"]
+    return unpack_mems16(p["mems"]) if f == MEM_PACKED16 else unpack_mems8(p["mems"]) if f == MEM_LEAN8 else p["mems"].copy()
 
 
 EXT_PAIR_DT = np.dtype([("q_off", "<u8"), ("t_off", "<u8"), ("qlen", "<i4"), ("tlen", "<i4"), ("h0", "<i4"), ("reserved", "<i4")])   # cs_ext_pair_t
@@ -760,7 +782,7 @@ class Engine:
 
     def seed_batch_packed(self, bases, offsets, params=None):
         """Host buffers in, the PACKED CSR (what crosses PCIe) out as views of the engine's pinned buffers: dict(mem_format, mem_off,
-        mems (MEM16_DT or INTV_DT), seed_off, seed_rbeg, max_occ); valid until the next call (cs_engine_seed_batch_packed)"""
+        mems (MEM16_DT, MEM8_DT under RESULT_LEAN, or INTV_DT), seed_off, seed_rbeg, max_occ); valid until the next call (cs_engine_seed_batch_packed)"""
         params = params or Params()
         if not isinstance(bases, PinnedArray):
             bases = np.ascontiguousarray(bases, dtype=np.uint8)
@@ -789,7 +811,7 @@ class Engine:
         sal = bool(res.seed_off)
         return PackedResult(n_reads=n, n_mems=int(res.n_mems), n_seeds=int(res.n_seeds), mem_format=int(res.mem_format), max_occ=int(res.max_occ),
                             mem_off=_view(res.mem_off, "<u8", n + 1, False),
-                            mems=_view(res.mems, MEM16_DT if res.mem_format == 1 else INTV_DT, int(res.n_mems), False),
+                            mems=_view(res.mems, {MEM_PACKED16: MEM16_DT, MEM_LEAN8: MEM8_DT}.get(int(res.mem_format), INTV_DT), int(res.n_mems), False),
                             seed_off=_view(res.seed_off, "<u8", n + 1, False) if sal else None, seed_format=int(res.seed_format),
                             seed_rbeg_lo=_view(res.seed_rbeg_lo, "<u4", int(res.n_seeds), False) if sal else None,
                             seed_rbeg_hi=_view(res.seed_rbeg_hi, "u1", int(res.n_seeds), False) if sal else None)

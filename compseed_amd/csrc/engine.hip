@@ -19,6 +19,7 @@ extern "C" void cs_params_default(cs_params_t *p)
 	if (!p) return;
 	p->min_seed_len = 19; p->split_factor = 1.5f; p->split_width = 10; p->max_occ = 500; p->max_mem_intv = 20;
 	p->want_sal = 1; p->sst_mode = 1; p->disable = 0; p->count_traffic = 0;
+	p->result_flags = 0; p->reserved = 0;
 }
 extern "C" void cs_engine_options_default(cs_engine_options_t *o)
 {

@@ -152,6 +152,9 @@ struct cs_engine {
 	PinBuf<uint64_t> h_mem_off, h_seed_off; PinBuf<OutMem> h_mems; PinBuf<OutSeed> h_seeds;
 };
 
+// cs_params_t.result_flags / reserved, checked by every seed entry point before it touches the device
+inline bool result_flags_ok(const cs_params_t *par) { return (par->result_flags & ~CS_RESULT_LEAN) == 0 && par->reserved == 0; }
+inline bool lean_results(const cs_params_t *par) { return (par->result_flags & CS_RESULT_LEAN) != 0; }
 inline int n_pass_ctx(const cs_engine *e) { return e->ctx[1] ? 2 : 1; }
 inline void note_ctx_bytes(cs_engine *e, const PassCtx *c) { e->ctx_bytes[c->id].store(c->device_bytes(), std::memory_order_relaxed); }
 inline void invalidate_last(cs_engine *e) { for (auto &c : e->ctx) if (c) c->last.valid = false; e->last_ctx = nullptr; e->last_in_held = false; }

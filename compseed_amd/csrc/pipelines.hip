@@ -18,7 +18,7 @@
 // cs_engine_seed_batch_packed / cs_engine_seed_batch: the boundary the reference-side patch calls, i.e. the part
 // of the path the reference overlaps with kt_pipeline (main.cpp:438, cstl/kthread.c:121: read the next chunk / process / write).
 // The batch is cut into sub-batches; an upload thread stages sub-batch i+1 while the calling thread seeds sub-batch i, whose
-// results are packed on the device (16-byte mems, 8-byte seeds: include/compseed_amd.h) into one of two buffers and go to pinned
+// results are packed on the device (16-byte mems, 8-byte under CS_RESULT_LEAN, 5-byte seeds: include/compseed_amd.h) into one of two buffers and go to pinned
 // host memory on a copy stream of their own while sub-batch i+1 is seeded; cs_engine_seed_batch additionally expands finished
 // sub-batches to cs_intv_t / cs_seed_t on an expander thread (itself multi-threaded) beside all that.
 __global__ void pack_mems16_kernel(const OutMem *m, uint64_t n, uint4 *out)
@@ -28,6 +28,15 @@ __global__ void pack_mems16_kernel(const OutMem *m, uint64_t n, uint4 *out)
 		const uint64_t beg = v.info >> 32, end = v.info & 0xffffffffull;
 		const uint64_t w0 = v.x0 | (v.x2 & 0x7fffffffull) << 33, w1 = v.x1 | beg << 33 | end << 48 | (v.x2 >> 31) << 63;
 		out[i] = make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
+	}
+}
+// CS_RESULT_LEAN: x2 and the two query positions in one word (cs_mem8_t); 32 bytes read, 8 written per lane, both coalesced
+__global__ void pack_mems8_kernel(const OutMem *m, uint64_t n, uint64_t *out)
+{
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+		const OutMem v = m[i];
+		const uint64_t beg = v.info >> 32, end = v.info & 0xffffffffull;
+		out[i] = v.x2 | beg << 34 | end << 49;
 	}
 }
 // a seed travels as its rbeg only, in 40 bits: positions are below 2^37 (checked at engine creation), so the low word and the fifth byte go
@@ -152,7 +161,7 @@ struct PackSlot {                        // a part's results as they travel, pac
 };
 struct BatchState {
 	uint64_t id = ~0ull; int64_t n_reads = 0; int parts_total = 0, parts_queued = 0; uint64_t mem_base = 0, seed_base = 0;
-	int rc = CS_OK; std::string err; bool pk16 = false, sal = false, expand = false, expanded = false; int max_occ = 0;
+	int rc = CS_OK; std::string err; bool sal = false, expand = false, expanded = false; int mem_format = CS_MEM_FULL32, max_occ = 0;
 };
 struct ResultSlot {                      // a batch's packed results in pinned memory, and the batch they belong to: batch id % PIPE_DEPTH
 	PinBuf<uint64_t> moff, soff; PinBuf<uint8_t> mems; PinBuf<uint32_t> rlo; PinBuf<uint8_t> rhi;
@@ -163,7 +172,7 @@ struct HostJob {
 	uint64_t batch = 0; int part = 0, n_parts = 0;
 	const uint8_t *bases = nullptr; const uint64_t *offsets = nullptr;
 	int64_t r0 = 0, n = 0, n_reads = 0; uint64_t b0 = 0, nb = 0;
-	cs_params_t par{}; bool pk16 = false, expand = false, packed = false; // packed: the host makes the records (host_pack.cpp)
+	cs_params_t par{}; int mem_format = CS_MEM_FULL32; bool expand = false, packed = false; // packed: the host makes the records (host_pack.cpp)
 	InSlot *in = nullptr;                // from the upload thread on
 };
 struct XJob { uint64_t batch; int64_t r0, n; uint64_t mem_base, nm, seed_base, ns; hipEvent_t ev; bool last; };
@@ -271,7 +280,7 @@ static void pipe_expand_thread(cs_engine *e)
 		}
 		if (ok) {
 			cs_packed_result_t Q; memset(&Q, 0, sizeof Q);
-			Q.n_reads = b.n_reads; Q.mem_format = b.pk16 ? CS_MEM_PACKED16 : CS_MEM_FULL32; Q.max_occ = b.max_occ;
+			Q.n_reads = b.n_reads; Q.mem_format = b.mem_format; Q.max_occ = b.max_occ;
 			Q.mem_off = rs.moff.p; Q.mems = rs.mems.p; Q.seed_off = b.sal ? rs.soff.p : nullptr; Q.seed_format = CS_SEED_RBEG40; Q.seed_rbeg_lo = b.sal ? rs.rlo.p : nullptr; Q.seed_rbeg_hi = b.sal ? rs.rhi.p : nullptr;
 			expand_parallel(Q, hp.x_mems.p, hp.x_seeds.p, x.r0, x.r0 + x.n, e->opt.expand_threads);
 		}
@@ -298,7 +307,7 @@ struct Part {
 	uint64_t mem_base, seed_base;        // mems / seeds of the earlier parts of the batch
 	PartStatus st; uint64_t nm = 0, ns = 0;
 	bool sal() const { return j.par.want_sal != 0; }
-	size_t msz() const { return j.pk16 ? 16 : 32; }
+	size_t msz() const { return j.mem_format == CS_MEM_LEAN8 ? sizeof(cs_mem8_t) : j.mem_format == CS_MEM_PACKED16 ? sizeof(cs_mem16_t) : sizeof(cs_intv_t); } // an element of the batch's own format
 };
 
 // The steps of the seeding thread, in the order it takes them.  Those that wait return false when the pipe is being stopped.
@@ -366,7 +375,8 @@ static void pack_and_download(cs_engine *e, HostPipe &hp, PassCtx *c, Part &p)
 	const unsigned g = (unsigned)e->n_cu * 8;
 	hipLaunchKernelGGL(shift_words_kernel, dim3(g), dim3(256), 0, s, (const uint64_t *)c->d_mem_off.p, (uint64_t)j.n + 1, p.mem_base, ps.moff.p);
 	if (nm) {
-		if (j.pk16) hipLaunchKernelGGL(pack_mems16_kernel, dim3(g), dim3(256), 0, s, (const OutMem *)c->d_mems.p, nm, (uint4 *)ps.mems.p);
+		if (j.mem_format == CS_MEM_LEAN8) hipLaunchKernelGGL(pack_mems8_kernel, dim3(g), dim3(256), 0, s, (const OutMem *)c->d_mems.p, nm, (uint64_t *)ps.mems.p);
+		else if (j.mem_format == CS_MEM_PACKED16) hipLaunchKernelGGL(pack_mems16_kernel, dim3(g), dim3(256), 0, s, (const OutMem *)c->d_mems.p, nm, (uint4 *)ps.mems.p);
 		else st.hip(hipMemcpyAsync(ps.mems.p, c->d_mems.p, (size_t)nm * 32, hipMemcpyDeviceToDevice, s), "copying mems");
 	}
 	if (p.sal()) {
@@ -438,7 +448,9 @@ static std::vector<HostJob> make_parts(const cs_engine *e, uint64_t id, const st
 		HostJob j; j.batch = id; j.part = (int)i; j.n_parts = (int)kparts; j.bases = bases; j.offsets = offsets; j.n_reads = n_reads;
 		j.r0 = cut[(size_t)i]; j.n = cut[(size_t)i + 1] - j.r0;
 		j.b0 = n_reads ? offsets[j.r0] : 0; j.nb = n_reads ? offsets[j.r0 + j.n] - j.b0 : 0;
-		j.par = *par; j.pk16 = (e->ix.seq_len >> 33) == 0 && max_len < (1u << 15); j.expand = expand;
+		j.par = *par; j.expand = expand;
+		// the packed forms need an index shorter than 2^33 symbols and reads shorter than 2^15 bases; a lean batch takes the 8-byte one
+		j.mem_format = (e->ix.seq_len >> 33) == 0 && max_len < (1u << 15) ? (lean_results(par) ? CS_MEM_LEAN8 : CS_MEM_PACKED16) : CS_MEM_FULL32;
 		j.packed = host_pack;
 		const size_t n_rec = (size_t)(j.nb >> 5) + (size_t)j.n;
 		cap.in = std::max<size_t>(cap.in, host_pack ? (n_rec + 4) * 16 : j.nb); cap.off = std::max<size_t>(cap.off, (size_t)j.n + 1);
@@ -472,6 +484,7 @@ static int grow_shared(cs_engine *e, HostPipe &hp, std::unique_lock<std::mutex> 
 static int pipe_submit(cs_engine *e, const cs_params_t *par, int64_t n_reads, const uint8_t *bases, const uint64_t *offsets, bool expand)
 {
 	if (!e || !par || n_reads < 0 || (n_reads > 0 && !offsets)) return fail(CS_EINVAL, "cs_engine_submit: bad argument");
+	if (!result_flags_ok(par)) return fail(CS_EINVAL, "unknown bits in result_flags, or reserved is not 0");
 	if (n_reads >= (int64_t)0xffffffffll) return fail(CS_ERANGE, "more than 2^32-1 reads in one call");
 	if (par->min_seed_len < 1 || par->max_occ < 1 || par->split_width < 0) return fail(CS_EINVAL, "bad seeding parameters");
 	HIP_TRY(hipSetDevice(e->device));
@@ -496,7 +509,7 @@ static int pipe_submit(cs_engine *e, const cs_params_t *par, int64_t n_reads, co
 	CS_TRY(grow_shared(e, hp, lk, rs, cap, par->want_sal != 0));
 	BatchState &b = rs.b;
 	b = BatchState();
-	b.id = id; b.n_reads = n_reads; b.parts_total = (int)parts.size(); b.pk16 = parts[0].pk16; b.sal = par->want_sal != 0; b.expand = expand; b.max_occ = par->max_occ;
+	b.id = id; b.n_reads = n_reads; b.parts_total = (int)parts.size(); b.mem_format = parts[0].mem_format; b.sal = par->want_sal != 0; b.expand = expand; b.max_occ = par->max_occ;
 	for (auto &j : parts) hp.q_up.push_back(j);
 	if (e->opt.verbose > 1) fprintf(stderr, "[cs_engine] batch %llu submitted at %.1f ms in %d part(s)\n", (unsigned long long)id, pipe_ms(), (int)parts.size());
 	hp.n_submitted++;
@@ -542,7 +555,7 @@ static int pipe_collect(cs_engine *e, cs_packed_result_t *out)
 	}
 	if (rc != CS_OK) return fail(rc, err);
 	out->n_reads = b.n_reads; out->n_mems = b.mem_base; out->n_seeds = b.seed_base; out->max_occ = b.max_occ;
-	out->mem_format = b.pk16 ? CS_MEM_PACKED16 : CS_MEM_FULL32;
+	out->mem_format = b.mem_format;
 	out->mem_off = rs.moff.p; out->mems = rs.mems.p;
 	out->seed_off = b.sal ? rs.soff.p : nullptr; out->seed_format = CS_SEED_RBEG40;
 	out->seed_rbeg_lo = b.sal ? rs.rlo.p : nullptr; out->seed_rbeg_hi = b.sal ? rs.rhi.p : nullptr;
@@ -602,6 +615,7 @@ void host_pipe_drain(cs_engine *e) { if (e->hp) e->hp->drain(); }
 extern "C" int cs_engine_submit_device(cs_engine_t *e, const cs_params_t *par, int64_t n_reads, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_bases)
 {
 	if (!e || !par || n_reads < 0 || (n_reads > 0 && !d_offsets) || (n_bases > 0 && !d_bases)) return fail(CS_EINVAL, "cs_engine_submit_device: bad argument");
+	if (!result_flags_ok(par)) return fail(CS_EINVAL, "unknown bits in result_flags, or reserved is not 0");
 	if (n_reads >= (int64_t)0xffffffffll) return fail(CS_ERANGE, "more than 2^32-1 reads in one call");
 	if (host_pipe_busy(e)) return fail(CS_EINVAL, "cs_engine_submit_device: host batches are in flight (cs_engine_submit), collect them first");
 	HIP_TRY(hipSetDevice(e->device));

@@ -231,7 +231,9 @@ __global__ void nt4_kernel(const uint8_t *in, uint8_t *out, uint64_t n)
 	for (uint64_t i = (nv << 4) + tid; i < n; i += stride) out[i] = (uint8_t)nt4_of(in[i]);
 }
 
-// per-read sort by info (comp_seed.cpp:2301) fused with the CSR compaction: rank every mem among its read's mems
+// per-read sort by info (comp_seed.cpp:2301) fused with the CSR compaction: rank every mem among its read's mems.
+// LEAN (CS_RESULT_LEAN): the mems are stored with x1 = 0
+template <bool LEAN>
 __global__ void sort_compact_kernel(const OutMem *raw, const uint32_t *cnt, uint32_t cap, const uint64_t *mem_off, uint64_t base_off,
                                     int64_t n_reads, const uint32_t *slot_of_read, OutMem *mems)
 {
@@ -244,7 +246,8 @@ __global__ void sort_compact_kernel(const OutMem *raw, const uint32_t *cnt, uint
 	for (uint32_t a = 0; a < n; ++a) {
 		uint64_t ka = src[a].info; uint32_t rank = 0;
 		for (uint32_t b = 0; b < n; ++b) { uint64_t kb = src[b].info; rank += (kb < ka) || (kb == ka && b < a); }
-		dst[rank] = src[a];
+		if (LEAN) { OutMem m = src[a]; m.x1 = 0; dst[rank] = m; }
+		else dst[rank] = src[a];
 	}
 }
 

@@ -109,6 +109,7 @@ __global__ void patch_counts_kernel(const uint32_t *cnt2, const uint32_t *list, 
 	cnt[list[t] - first_read] = cnt2[t];
 }
 // second-pass variant of sort_compact_kernel: task t holds read list[t]
+template <bool LEAN>
 __global__ void sort_compact_list_kernel(const OutMem *raw, const uint32_t *cnt2, uint32_t cap2, const uint32_t *list, int64_t n_tasks,
                                          const uint64_t *mem_off, OutMem *mems)
 {
@@ -120,7 +121,8 @@ __global__ void sort_compact_list_kernel(const OutMem *raw, const uint32_t *cnt2
 	for (uint32_t a = 0; a < n; ++a) {
 		uint64_t ka = src[a].info; uint32_t rank = 0;
 		for (uint32_t b = 0; b < n; ++b) { uint64_t kb = src[b].info; rank += (kb < ka) || (kb == ka && b < a); }
-		dst[rank] = src[a];
+		if (LEAN) { OutMem m = src[a]; m.x1 = 0; dst[rank] = m; }
+		else dst[rank] = src[a];
 	}
 }
 
@@ -250,6 +252,7 @@ struct SplitRun {
 	int64_t nb;
 	uint64_t fq_cap, ovf_cap, chunk;
 	bool count, r2text, r3_text, r3_async, fwd0_on;
+	bool lean; // CS_RESULT_LEAN: r3text_kernel leaves x1 alone (the sort stores 0 there)
 };
 
 // The kernels' arguments for reads [0, nb) of d_off; the iterations set the queue fields (fq, n_f, fq_next, aux_next) per launch.
@@ -313,10 +316,12 @@ static int launch_r3text(const cs_engine *e, PassCtx *c, const SplitRun &R, cons
 	HIP_TRY(hipEventRecord(c->ev_r3a, s));
 	HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_r3a, 0));
 	const dim3 grid((unsigned)std::min<uint64_t>((uint64_t)e->n_cu * 16, ((uint64_t)nb + 255) / 256));
-	// (the instantiation follows the index: 8-byte inverse-SA entries that carry rep[] answer "unique? its rank" with one load)
-	if (e->ix.isa_fused)
-		hipLaunchKernelGGL(r3text_kernel<true>, grid, dim3(256), 0, c->stream2, R.A, (const uint32_t *)c->d_cnt_snap.p, c->d_sctr.p + SC_R3_TEXT_SEEDS, (const uint8_t *)c->d_pending.p);
-	else hipLaunchKernelGGL(r3text_kernel<false>, grid, dim3(256), 0, c->stream2, R.A, (const uint32_t *)c->d_cnt_snap.p, c->d_sctr.p + SC_R3_TEXT_SEEDS, (const uint8_t *)c->d_pending.p);
+	// (the instantiation follows the index: 8-byte inverse-SA entries that carry rep[] answer "unique? its rank" with one load; and the
+	// call: a lean result does not ask for the reverse-strand ranks, which only make x1)
+#define LAUNCH_R3TEXT(FUSED, LEAN) hipLaunchKernelGGL((r3text_kernel<FUSED, LEAN>), grid, dim3(256), 0, c->stream2, R.A, (const uint32_t *)c->d_cnt_snap.p, c->d_sctr.p + SC_R3_TEXT_SEEDS, (const uint8_t *)c->d_pending.p)
+	if (e->ix.isa_fused) { if (R.lean) LAUNCH_R3TEXT(true, true); else LAUNCH_R3TEXT(true, false); }
+	else { if (R.lean) LAUNCH_R3TEXT(false, true); else LAUNCH_R3TEXT(false, false); }
+#undef LAUNCH_R3TEXT
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->ev_r3b, c->stream2));
 	return CS_OK;
@@ -418,7 +423,7 @@ static int run_smem_split_body(const cs_engine *e, PassCtx *c, const cs_params_t
 	if (par->split_width > 16382) return 1; // min_intv does not fit the 14-bit task field: use the fused kernel
 	const uint32_t stride = max_len + 1;
 	SplitRun R;
-	R.nb = nb; R.count = par->count_traffic != 0;
+	R.nb = nb; R.count = par->count_traffic != 0; R.lean = lean_results(par);
 	R.fq_cap = (uint64_t)nb * 8 + 4096; R.ovf_cap = (uint64_t)nb * 4 + 65536;
 	R.chunk = std::max<uint64_t>(4096, e->lep_arena_bytes / ((size_t)stride * sizeof(uint4)));
 	R.chunk = std::min<uint64_t>(R.chunk, R.fq_cap);
@@ -581,15 +586,16 @@ static int finish_split_batch(const cs_engine *e, PassCtx *c, const cs_params_t 
 	}
 	uint64_t new_total = 0;
 	const uint32_t mo = (uint32_t)par->max_occ;
+	const bool lean = lean_results(par); // the kernels below write the final mems[]: their <true> instantiations store x1 = 0
 	if (total_seeds) {
 		CS_TRY(place_mems(c, b0, nb, *total_mems, false, &new_total, total_seeds));
 		unsigned long long *bad = c->d_ctr.p + CTR_SEED_RANGE;
 		HIP_TRY(hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
 		HIP_TRY(hipEventRecord(c->ev[0], s));
-		hipLaunchKernelGGL(sort_expand16_kernel, dim3(grid_for(nb * 16, 256)), dim3(256), 0, s, e->ix, c->d_out.p, c->d_cnt.p, cap, c->d_mem_off.p + b0,
-		                   c->d_seed_off.p + b0, nb, c->d_mems.p, c->d_seeds.p, mo, bad);
-		hipLaunchKernelGGL(sort_compact_wave_kernel, dim3(grid_for(nb, 256)), dim3(256), 0, s, c->d_out.p, c->d_cnt.p, cap, c->d_ovfrec.p,
-		                   c->d_okey2.p, c->d_oidx2.p, n_ovf, c->d_mem_off.p + b0, nb, c->d_mems.p, (uint64_t *)nullptr, mo);
+		LAUNCH_EITHER(lean, sort_expand16_kernel<true>, sort_expand16_kernel<false>, dim3(grid_for(nb * 16, 256)), dim3(256), s, e->ix, c->d_out.p, c->d_cnt.p, cap, c->d_mem_off.p + b0,
+		              c->d_seed_off.p + b0, nb, c->d_mems.p, c->d_seeds.p, mo, bad);
+		LAUNCH_EITHER(lean, sort_compact_wave_kernel<true>, sort_compact_wave_kernel<false>, dim3(grid_for(nb, 256)), dim3(256), s, c->d_out.p, c->d_cnt.p, cap, c->d_ovfrec.p,
+		              c->d_okey2.p, c->d_oidx2.p, n_ovf, c->d_mem_off.p + b0, nb, c->d_mems.p, (uint64_t *)nullptr, mo);
 		hipLaunchKernelGGL(sal_expand_heavy_kernel, dim3(grid_for(nb, 256)), dim3(256), 0, s, e->ix, c->d_cnt.p, cap, c->d_mem_off.p + b0, c->d_seed_off.p + b0,
 		                   nb, (const OutMem *)c->d_mems.p, c->d_seeds.p, mo, bad);
 		HIP_TRY(hipGetLastError());
@@ -603,10 +609,10 @@ static int finish_split_batch(const cs_engine *e, PassCtx *c, const cs_params_t 
 	}
 	CS_TRY(place_mems(c, b0, nb, *total_mems, true, &new_total, nullptr, salcnt_ok));
 	// (up to 64 mems and none beyond `cap`: 16 lanes per read; all other reads: a wave each)
-	hipLaunchKernelGGL(sort_compact16_kernel, dim3(grid_for(nb * 16, 256)), dim3(256), 0, s, c->d_out.p, c->d_cnt.p, cap,
-	                   c->d_mem_off.p + b0, nb, c->d_mems.p, c->d_salcnt.p, mo);
-	hipLaunchKernelGGL(sort_compact_wave_kernel, dim3(grid_for(nb, 256)), dim3(256), 0, s, c->d_out.p, c->d_cnt.p, cap, c->d_ovfrec.p,
-	                   c->d_okey2.p, c->d_oidx2.p, n_ovf, c->d_mem_off.p + b0, nb, c->d_mems.p, c->d_salcnt.p, mo);
+	LAUNCH_EITHER(lean, sort_compact16_kernel<true>, sort_compact16_kernel<false>, dim3(grid_for(nb * 16, 256)), dim3(256), s, c->d_out.p, c->d_cnt.p, cap,
+	              c->d_mem_off.p + b0, nb, c->d_mems.p, c->d_salcnt.p, mo);
+	LAUNCH_EITHER(lean, sort_compact_wave_kernel<true>, sort_compact_wave_kernel<false>, dim3(grid_for(nb, 256)), dim3(256), s, c->d_out.p, c->d_cnt.p, cap, c->d_ovfrec.p,
+	              c->d_okey2.p, c->d_oidx2.p, n_ovf, c->d_mem_off.p + b0, nb, c->d_mems.p, c->d_salcnt.p, mo);
 	HIP_TRY(hipGetLastError());
 	*total_mems = new_total;
 	return CS_OK;
@@ -658,11 +664,12 @@ static int run_fused_batch(const cs_engine *e, PassCtx *c, const cs_params_t *pa
 	uint64_t new_total = 0;
 	CS_TRY(place_mems(c, b0, nb, *total_mems, false, &new_total));
 	// mem_off already holds absolute offsets, so base_off = 0 and the per-read offset array is shifted by b0
-	hipLaunchKernelGGL(sort_compact_kernel, dim3(grid_for(nb, 128)), dim3(128), 0, s, c->d_out.p, c->d_cnt.p, cap, c->d_mem_off.p + b0,
-	                   (uint64_t)0, nb, (const uint32_t *)nullptr, c->d_mems.p);
+	const bool lean = lean_results(par); // the two kernels that write this path's final mems[]
+	LAUNCH_EITHER(lean, sort_compact_kernel<true>, sort_compact_kernel<false>, dim3(grid_for(nb, 128)), dim3(128), s, c->d_out.p, c->d_cnt.p, cap, c->d_mem_off.p + b0,
+	              (uint64_t)0, nb, (const uint32_t *)nullptr, c->d_mems.p);
 	if (n_ovf > 0)
-		hipLaunchKernelGGL(sort_compact_list_kernel, dim3(grid_for(n_ovf, 64)), dim3(64), 0, s, c->d_out2.p, c->d_cnt2.p, cap2, c->d_ovf.p,
-		                   n_ovf, c->d_mem_off.p + b0, c->d_mems.p);
+		LAUNCH_EITHER(lean, sort_compact_list_kernel<true>, sort_compact_list_kernel<false>, dim3(grid_for(n_ovf, 64)), dim3(64), s, c->d_out2.p, c->d_cnt2.p, cap2, c->d_ovf.p,
+		              n_ovf, c->d_mem_off.p + b0, c->d_mems.p);
 	HIP_TRY(hipGetLastError());
 	*total_mems = new_total;
 	return CS_OK;
@@ -842,7 +849,8 @@ extern "C" int cs_engine_seed_batch_device(cs_engine_t *e, const cs_params_t *pa
 {
 	if (!e || !par || !out || n_reads < 0 || (n_reads > 0 && !d_offsets) || (n_bases > 0 && !d_bases))
 		return fail(CS_EINVAL, "cs_engine_seed_batch_device: bad argument");
-	if (n_reads >= (int64_t)0xffffffffll) return fail(CS_ERANGE, "more than 2^32-1 reads in one call");
+	if (!result_flags_ok(par)) return fail(CS_EINVAL, "unknown bits in result_flags, or reserved is not 0");
+	if (n_reads >=(int64_t)0xffffffffll) return fail(CS_ERANGE, "more than 2^32-1 reads in one call");
 	if (pipe_busy(e)) return fail(CS_EINVAL, "cs_engine_seed_batch_device: submitted batches are in flight, collect them first");
 	HIP_TRY(hipSetDevice(e->device));
 	uint64_t nm = 0, ns = 0;

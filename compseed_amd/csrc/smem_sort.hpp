@@ -16,6 +16,9 @@ __device__ __forceinline__ const OutMem &mem_at(const OutMem *src, uint32_t cap,
 // read.  A wave owns 64 consecutive reads, finds the heavy ones by ballot and rank-sorts each with all 64 lanes: lane j
 // owns mems j, j+64, ...; the keys of 64 mems at a time sit in registers and travel by shuffle.  (One lane per read made
 // this kernel as slow as its slowest read: 5 ms for a handful of reads with hundreds of mems.)
+// LEAN (here and in the two kernels below; CS_RESULT_LEAN): the sorted mems are stored with x1 = 0.  A template parameter, not an
+// argument: the <false> instantiations are the kernels as they were.
+template <bool LEAN>
 __global__ __launch_bounds__(256) void sort_compact_wave_kernel(const OutMem *raw, const uint32_t *cnt, uint32_t cap, const OvfRec *ovf, const uint32_t *ovf_key,
                                                                 const uint32_t *ovf_idx, uint64_t n_ovf, const uint64_t *mem_off, int64_t n_reads, OutMem *mems,
                                                                 uint64_t *salcnt, uint32_t max_occ)
@@ -49,6 +52,7 @@ __global__ __launch_bounds__(256) void sort_compact_wave_kernel(const OutMem *ra
 					rank += (kj < ma.info) || (kj == ma.info && b0 + (uint32_t)j < a);
 				}
 			}
+			if (LEAN) ma.x1 = 0;
 			if (a < n) { dst[rank] = ma; if (salcnt) salcnt[mem_off[r] + rank] = ma.x2 < max_occ ? ma.x2 : max_occ; } // (null: sal_expand_heavy_kernel follows)
 		}
 	}
@@ -58,6 +62,7 @@ __global__ __launch_bounds__(256) void sort_compact_wave_kernel(const OutMem *ra
 // (repeat-rich reads): lane a owns mems a, a+16, a+32, a+48.  Each mem is read once (coalesced: 16 lanes x 32 B contiguous),
 // keys travel by shuffle, and every lane writes its mems at their ranks.  Reads with more than 64 mems, or whose mems
 // spilled beyond `cap`, are left to sort_compact_wave_kernel.
+template <bool LEAN>
 __global__ __launch_bounds__(256) void sort_compact16_kernel(const OutMem *raw, const uint32_t *cnt, uint32_t cap, const uint64_t *mem_off,
                                                              int64_t n_reads, OutMem *mems, uint64_t *salcnt, uint32_t max_occ)
 {
@@ -86,7 +91,7 @@ __global__ __launch_bounds__(256) void sort_compact16_kernel(const OutMem *raw, 
 	if (n) {
 		OutMem *dst = mems + mem_off[r]; uint64_t *dsc = salcnt + mem_off[r];
 #pragma unroll
-		for (int s = 0; s < 4; ++s) if (a + 16u * s < n) { dst[rank[s]] = m[s]; dsc[rank[s]] = m[s].x2 < max_occ ? m[s].x2 : max_occ; }
+		for (int s = 0; s < 4; ++s) if (a + 16u * s < n) { if (LEAN) m[s].x1 = 0; dst[rank[s]] = m[s]; dsc[rank[s]] = m[s].x2 < max_occ ? m[s].x2 : max_occ; }
 	}
 }
 
@@ -131,6 +136,7 @@ __device__ __forceinline__ uint64_t div48_16(uint64_t x, uint32_t d)
 // sal_expand_kernel's arithmetic.  Up to SAL_LIGHT slots: by the lane that holds the mem; more: by the 16 lanes of the group, 16 slots per step.
 // m[s].x2 stays the RAW word from the load to the expansion (fm_device.hpp, MEM_POS_TAG): everything that wants x2 (sal_slots, step, the
 // `bad` check through the slot counts, mems[]) sees mem_x2() of it, and a tagged mem's one seed is put_seed_pos, not put_seed.
+template <bool LEAN>
 __global__ __launch_bounds__(256, 8) void sort_expand16_kernel(const DevIndex ix, const OutMem *raw, const uint32_t *cnt, uint32_t cap, const uint64_t *mem_off,
                                                             const uint64_t *seed_off, int64_t n_reads, OutMem *mems, OutSeed *seeds, uint32_t max_occ, unsigned long long *bad)
 {
@@ -164,7 +170,7 @@ __global__ __launch_bounds__(256, 8) void sort_expand16_kernel(const DevIndex ix
 	if (n) {
 		OutMem *dst = mems + mem_off[r];
 #pragma unroll
-		for (int s = 0; s < 4; ++s) if (a + 16u * s < n) { OutMem o = m[s]; o.x2 = mem_x2(o.x2); dst[rank[s]] = o; } // (no tag leaves the sort)
+		for (int s = 0; s < 4; ++s) if (a + 16u * s < n) { OutMem o = m[s]; o.x2 = mem_x2(o.x2); if (LEAN) o.x1 = 0; dst[rank[s]] = o; } // (no tag leaves the sort)
 	}
 	__syncthreads(); // (every thread of the block gets here: nothing above returns)
 	uint32_t total;

@@ -267,7 +267,10 @@ __global__ void mark_pending_kernel(const uint64_t *fq, const unsigned long long
 //     starts at the snapshot count, and out_cnt[r] is stored once at the end; other reads take their slots with atomics as before
 //     (the thin iterations beside the kernel may append to their lists).  One lane emits a read's seeds in order either way.
 //     The SA slots of the seeds (SplitArgs::out_scnt) add up in a register and go out as one add per read, beside the count.
-template <bool FUSED>
+//   * LEAN (CS_RESULT_LEAN): the caller reads no x1, and the reverse-strand rank ISA[seq_len - (p + k1)] of a unique k1-mer is read
+//     for nothing else, so those loads are not issued and a1 is 0 (the sort stores x1 = 0 whatever a kernel left there); C.isa counts
+//     what was asked for.
+template <bool FUSED, bool LEAN>
 __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArgs A, const uint32_t *cnt_snap, unsigned long long *n_text_seeds, const uint8_t *pending)
 {
 	const DevIndex &ix = A.ix;
@@ -369,11 +372,11 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 					vj[j] = 255u; a0[j] = a1[j] = 0;
 					if (j < ns) {
 						const uint64_t pj = p + (uint64_t)(j * k1);
-						if (FUSED) { a0[j] = isa_rep_direct(ix, pj, vj[j]); a1[j] = isa_direct(ix, ix.seq_len - (pj + (uint64_t)k1)); } // (pj + k1 <= cp + ce - cb <= seq_len)
+						if (FUSED) { a0[j] = isa_rep_direct(ix, pj, vj[j]); if (!LEAN) a1[j] = isa_direct(ix, ix.seq_len - (pj + (uint64_t)k1)); } // (pj + k1 <= cp + ce - cb <= seq_len)
 						else vj[j] = (uint32_t)ix.rep[pj];
 					}
 				}
-				if (FUSED) C.isa += 2u * (uint32_t)ns; else C.rep += (uint32_t)ns; // (single entries, one line apiece: a byte of rep[] is counted like the 8-byte loads of r2text_kernel)
+				if (FUSED) C.isa += (LEAN ? 1u : 2u) * (uint32_t)ns; else C.rep += (uint32_t)ns; // (single entries, one line apiece: a byte of rep[] is counted like the 8-byte loads of r2text_kernel)
 				int nu = 0; // leading unique k1-mers
 #pragma unroll
 				for (int j = 0; j < SPEC; ++j) if (nu == j && vj[j] < (uint32_t)k1) nu = j + 1;
@@ -382,9 +385,9 @@ __global__ __launch_bounds__(256, CS_R3_WAVES) void r3text_kernel(const SplitArg
 #pragma unroll
 						for (int j = 0; j < SPEC; ++j) {
 							const uint64_t pj = p + (uint64_t)(j * k1);
-							a0[j] = j < nu ? isa_direct(ix, pj) : 0; a1[j] = j < nu ? isa_direct(ix, ix.seq_len - (pj + (uint64_t)k1)) : 0;
+							a0[j] = j < nu ? isa_direct(ix, pj) : 0; a1[j] = !LEAN && j < nu ? isa_direct(ix, ix.seq_len - (pj + (uint64_t)k1)) : 0;
 						}
-						C.isa += 2u * (uint32_t)nu;
+						C.isa += (LEAN ? 1u : 2u) * (uint32_t)nu;
 					}
 					const uint32_t k0 = take((uint32_t)nu);
 #pragma unroll

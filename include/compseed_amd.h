@@ -65,7 +65,18 @@ typedef struct {
 	                          * profiling).  0 [default] = everything the engine was created with is used */
 	uint32_t count_traffic;  /* 1: run the instantiations of the SMEM kernels that count their index-side accesses
 	                          * (cs_engine_traffic_model); same results, a few per cent slower.  0 [default] */
+	uint32_t result_flags;   /* bit mask of CS_RESULT_*: what the caller will not read of the results.  0 [default] = everything is
+	                          * delivered; an unknown bit gives CS_EINVAL from every seed entry point */
+	uint32_t reserved;       /* must be 0 (CS_EINVAL otherwise) */
 } cs_params_t;
+
+/* cs_params_t.result_flags.  CS_RESULT_LEAN: "I will not read x0 / x1 of the mems" -- nothing behind SAL does (chaining reads x2 and
+ * info, comp_seed.cpp:241-285).  x1 then reads 0 in every mem every entry point hands out: the inverse-SA reads that only made it are
+ * not issued and the kernels that write the sorted mems store 0, so a lean result is the same whatever `disable`, `sst_mode` or the
+ * engine options are, like any other.  The packed host variants send a mem as 8 bytes instead of 16 (CS_MEM_LEAN8 below), x0 == 0
+ * after cs_unpack_mem and in cs_engine_seed_batch's arrays; in device results and where CS_MEM_FULL32 applies x0 stays as computed.
+ * mem_off, x2, info, seed_off, the seeds and the cs_stats_t counters are bit for bit those of result_flags 0. */
+#define CS_RESULT_LEAN 1u
 
 /* cs_params_t.disable: every mechanism below is exact; switching one off changes speed and counters only */
 #define CS_DISABLE_TEXT_MODE    0x01u  /* unique forward matches compared against the 2-bit text instead of the FM index      */
@@ -236,18 +247,23 @@ int  cs_engine_collect_device(cs_engine_t *e, cs_result_t *out);
  *      multi-threaded expansion into cs_intv_t / cs_seed_t arrays.  Both split the batch into sub-batches and overlap the upload
  *      of the next, the seeding of the current and the download (and expansion) of the previous one.
  *      mem_format CS_MEM_PACKED16 needs an index shorter than 2^33 symbols and reads shorter than 2^15 bases (hg19 / T2T, short
- *      reads); anything else comes back as CS_MEM_FULL32 (plain cs_intv_t); seeds as their rbeg in 40 bits either way. */
+ *      reads); anything else comes back as CS_MEM_FULL32 (plain cs_intv_t); seeds as their rbeg in 40 bits either way.
+ *      Under CS_RESULT_LEAN the mems travel as CS_MEM_LEAN8 exactly where CS_MEM_PACKED16 applies otherwise -- x2 and the two query
+ *      positions in one word, x0 = x1 = 0 after unpacking -- and as CS_MEM_FULL32 with x1 = 0 elsewhere. */
 #define CS_MEM_FULL32   0
 #define CS_MEM_PACKED16 1
+#define CS_MEM_LEAN8    2
 typedef struct { uint64_t w0, w1; } cs_mem16_t;
 /* w0 = x0 | (x2 & 0x7fffffff) << 33;   w1 = x1 | beg << 33 | end << 48 | (x2 >> 31) << 63 */
+typedef struct { uint64_t w; } cs_mem8_t;
+/* w = x2 | beg << 34 | end << 49   (x2 < 2^34: the index is shorter than 2^33 symbols; beg, end < 2^15) */
 typedef struct {
 	int64_t   n_reads;
 	uint64_t  n_mems, n_seeds;
-	int32_t   mem_format;        /* CS_MEM_PACKED16 or CS_MEM_FULL32 */
+	int32_t   mem_format;        /* CS_MEM_PACKED16 or CS_MEM_FULL32; under CS_RESULT_LEAN: CS_MEM_LEAN8 or CS_MEM_FULL32 (x1 = 0) */
 	int32_t   max_occ;           /* the -c the batch was seeded with: a mem owns min(x2, max_occ) consecutive entries of seed_rbeg */
 	const uint64_t *mem_off;     /* n_reads + 1 */
-	const void     *mems;        /* cs_mem16_t[n_mems] or cs_intv_t[n_mems] */
+	const void     *mems;        /* cs_mem16_t[n_mems], cs_mem8_t[n_mems] or cs_intv_t[n_mems], as mem_format says */
 	const uint64_t *seed_off;    /* n_reads + 1, NULL when want_sal == 0 */
 	int32_t   seed_format;       /* CS_SEED_RBEG40: a seed's rbeg as 40 bits in two planes (reference positions are below 2^37) */
 	int32_t   reserved;
@@ -279,6 +295,11 @@ static inline void cs_unpack_mem(const cs_packed_result_t *r, uint64_t i, cs_int
 		m->x0 = p.w0 & 0x1ffffffffull; m->x1 = p.w1 & 0x1ffffffffull;
 		m->x2 = (p.w0 >> 33) | ((p.w1 >> 63) << 31);
 		m->info = ((p.w1 >> 33) & 0x7fffull) << 32 | ((p.w1 >> 48) & 0x7fffull);
+	} else if (r->mem_format == CS_MEM_LEAN8) {
+		const uint64_t w = ((const cs_mem8_t *)r->mems)[i].w;
+		m->x0 = 0; m->x1 = 0;
+		m->x2 = w & 0x3ffffffffull;
+		m->info = ((w >> 34) & 0x7fffull) << 32 | ((w >> 49) & 0x7fffull);
 	} else *m = ((const cs_intv_t *)r->mems)[i];
 }
 static inline uint32_t cs_mem_seed_count(const cs_intv_t *m, int32_t max_occ) { return m->x2 < (uint64_t)max_occ ? (uint32_t)m->x2 : (uint32_t)max_occ; }
