@@ -21,7 +21,8 @@ SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", 
            "cs_engine_extend", "cs_engine_sa", "cs_engine_probe_random_lines", "cs_device_alloc", "cs_device_free", "cs_device_upload",
            "cs_device_download", "cs_device_sync", "cs_packed_seed_rbeg", "cs_engine_check_index",
            "cs_ext_params_default", "cs_extender_create", "cs_extender_destroy", "cs_extend_batch", "cs_extend_batch_device", "cs_extender_stats",
-           "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_extend_chains_device", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats"]
+           "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_extend_chains_device", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats",
+           "cs_regions_cigar", "cs_cigar_stats"]
 
 
 class CSError(RuntimeError):
@@ -195,6 +196,20 @@ class CAlnResult(C.Structure):
 
 class AlnStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("reads", "regions", "pairs", "retries", "purged", "launches", "ext_cells")] + [("ext_kernel_ms", C.c_double)]
+
+
+# cs_aln_t: a region's alignment (cs_regions_cigar); _pad is the C struct's padding before the two offsets
+ALN_DT = np.dtype([("pos", "<i8"), ("rid", "<i4"), ("is_rev", "<i4"), ("score", "<i4"), ("nm", "<i4"), ("n_cigar", "<i4"), ("w", "<i4"), ("tries", "<i4"), ("_pad", "<i4"),
+                   ("cigar_off", "<u8"), ("md_off", "<u8")])
+CIGAR_SMALL_SCRATCH = 1
+
+
+class CCigarResult(C.Structure):
+    _fields_ = [("n_regs", C.c_uint64), ("n_cigar", C.c_uint64), ("md_bytes", C.c_uint64), ("alns", C.c_void_p), ("cigar", C.c_void_p), ("md", C.c_void_p)]
+
+
+class CigarStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("regions", "dp_jobs", "nodp_jobs", "retries", "rejected", "cells", "launches")] + [("kernel_ms", C.c_double)]
 
 
 class IndexCheck(C.Structure):
@@ -402,6 +417,8 @@ def load_library():
     L.cs_dedup_params_default.argtypes = [C.POINTER(DedupParams)]
     L.cs_dedup_params_default.restype = None
     L.cs_dedup_regions.argtypes = [vp, C.POINTER(DedupParams), C.POINTER(CAlnResult), vp, vp, C.POINTER(CAlnResult), C.POINTER(vp)]
+    L.cs_regions_cigar.argtypes = [vp, C.POINTER(CAlnResult), vp, vp, C.c_uint32, C.POINTER(CCigarResult)]
+    L.cs_cigar_stats.argtypes = [vp, C.POINTER(CigarStats)]
     _lib = L
     return L
 
@@ -1035,6 +1052,30 @@ class Aligner:
         out = CAlnResult(); nc = C.c_void_p()
         _check(self.L.cs_dedup_regions(self.h, C.byref(params), C.byref(cin), bases.ctypes.data if bases.size else None, ro.ctypes.data, C.byref(out), C.byref(nc)))
         return dict(reg_off=_view(out.reg_off, "<u8", int(out.n_reads) + 1, copy), regs=_view(out.regs, ALNREG_DT, int(out.n_regs), copy), n_comp=_view(nc.value, "<i4", int(out.n_regs), copy))
+
+    def regions_cigar(self, reg_off, regs, bases, read_offsets, flags=0):
+        """cs_regions_cigar (mem_reg2aln without primary marking, MAPQ and SAM text): regions as extend_chains or dedup_regions return them ->
+        dict(alns: one ALN_DT record per region, cigar: uint32 in BAM coding, md: the NUL-terminated strings), copies.  Regions that
+        bridge the strands come back empty with nm = -1 and the call raises CSError(-1) AFTER the others were made: the exception
+        carries them as `.result`."""
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.uint64); regs = np.ascontiguousarray(regs, dtype=ALNREG_DT)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8); ro = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+        cin = CAlnResult(reg_off.size - 1, regs.size, reg_off.ctypes.data, regs.ctypes.data if regs.size else None)
+        out = CCigarResult()
+        rc = self.L.cs_regions_cigar(self.h, C.byref(cin), bases.ctypes.data if bases.size else None, ro.ctypes.data, int(flags), C.byref(out))
+        res = None
+        if out.alns or (rc == 0 and out.md):
+            res = dict(alns=_view(out.alns, ALN_DT, int(out.n_regs), True), cigar=_view(out.cigar, "<u4", int(out.n_cigar), True), md=_view(out.md, "u1", int(out.md_bytes), True))
+        if rc != 0:
+            e = CSError(rc, self.L.cs_last_error().decode(errors="replace"))
+            e.result = res if res is not None and int(res["alns"].size) == regs.size and bool((res["alns"]["nm"] == -1).any()) else None
+            raise e
+        return res
+
+    def cigar_stats(self):
+        st = CigarStats()
+        _check(self.L.cs_cigar_stats(self.h, C.byref(st)))
+        return {n: (float(getattr(st, n)) if n == "kernel_ms" else int(getattr(st, n))) for n, _ in CigarStats._fields_}
 
     def stats(self):
         st = AlnStats()

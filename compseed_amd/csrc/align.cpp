@@ -22,6 +22,7 @@ struct cs_aligner {
 	std::vector<uint64_t> reg_off; std::vector<cs_alnreg_t> regs;
 	std::vector<uint64_t> dd_off; std::vector<cs_alnreg_t> dd_regs; std::vector<int32_t> dd_ncomp;   // cs_dedup_regions' result
 	cs_aln_stats_t st{};
+	cs_cigar_gpu *cig = nullptr;          // the device side of cs_regions_cigar (cigar_gpu.hip), with its result
 };
 
 
@@ -65,6 +66,7 @@ extern "C" void cs_aligner_destroy(cs_aligner_t *A)
 {
 	if (!A) return;
 	if (A->gpu) cs_aligner_gpu_release_(A->gpu);
+	if (A->cig) cs_cigar_gpu_release_(A->cig);
 	if (A->ext) cs_extender_destroy(A->ext);
 	delete A;
 }
@@ -114,6 +116,23 @@ extern "C" int cs_dedup_regions(cs_aligner_t *A, const cs_dedup_params_t *par, c
 	out->n_reads = regs->n_reads; out->n_regs = A->dd_regs.size(); out->reg_off = A->dd_off.data(); out->regs = A->dd_regs.data();
 	if (n_comp) *n_comp = A->dd_ncomp.data();
 	return CS_OK;
+}
+
+// from regions to CIGAR / NM / MD (mem_reg2aln without primary marking, MAPQ and SAM text): only what the host can know is checked here,
+// the arrays are checked by a kernel (cigar_gpu.hip)
+extern "C" int cs_regions_cigar(cs_aligner_t *A, const cs_aln_result_t *regs, const uint8_t *bases, const uint64_t *read_offsets, uint32_t flags, cs_cigar_result_t *out)
+{
+	if (!A || !regs || !out) return cs_fail_(CS_EINVAL, "cs_regions_cigar: null argument");
+	if (flags & ~CS_CIGAR_SMALL_SCRATCH) return cs_fail_(CS_EINVAL, "cs_regions_cigar: unknown flags");
+	if (regs->n_reads < 0 || (regs->n_reads > 0 && (!regs->reg_off || !read_offsets)) || (regs->n_regs > 0 && (!regs->regs || !bases))) return cs_fail_(CS_EINVAL, "cs_regions_cigar: bad argument");
+	if (A->device < 0) return cs_fail_(CS_EDEVICE, "cs_regions_cigar: this aligner was created without a device (device -1): the alignments are made on the GPU only");
+	if (regs->n_regs >= 0xffffffffull || regs->n_reads >= 0xffffffffll) return cs_fail_(CS_ERANGE, "cs_regions_cigar: 2^32 regions or reads or more in one call");
+	return cs_regions_cigar_gpu_(&A->cig, A->device, A->ref, A->pac, A->par, regs, bases, read_offsets, flags, out);
+}
+extern "C" int cs_cigar_stats(const cs_aligner_t *A, cs_cigar_stats_t *st)
+{
+	if (!A || !st) return cs_fail_(CS_EINVAL, "null argument");
+	return cs_cigar_gpu_stats_(A->cig, st);
 }
 
 extern "C" int cs_aligner_stats(const cs_aligner_t *A, cs_aln_stats_t *st)

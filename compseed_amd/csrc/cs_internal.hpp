@@ -72,6 +72,13 @@ int cs_extend_chains_device_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t 
                                  const cs_chain_result_t *d_chains, const int32_t *d_cseed_score, const uint8_t *d_bases, const uint64_t *d_read_offsets, uint32_t flags,
                                  cs_aln_result_t *d_out, cs_aln_stats_t &st);
 
+// the device side of cs_regions_cigar (cigar_gpu.hip): from regions to CIGAR, NM and MD; made by the first call
+struct cs_cigar_gpu;
+void cs_cigar_gpu_release_(cs_cigar_gpu *g);
+int cs_cigar_gpu_stats_(const cs_cigar_gpu *g, cs_cigar_stats_t *st);
+int cs_regions_cigar_gpu_(cs_cigar_gpu **gp, int device, const cs_refseq_view &R, const std::vector<uint8_t> &pac, const cs_aln_params_t &o, const cs_aln_result_t *regs,
+                          const uint8_t *bases, const uint64_t *read_offsets, uint32_t flags, cs_cigar_result_t *out);
+
 // ---- the host passes' work sharing: fn(k) for k in [0, n_chunks) on T threads, chunks of reads handed out by a counter.  (A read inside a
 // repeat costs a hundred times the average in the quadratic passes -- chain filter, dedup --; equal shares left fifteen threads waiting for
 // the one that drew them: cs_chain_filter 107 -> 40 ms per million reads on 16 threads.)

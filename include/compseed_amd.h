@@ -501,6 +501,28 @@ void cs_dedup_params_default(cs_dedup_params_t *p);
 int  cs_dedup_regions(cs_aligner_t *a, const cs_dedup_params_t *par, const cs_aln_result_t *regs, const uint8_t *bases, const uint64_t *read_offsets,
                       cs_aln_result_t *out, const int32_t **n_comp);
 int  cs_aligner_stats(const cs_aligner_t *a, cs_aln_stats_t *st);
+/* From regions to alignments on the GPU: what the reference does with every region it reports (mem_reg2aln, comp_seed.cpp:811-880, without
+ * primary marking, MAPQ and SAM text, which stay the caller's) -- the band inferred from the region, the banded global alignment with
+ * backtrack (bwa_gen_cigar2 / ksw_global2) up to three times with a doubled band, NM and MD, a leading or else a trailing deletion
+ * squeezed out, the soft clips, and the position in contig coordinates.  Host arrays in (`regs`: cs_extend_chains' or cs_dedup_regions'
+ * result, or the caller's regions in that form; `bases` / `read_offsets`: the reads); host arrays owned by the aligner out, valid until
+ * its next cs_regions_cigar.  One cs_aln_t per input region, in input order: `score` the last try's global score, `w` / `tries` that
+ * try's band (mem_reg2aln's w2) and number; `cigar[cigar_off, cigar_off + n_cigar)` in BAM coding (len << 4 | op; M 0, I 1, D 2, S 3);
+ * `md + md_off` a NUL-terminated string.  The CIGARs lie in the order in which the pass finished them, not in region order: only the
+ * offsets say where.  A purged region (qe <= qb) or an unmapped one (rb < 0 or re < 0) gives an empty result: rid = pos = -1,
+ * n_cigar = 0, nm = 0, md_off at an empty string.  Scoring and w are the aligner's cs_aln_params_t.  Errors, in this order: a NULL `a`,
+ * `regs` or `out`, or unknown flag bits CS_EINVAL; NULL arrays where the counts say there are entries CS_EINVAL; an aligner created with
+ * device -1 CS_EDEVICE; 2^32 regions or reads or more CS_ERANGE; inconsistent input -- reg_off / read_offsets that are not CSR offset
+ * arrays from 0, a read with regions of 65,536 bases or more, a live region outside its read or outside [0, 2 l_pac) or spanning more
+ * than 131,072 reference bases -- CS_EINVAL, found by a checking kernel before any kernel follows an offset; regions that
+ * bwa_gen_cigar2 rejects (they bridge the strands) are delivered empty with nm = -1, and the call returns CS_EINVAL after delivering the
+ * others.  After any error the aligner is usable for the next call. */
+#define CS_CIGAR_SMALL_SCRATCH 1u   /* tests: a backtrack-matrix budget of 64 KiB per chunk of jobs instead of 256 MiB; the same alignments */
+typedef struct { int64_t pos; int32_t rid, is_rev, score, nm, n_cigar, w, tries; uint64_t cigar_off, md_off; } cs_aln_t;
+typedef struct { uint64_t n_regs, n_cigar, md_bytes; const cs_aln_t *alns; const uint32_t *cigar; const char *md; } cs_cigar_result_t;
+typedef struct { uint64_t regions, dp_jobs, nodp_jobs, retries, rejected, cells, launches; double kernel_ms; } cs_cigar_stats_t;
+int  cs_regions_cigar(cs_aligner_t *a, const cs_aln_result_t *regs, const uint8_t *bases, const uint64_t *read_offsets, uint32_t flags, cs_cigar_result_t *out);
+int  cs_cigar_stats(const cs_aligner_t *a, cs_cigar_stats_t *st);
 
 /* ---- the result of the LAST device-variant call, without moving it: an order-sensitive 64-bit digest per array
  *      (sum over the array's 64-bit words w[i] of splitmix64(w[i] + i * 0x9E3779B97F4A7C15), mod 2^64), so that two runs over

@@ -6,6 +6,8 @@ seeding of the batch), both checked equal to the host chains over the whole batc
 cs_chain_filter_device (fed by the device chain call's result) and cs_chain_filter_gpu (host arrays), both checked equal to the host filter.
 Beside the host extend_chains row: cs_extend_chains_device on the device filter's result, with every region kept and with the purged ones
 left behind (CS_ALN_DEV_COMPACT), each with the time download_regions takes; checked equal to the host call's regions / its regions with qe > qb.
+Behind dedup_regions: "regions -> CIGAR", cs_regions_cigar over the de-duplicated regions (host arrays in and out), wall time as ms per million
+reads, with the device span and the job counts of cs_cigar_stats; nothing in the reference is timed separately to compare it with.
 usage: align_bench.py [reads] [--synth-mbp M]"""
 import gzip, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,6 +80,7 @@ def run(n=200000, synth_mbp=0.0):
         g = al.extend_chains(f["chain_off"], f["chains"], f["cseed_off"], f["cseeds"], bases, off, cseed_score=f["cseed_score"], copy=False); t4 = time.perf_counter()
         st1 = al.stats()
         d = al.dedup_regions(g["reg_off"], g["regs"], bases, off, copy=False); t5 = time.perf_counter()
+        cs0 = al.cigar_stats(); tc0 = time.perf_counter(); cg_res = al.regions_cigar(d["reg_off"], d["regs"], bases, off); tc1 = time.perf_counter(); cs1 = al.cigar_stats()
         # the chain pass on the GPU: host arrays in and out (PCIe both ways), then from the engine's device result (seeded once more)
         t6 = time.perf_counter(); cg = chd.chain_gpu(res.mem_off, res.mems, res.seed_off, res.seeds, off, ca.ChainParams(), copy=False); t7 = time.perf_counter()
         assert same(cg, c), "cs_chain_batch_gpu differs from cs_chain_batch"
@@ -124,6 +127,12 @@ def run(n=200000, synth_mbp=0.0):
     kms = st1["ext_kernel_ms"] - st0["ext_kernel_ms"]
     out["extension_kernels"] = {"ms": kms, "pairs_per_s": (st1["pairs"] - st0["pairs"]) / (kms * 1e-3) if kms > 0 else None, "dp_cells_per_pair": (st1["ext_cells"] - st0["ext_cells"]) / max(1, st1["pairs"] - st0["pairs"]),
                                 "note": "the extension kernels alone (HIP events) on this run's own pairs: extensions of real chains die at different rows, unlike the uniform pairs of tools/extend_bench.py"}
+    cd = {k: cs1[k] - cs0[k] for k in cs1}
+    out["regions -> CIGAR"] = {"ms": 1e3 * (tc1 - tc0), "reads_per_s": n / (tc1 - tc0), "ms_per_million_reads": 1e3 * (tc1 - tc0) * 1e6 / n, "device_span_ms": cd["kernel_ms"],
+                               "regions": cd["regions"], "dp_jobs": cd["dp_jobs"], "nodp_jobs": cd["nodp_jobs"], "retries": cd["retries"], "dp_cells": cd["cells"], "launches": cd["launches"],
+                               "cigar_ops": int(cg_res["cigar"].size), "md_bytes": int(cg_res["md"].size),
+                               "note": "a first measurement: host arrays in and out, the binding's copies of the result included; device_span_ms runs from the first kernel to the last and "
+                                       "includes the copies and host waits between them; not part of behind_seeding_reads_per_s"}
     t_all = sum(out[k]["ms"] for k in ("chain", "chain_filter", "extend_chains", "dedup_regions"))
     out["behind_seeding_reads_per_s"] = n / (t_all * 1e-3)
     if tmpdir:
