@@ -2,6 +2,7 @@
 // scheme (bwd_win0_kernel, bwd_win_kernel, bwd_wide_kernel).  Overview: smem_common.hpp.
 #pragma once
 #include "smem_common.hpp"
+#include "lane_sets.hpp"
 
 namespace csd {
 
@@ -138,7 +139,7 @@ __device__ __forceinline__ void bwd_groups_run(const SplitArgs &A, const BTask *
 // stores no others under this scheme); each walks alone from the pivot.  ~16 table reads + ~40 extensions, 5 deep,
 // replace 136 extensions, 17 deep; results identical.
 //
-// A group of G lanes per call: lanes 0..17 take the ends x+1 .. x+18, lanes 18.. take the stored LEPs in ascending order.
+// A set of lanes per call: its first 18 lanes take the ends x+1 .. x+18, the following ones the stored LEPs in ascending order.
 // in two halves: the filter (does the end's min_seed_len-mer occur at all? -> its jump-table code), and the table lookup
 template <class WC>
 __device__ __forceinline__ bool win_lane_filter(const SplitArgs &A, PackedReader &rd, uint32_t gl, int x, int ret, uint32_t &code, WC &W)
@@ -176,70 +177,87 @@ __device__ __forceinline__ bool win_lane_init(const SplitArgs &A, PackedReader &
 	return win_lane_filter(A, rd, gl, x, ret, code, W) && win_lane_jump(A, code, x + 1 + (int)gl, min_intv, e, pend, s, my_q, my_hits, W);
 }
 
-template <int G, class WC>
+// Lanes by need, not by group: a call with n stored LEPs takes 18 + n lanes, any free ones (lane_sets.hpp).  The wave keeps a
+// wave-uniform mask F of the lanes that belong to no call; a lane keeps the lane set of its call (gmask, 0: free) and finds its place
+// by its rank in that set -- ranks 0..17 are the window lanes, rank 18 + j is LEP j.  The loop below addresses a call only through
+// gmask-masked ballots and the next higher member of a ballot, so the lanes of a call need not be contiguous or aligned.  Calls are
+// taken in queue order (both classes, 4 and 5, from one slot counter: one scan of the queue); the next call waits until F holds 18 + n
+// lanes, which an empty wave always does.  Placement is tried at loop entry and in iterations after F changed, never on the common path.
+// CS_WIN_RELEASE: lanes that cannot matter any more (valid == false: the filter or the jump lookup failed, or the equal-size rule
+// stopped them) go back to F at once, all but the call's rank 0, which pushes the call's successor at its end.  A lane that stopped
+// with valid == true holds f and e for the first-survivor rule and stays to the end of its call.
+#ifndef CS_WIN_RELEASE
+#define CS_WIN_RELEASE 1
+#endif
+template <class WC>
 __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq, uint64_t n_tasks, unsigned long long *ctr, WaveOut &O,
-                                            unsigned long long &my_q, unsigned long long &my_hits, WC &W)
+                                            unsigned long long &my_q, unsigned long long &my_hits, uint8_t *slot_w, WC &W)
 {
-	constexpr uint32_t MYCLS = G == 32 ? 4u : 5u;
 	const DevIndex &ix = A.ix;
-	const uint32_t lane = threadIdx.x & 63u, gl = lane % G, gbase = lane - gl;
-	const uint64_t gmask = (G >= 64) ? ~0ull : (((1ull << (G & 63)) - 1ull) << gbase);
-	bool active = false, walking = false, valid = false;
+	const uint32_t lane = threadIdx.x & 63u;
+	uint64_t gmask = 0;
+	bool walking = false, valid = false;
 	uint32_t r = 0, kind = 0, min_intv = 1, pend = 0;
 	int s = 0, f = 0, ret = 0, xp = 0, clk = 0;
 	Intv e = {0, 0, 0};
 	PackedReader rd;
-	uint64_t batch_base = 0, avail_m = 0; bool exhausted = false;
-	for (;;) { // task acquisition exactly as in bwd_groups_run
-		uint64_t idle_m = __ballot(!active && gl == 0);
-		if (idle_m != 0 && avail_m == 0 && !exhausted) {
-			int src = __ffsll((long long)idle_m) - 1;
-			unsigned long long base = 0;
-			if ((int)lane == src) base = atomicAdd(ctr, 64ull);
-			base = __shfl(base, src);
-			if (base >= n_tasks) exhausted = true;
-			else {
-				uint64_t slot = base + lane;
-				uint32_t cls = slot < n_tasks ? bq[slot].cls : 0xffffffffu;
-				avail_m = __ballot(cls == MYCLS);
-				batch_base = base;
+	// wave-uniform: the free lanes, the 64 slots drawn last and which of them still wait, and the lanes the next placement needs
+	// (18 + n of the call at the head once known, 19 before -- no call takes fewer --, 65 when the queue is used up)
+	uint64_t F = ~0ull, batch_base = 0, avail_m = 0; bool exhausted = false, place = true; uint32_t need = WIN_LANES + 1;
+	for (;;) {
+		if (place && csls::count(F) >= need) {
+			bool fresh = false; uint64_t t = 0;
+			for (;;) {
+				if (avail_m == 0) {
+					if (exhausted) { need = 65; break; }
+					unsigned long long base = 0;
+					if (lane == 0) base = atomicAdd(ctr, 64ull);
+					base = (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)base) | (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32;
+					if (base >= n_tasks) { exhausted = true; need = 65; break; }
+					const uint64_t slot = base + lane;
+					uint32_t cls = 0xffffffffu, n = 0;
+					if (slot < n_tasks) { cls = bq[slot].cls; n = bq[slot].n; }
+					avail_m = __ballot(cls == 4u || cls == 5u);  // (n <= WIN_G64_LEPS: 18 + n <= 64)
+					batch_base = base;
+					__builtin_amdgcn_wave_barrier();             // (the previous draw's widths have all been read)
+					slot_w[lane] = (uint8_t)(WIN_LANES + n);
+					__builtin_amdgcn_wave_barrier();
+					continue;
+				}
+				const int k = __ffsll((long long)avail_m) - 1;
+				const uint32_t w = __builtin_amdgcn_readfirstlane((uint32_t)slot_w[k]);
+				if (csls::count(F) < w) { need = w; break; } // the head of the queue waits for lanes; nothing overtakes it
+				const bool join = csls::takes(F, lane, w);
+				const uint64_t take = __ballot(join);
+				if (join) { gmask = take; t = batch_base + (uint64_t)k; fresh = true; }
+				F = csls::release(F, take); avail_m &= avail_m - 1; need = WIN_LANES + 1;
 			}
-		}
-		if (idle_m != 0 && avail_m != 0) {
-			int kth = __popcll(idle_m & ((1ull << gbase) - 1ull));
-			uint64_t m = avail_m;
-			for (int q = 0; q < kth; ++q) m &= m - 1;
-			bool mine = !active && m != 0;
-			uint64_t t = batch_base + (uint64_t)(__ffsll((long long)m) - 1);
-			int taken = __popcll(idle_m), have = __popcll(avail_m);
-			if (taken > have) taken = have;
-			for (int q = 0; q < taken; ++q) avail_m &= avail_m - 1;
-			if (mine) {
+			if (fresh) {
+				const uint32_t gl = csls::rank_in(gmask, lane);
 				BTask bt = bq[t];
 				r = bt.r; kind = bt.mi_kind >> 14; min_intv = bt.mi_kind & 0x3fffu; ret = bt.ret; xp = bt.x;
-				const int n = bt.n;
 				const uint64_t rb = A.off[r];
 				f = 0x7fffffff;
 				rd.start(A.seqp, rb, r, xp);
 				if (gl < (uint32_t)WIN_LANES) valid = win_lane_init(A, rd, gl, xp, ret, min_intv, e, pend, s, my_q, my_hits, W);
-				else {
-					int j = (int)gl - WIN_LANES;
-					valid = j < n;
-					if (valid) { unpack_lep(A.lep[(size_t)t * A.lep_stride + j], e, pend); s = xp - 1; wc_add(W, EV_LEP); }
+				else { // (the set has exactly 18 + n members: every rank from 18 on has its LEP)
+					unpack_lep(A.lep[(size_t)t * A.lep_stride + ((int)gl - WIN_LANES)], e, pend); s = xp - 1; wc_add(W, EV_LEP);
+					valid = true;
 				}
 				walking = valid;
 				clk = xp + WIN_LANES - A.jump_k - 1; // the base in front of the last window lane, the first to join
 				if (clk < xp - 1) clk = xp - 1;        // (the LEP lanes join at the pivot)
-				active = true;
 			}
 		}
-		if (exhausted && avail_m == 0 && __ballot(active) == 0) break; // wave-uniform exit
+		place = false;
+		if (exhausted && avail_m == 0 && F == ~0ull) break; // wave-uniform exit
 		uint64_t push0 = FTASK_NONE, push1 = FTASK_NONE, aux0 = AUX_NONE;
 #ifdef CS_STEP_HIST
-		W.steps((uint32_t)__popcll(__ballot(active && walking && s == clk)));
+		W.steps((uint32_t)__popcll(__ballot(gmask != 0 && walking && s == clk)));
 #endif
-		if (active) {
-			// One clock per group: position clk is the read base every walking lane prepends in this iteration.  A lane joins
+		bool ended = false;
+		if (gmask != 0) {
+			// One clock per call: position clk is the read base every walking lane prepends in this iteration.  A lane joins
 			// when the clock reaches the base in front of its match (the window lanes start staggered, the LEPs at the pivot),
 			// so all lanes that walk hold matches with the SAME start, and the equal-size rule of bwt.c:337-340 applies to
 			// them as it stands: a match with as many occurrences as the next longer walking one has the same occurrences,
@@ -256,21 +274,27 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 			if ((clk & 3) == 0) { // (every fourth step is enough: a lane that could have stopped earlier only repeats a few extensions)
 				const bool surv = step && walking;
 				const uint64_t lm = __ballot(surv) & gmask;
-				const uint64_t above = lane == 63 ? 0ull : lm & ~((2ull << lane) - 1ull);
-				const int asrc = above ? __ffsll((long long)above) - 1 : (int)lane;
-				const uint64_t ax2 = __shfl(e.x2, asrc);
-				if (surv && above && ax2 == e.x2) { walking = false; valid = false; }
+				const uint64_t ax2 = __shfl(e.x2, (int)csls::next_member(lm, lane));
+				if (surv && (lm & csls::above(lane)) && ax2 == e.x2) { walking = false; valid = false; }
 			}
 			--clk;
 			if ((__ballot(walking) & gmask) == 0) { // all ends of this call are settled: apply the first-survivor rule
-				uint64_t vm = __ballot(valid) & gmask;
-				uint64_t higher = lane == 63 ? 0ull : vm & ~((2ull << lane) - 1ull);
-				int src = higher ? __ffsll((long long)higher) - 1 : (int)lane;
-				int fn = __shfl(f, src);
+				const uint64_t vm = __ballot(valid) & gmask, higher = vm & csls::above(lane);
+				const int fn = __shfl(f, (int)csls::next_member(vm, lane));
 				if (valid && (higher == 0 || f < fn)) push0 = emit_smem(A, r, kind, e, f + 1, pend, aux0);
-				if (kind == TK_ROUND1 && gl == 0) push1 = chain_round1(rd, r, (int)(A.off[r + 1] - A.off[r]), ret, xp);
-				active = false; valid = false;
+				if (kind == TK_ROUND1 && csls::rank_in(gmask, lane) == 0) push1 = chain_round1(rd, r, (int)(A.off[r + 1] - A.off[r]), ret, xp);
+				ended = true; valid = false;
 			}
+		}
+		// lanes that go back to F: those of the calls that ended, and (CS_WIN_RELEASE) those that can no longer matter
+#if CS_WIN_RELEASE
+		const uint64_t gone = __ballot(ended || (gmask != 0 && !valid && csls::rank_in(gmask, lane) != 0));
+#else
+		const uint64_t gone = __ballot(ended);
+#endif
+		if (gone) {
+			F |= gone; place = true;
+			gmask = csls::has(gone, lane) ? 0ull : csls::release(gmask, gone);
 		}
 		if (__ballot((push0 & push1) != FTASK_NONE)) { // (a call ends once in ~20 iterations: keep the dispenser code off the common path)
 			wave_push<32>(O, push0 != FTASK_NONE, push0, A, aux0);
@@ -590,21 +614,16 @@ __global__ __launch_bounds__(BLOCK, CS_WIN0_WAVES) void bwd_win0_kernel(const Sp
 	wc_flush(W, A.evc, KID_BWD_WIN0);
 }
 
-// window scheme: ctrs[0] / ctrs[1] are the slot counters of the classes with up to 14 / 46 stored LEPs
+// window scheme: the calls with 1 to 46 stored LEPs, all from the one slot counter ctrs[0]
 template <int BLOCK, bool COUNT>
 __global__ __launch_bounds__(BLOCK, CS_WIN_WAVES) void bwd_win_kernel(const SplitArgs A, const BTask *bq, uint64_t n_tasks, unsigned long long *ctrs)
 {
 	if (*A.n_btasks == 0) return;
+	__shared__ uint8_t slot_w[BLOCK / 64][64]; // per wave: the lanes each of the 64 slots drawn last needs
 	WaveOut O = {0, 0};
 	WaveCtrT<COUNT> W;
 	unsigned long long my_q = 0, my_hits = 0;
-	if ((blockIdx.x & 7u) != 7u) {
-		bwd_win_run<32>(A, bq, n_tasks, ctrs + 0, O, my_q, my_hits, W);
-		bwd_win_run<64>(A, bq, n_tasks, ctrs + 1, O, my_q, my_hits, W);
-	} else {
-		bwd_win_run<64>(A, bq, n_tasks, ctrs + 1, O, my_q, my_hits, W);
-		bwd_win_run<32>(A, bq, n_tasks, ctrs + 0, O, my_q, my_hits, W);
-	}
+	bwd_win_run(A, bq, n_tasks, ctrs, O, my_q, my_hits, slot_w[threadIdx.x >> 6], W);
 	wave_push_finish(O, A);
 	atomicAdd(A.n_queries, my_q);
 	if (my_hits) atomicAdd(A.n_sst_hits, my_hits);

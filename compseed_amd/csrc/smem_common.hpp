@@ -10,7 +10,8 @@
 //                read when round 3 runs on the index only.  Starts from the k-mer jump table, leaves the index for the
 //                2-bit text once the match is unique, finishes calls whose sweep is trivial or can be read off the text.
 //   bwd_win0_kernel / bwd_win_kernel / bwd_wide_kernel   the backward sweeps under the window scheme (default): short match
-//                ends are settled through the jump table, stored LEPs walk in groups of 32/64 lanes on one clock.
+//                ends are settled through the jump table, stored LEPs walk on one clock per call; in bwd_win_kernel a call takes the
+//                18 + n lanes it needs, any free ones of its wave (lane_sets.hpp).
 //   bwd_all_kernel   the literal sweep (bwt.c:325-345), a GROUP of G lanes (16/32/64) per call; lane g holds LEP n-1-g in
 //                registers; every step extends ALL live intervals at once and the reference's sequential keep/emit rules
 //                are evaluated with a ballot and one shuffle: occurrence counts are monotone along the list (a longer
@@ -36,7 +37,8 @@ namespace csd {
 
 enum : uint32_t { TK_ROUND1 = 0, TK_ROUND2 = 1, TK_ROUND3 = 2, TK_NOP = 3, TK_TEXT = 4 /* fwd_kernel-internal: a round-1 call in text mode */ };
 
-// window scheme (bwd_win_run): lanes 0..WIN_LANES-1 of a group hold the short matches, the rest hold LEPs
+// window scheme (bwd_win_run): ranks 0..WIN_LANES-1 of a call's lane set hold the short matches, the rest hold LEPs; the size classes
+// 4 (up to WIN_G32_LEPS stored LEPs) and 5 (up to WIN_G64_LEPS: 64 lanes) are both bwd_win_kernel's
 constexpr int WIN_LANES = 18, WIN_G32_LEPS = 32 - WIN_LANES, WIN_G64_LEPS = 64 - WIN_LANES;
 
 // forward task, 8 bytes: read | pivot | min_intv | kind
