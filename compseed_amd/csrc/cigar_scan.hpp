@@ -1,8 +1,8 @@
 // cigar_scan.hpp -- mem_reg2aln for ONE region (comp_seed.cpp:811-880: the band and its retries, bwa_gen_cigar2 of bwalib/bwa.c:147-233,
 // ksw_global2 of bwalib/ksw.c:504-606 with its backtrack, NM and MD, the squeezed deletion, the clips, the contig-relative position), as
 // bodies a device pass (cigar_gpu.hip) and a plain C++ program (tests/cpp/cigar_scan_check.cpp: W = 1 over the goldens, W = 8 / 64 on
-// threads in lockstep) run alike.  The lane primitives are dedup_scan.hpp's CSD_ macros, and so are Span / span_q / span_t, sc_mat,
-// wprefix_max and the band formula.  In the order of the pass:
+// threads in lockstep) run alike.  The lane primitives are wave_lanes.hpp's; Span / span_q / span_t, sc_mat and banded_global_score,
+// which global_fill restates with the backtrack matrix beside it, are band_align.hpp's.  In the order of the pass:
 //   check_read     a lane per read: the offsets are CSR arrays, a read with regions is shorter than MAX_READ_LEN, a live mapped region lies
 //                  inside its read and inside [0, 2 l_pac) and spans at most 2 MAX_READ_LEN of the reference; rd[g] = the region's read.
 //                  The lane compares its own entries BEFORE it walks [reg_off[r], reg_off[r + 1]); nothing else follows an offset before
@@ -21,7 +21,8 @@
 // No body waits for another lane's memory: order comes from the kernel boundaries (or from the wave's own barrier inside global_fill).
 // Float and double expressions are the reference's, operand for operand; the units that include this are compiled with -ffp-contract=off.
 #pragma once
-#include "dedup_scan.hpp"
+#include "band_align.hpp"
+#include "wave_lanes.hpp"
 
 namespace cscg {
 using csdd::NEG; using csdd::NO_G; using csdd::Span; using csdd::sc_mat; using csdd::span_q; using csdd::span_t; using csdd::wprefix_max; using csdd::wsum; using csdd::wsync;
@@ -125,11 +126,11 @@ CS_HD inline uint64_t job_bytes(const cs_aln_params_t &o, const cs_alnreg_t &x, 
 template <int W> CS_HD int sum_score(const Span &S, const cs_aln_params_t &o, int lane)   // bwa.c:174-175
 {
 	int sc = 0;
-	for (int i = lane; i < S.qlen; i += W) sc += sc_mat(o, span_t(S, i), span_q(S, i));
+	for (int i = lane; i < S.qlen; i += W) sc += sc_mat(o.a, o.b, span_t(S, i), span_q(S, i));
 	return wsum<W>(sc);
 }
 
-// banded_global_score (dedup_scan.hpp) with ksw_global2's backtrack matrix: row i holds n_col bytes at z + i * n_col, column j at j - beg.
+// banded_global_score (band_align.hpp) with ksw_global2's backtrack matrix: row i holds n_col bytes at z + i * n_col, column j at j - beg.
 // The byte is the reference's (ksw.c:551-565): bits 0-1 the direction of H, bit 2 "E continues", bit 5 "F continues"; `f` is the F the
 // cell itself used, which the prefix maximum gives every lane at once.  H and E hold qlen + 1 words each.
 template <int W> CS_HD int global_fill(const Span &S, int tlen, const cs_aln_params_t &o, int w, int32_t *H, int32_t *E, uint8_t *z, int lane)
@@ -154,7 +155,7 @@ template <int W> CS_HD int global_fill(const Span &S, int tlen, const cs_aln_par
 			const int j = s + lane;
 			const bool in = j < end;
 			int32_t m = NEG, e = NEG;
-			if (in) { m = (lane == 0 && s > beg ? next_h : H[j]) + sc_mat(o, tb, span_q(S, j)); e = E[j]; }
+			if (in) { m = (lane == 0 && s > beg ? next_h : H[j]) + sc_mat(o.a, o.b, tb, span_q(S, j)); e = E[j]; }
 			if (s + W < end) next_h = H[s + W];
 			const int64_t g = in ? (int64_t)m + (int64_t)e_ins * j : NO_G;
 			const int64_t gx = wprefix_max<W>(g, lane, carry);

@@ -11,21 +11,16 @@
 //     p.score >= q.score gets q.qe = q.qb; the event is handled and the step restarts at j - 1 with the possibly merged `p` (a merge
 //     moves p.rb, so the end condition is evaluated per candidate against the current p, never cached).  Between two events `p` is
 //     constant and each `j` writes only its own `q`: that is the host's order;
-//   * the global alignment of a patch (banded_global_score of dedup.cpp, ksw_global2's score): rows = reference, in place in H and E as
-//     the host keeps them, a column per lane in strips of W.  Gaps open from the diagonal move only, so within a row neither E nor F
-//     depends on the row's own H: F(j) = max(NEG - e_ins (j - beg), max_{k<j} m(k) - oe_ins - e_ins (j - 1 - k)) is a prefix maximum
-//     of m(k) + e_ins k over the row, carried from strip to strip -- integer maxima, exact in any order.  The band's clipping, H[end] = h1,
-//     E[end] = NEG, the first column only while beg == 0 and the first row up to w are the host's.  Bases come from the read and from
-//     the packed reference on the fly (3 - base of the mirrored position on the reverse strand; both reversed when rb >= l_pac).
+//   * the global alignment of a patch is banded_global_score of band_align.hpp, a column per lane in strips of W; the lanes themselves --
+//     wsync, wballot, wbcast, wsum, wprefix_max, lanes_below and the CSD_ macros under them -- are wave_lanes.hpp's.  Both headers were
+//     split out of this one, which keeps what belongs to de-duplication; they keep its namespace.
 // Float and double expressions are the host's, operand for operand; the units that include this are compiled with -ffp-contract=off.
 #pragma once
-#include "cs_internal.hpp"
+#include "band_align.hpp"
 #include "klib_sort.hpp"
+#include "wave_lanes.hpp"
 
 namespace csdd {
-constexpr int32_t NEG = -0x40000000;          // MINUS_INF (ksw.c:490)
-constexpr int64_t NO_G = INT64_MIN / 2;       // "no column before this one" in the prefix maximum
-
 struct Par { cs_aln_params_t o; cs_dedup_params_t d; int64_t l_pac; const uint8_t *pac; };
 struct SRec { int64_t k0; int32_t k1, k2, idx; };                 // first sort: k0 = re; second: k0 = rb, k1 = score, k2 = qb
 struct ByEnd { CS_HD bool operator()(const SRec &x, const SRec &y) const { return x.k0 < y.k0; } };                                                   // alnreg_slt2
@@ -33,126 +28,6 @@ struct ByScore { CS_HD bool operator()(const SRec &x, const SRec &y) const { ret
 // the alignment's rows: `lds` holds 2 * lds_rows words (0: none), `hbm` 2 * (the read's length + 1)
 struct Work { int32_t *lds; int lds_rows; int32_t *hbm; };
 struct Stat { uint32_t aligns = 0, merges = 0; };
-
-// ---- the W lanes: shuffles and ballots of a wave, or nothing at all.  A plain C++ program may define the CSD_ macros before it includes
-// this header and run the W > 1 instantiations on lanes of its own (tests/cpp/dedup_scan_check.cpp: threads in lockstep); in device code
-// they are the wave's own, for a block of one wave.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define CSD_SYNC() __syncthreads()
-#define CSD_BALLOT(b) __ballot(b)
-#define CSD_SHFL(v, src, W) __shfl(v, src)
-#define CSD_SHFL_UP(v, d, W) __shfl_up(v, d)
-#define CSD_SHFL_XOR(v, d, W) __shfl_xor(v, d)
-#endif
-template <int W> CS_HD inline void wsync()
-{
-#ifdef CSD_SYNC
-	if constexpr (W > 1) CSD_SYNC();
-#endif
-}
-template <int W> CS_HD inline uint64_t wballot(bool b)
-{
-#ifdef CSD_SYNC
-	if constexpr (W > 1) return CSD_BALLOT(b);
-#endif
-	return b ? 1ull : 0ull;
-}
-template <int W> CS_HD inline int wbcast(int v, int src)
-{
-#ifdef CSD_SYNC
-	if constexpr (W > 1) return CSD_SHFL(v, src, W);
-#endif
-	(void)src;
-	return v;
-}
-template <int W> CS_HD inline int wsum(int v)
-{
-#ifdef CSD_SYNC
-	if constexpr (W > 1) for (int d = W >> 1; d > 0; d >>= 1) v += CSD_SHFL_XOR(v, d, W);
-#endif
-	return v;
-}
-// the maximum of g over the lanes below this one and `carry` (the strips before); carry takes the whole strip in
-template <int W> CS_HD inline int64_t wprefix_max(int64_t g, int lane, int64_t &carry)
-{
-	int64_t x = g;
-#ifdef CSD_SYNC
-	if constexpr (W > 1) {
-		for (int d = 1; d < W; d <<= 1) { const int64_t y = (int64_t)CSD_SHFL_UP((long long)x, d, W); if (lane >= d) x = x > y ? x : y; }
-		int64_t ex = (int64_t)CSD_SHFL_UP((long long)x, 1, W);
-		if (lane == 0) ex = NO_G;
-		ex = ex > carry ? ex : carry;
-		const int64_t all = (int64_t)CSD_SHFL((long long)x, W - 1, W);
-		carry = carry > all ? carry : all;
-		return ex;
-	}
-#endif
-	(void)lane;
-	const int64_t ex = carry;
-	carry = carry > x ? carry : x;
-	return ex;
-}
-CS_HD inline uint64_t lanes_below(int lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
-
-// entry t * 5 + q of bwa_fill_scmat's 5 x 5 matrix of int8_t as dedup_range fills it: a and -b pass through int8_t, and the flat array is
-// indexed with the query's code, which can be 5 for '-' (t <= 3: within the 25)
-CS_HD inline int sc_mat(const cs_aln_params_t &o, int t, int q) { const int x = t * 5 + q, i = x / 5, j = x - i * 5; return (i == 4 || j == 4) ? -1 : i == j ? (int)(int8_t)o.a : (int)(int8_t)-o.b; }
-
-// the two sequences of a patch as global_span_score lays them out: query[0, qlen) from the read at q0, the reference span [b, e)
-struct Span { const uint8_t *bases; int q0, qlen; bool rev; int64_t b, e, l_pac; const uint8_t *pac; };
-CS_HD inline int span_q(const Span &S, int j) { return cs_base_code_(S.bases[S.q0 + (S.rev ? S.qlen - 1 - j : j)]); }
-CS_HD inline int span_t(const Span &S, int64_t i)
-{
-	const int64_t p = S.rev ? S.e - 1 - i : S.b + i;
-	return p >= S.l_pac ? 3 - cs_pac_base_(S.pac, (S.l_pac << 1) - 1 - p) : cs_pac_base_(S.pac, p);
-}
-
-// banded_global_score of dedup.cpp (ksw_global2's score, ksw.c:504-587).  H and E hold qlen + 1 words each.
-template <int W> CS_HD int banded_global_score(const Span &S, int tlen, const cs_aln_params_t &o, int w, int32_t *H, int32_t *E, int lane)
-{
-	const int qlen = S.qlen, o_del = o.o_del, e_del = o.e_del, o_ins = o.o_ins, e_ins = o.e_ins;
-	const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
-	for (int j = lane; j <= qlen; j += W) { H[j] = j == 0 ? 0 : j <= w ? -(o_ins + e_ins * j) : NEG; E[j] = NEG; }
-	wsync<W>();
-	for (int i = 0; i < tlen; ++i) {
-		const int tb = span_t(S, i);
-		const int beg = i > w ? i - w : 0, end = i + w + 1 < qlen ? i + w + 1 : qlen;
-		const int32_t h1_0 = beg == 0 ? -(o_del + e_del * (i + 1)) : NEG;
-		if (beg >= end) {                                              // no column of this row inside the band: the host's H[end] = h1, E[end] = NEG
-			if (lane == 0) { H[end] = h1_0; E[end] = NEG; }
-			wsync<W>();
-			continue;
-		}
-		int64_t carry = NO_G;
-		int32_t next_h = 0;                                            // H[s + W] as the row before left it: the strip's last lane writes over it
-		for (int s = beg; s < end; s += W) {
-			const int j = s + lane;
-			const bool in = j < end;
-			int32_t m = NEG, e = NEG;
-			if (in) { m = (lane == 0 && s > beg ? next_h : H[j]) + sc_mat(o, tb, span_q(S, j)); e = E[j]; }
-			if (s + W < end) next_h = H[s + W];
-			const int64_t g = in ? (int64_t)m + (int64_t)e_ins * j : NO_G;
-			const int64_t gx = wprefix_max<W>(g, lane, carry);
-			wsync<W>();                                                // every lane has read its H[j] before a neighbour stores H[j + 1]
-			if (in) {
-				const int64_t f0 = (int64_t)NEG - (int64_t)e_ins * (j - beg), f1 = gx - oe_ins - (int64_t)e_ins * (j - 1);
-				const int32_t f = (int32_t)(f0 > f1 ? f0 : f1);
-				int32_t h = m >= e ? m : e;
-				h = h >= f ? h : f;
-				const int32_t x = m - oe_del;
-				e -= e_del; e = e > x ? e : x;
-				E[j] = e;
-				if (j == beg) H[beg] = h1_0;
-				H[j + 1] = h;
-				if (j + 1 == end) E[end] = NEG;
-			}
-		}
-		wsync<W>();
-	}
-	const int score = H[qlen];
-	wsync<W>();
-	return score;
-}
 
 // global_span_score of dedup.cpp (bwa_gen_cigar2 without the CIGAR); false = no alignment, *score untouched
 template <int W> CS_HD bool global_span_score(const Par &P, int w_, int l_query, const uint8_t *bases, int q0, int64_t rb, int64_t re, int *score, const Work &wk, int lane)
@@ -168,7 +43,7 @@ template <int W> CS_HD bool global_span_score(const Par &P, int w_, int l_query,
 	const Span S = {bases, q0, l_query, rb >= l_pac, b, e, l_pac, P.pac};
 	if (l_query == re - rb && w_ == 0) {
 		int sc = 0;
-		for (int i = lane; i < l_query; i += W) sc += sc_mat(P.o, span_t(S, i), span_q(S, i));
+		for (int i = lane; i < l_query; i += W) sc += sc_mat(P.o.a, P.o.b, span_t(S, i), span_q(S, i));
 		*score = wsum<W>(sc);
 		return true;
 	}

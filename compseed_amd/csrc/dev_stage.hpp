@@ -3,7 +3,9 @@
 // and the stage layer of the units outside the engine (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip, extend.hip): a grow-only device
 // buffer that frees before it allocates, the state every stage keeps (device, stream, timing events, pinned counter words, buffers) with
 // its creation, its release and the launch / upload / scan helpers, and the download of a chain result.  Header-only; a stage keeps its
-// own `enum { B_... }` of buffers and its kernels' Args, and derives its state from cs_dev_stage<B_COUNT>.
+// own `enum { B_... }` of buffers and its kernels' Args, and derives its state from cs_dev_stage<B_COUNT>.  This is the HOST half only:
+// what the kernels of chain_filter_gpu.hip and cigar_gpu.hip loop over are the bodies of chain_filter_scan.hpp and cigar_scan.hpp, on the
+// lanes of wave_lanes.hpp and the alignment of band_align.hpp, which plain C++ programs run on the CPU (tests/cpp/).
 #pragma once
 #include "cs_internal.hpp"
 

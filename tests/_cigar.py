@@ -104,7 +104,7 @@ def contigs():
 
 
 def build(out, lanes=1):
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off"] + (["-pthread", "-DCS_CG_EMU_W=%d" % lanes] if lanes > 1 else [])
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off"] + (["-pthread", "-DCS_EMU_W=%d" % lanes] if lanes > 1 else [])
     c = subprocess.run(cmd + ["-o", out, os.path.join(HERE, "cpp", "cigar_scan_check.cpp")], capture_output=True, text=True)
     assert c.returncode == 0 and not c.stderr, c.stderr                      # (no warnings either)
     return out

@@ -4,73 +4,19 @@
 // tests/test_cigar_scan_cpu.py writes a set's regions, reads, packed reference and contig offsets as flat binary files into a directory,
 // runs this over them and compares what it writes with the reference's own SAM lines (tests/golden/sam1).  No GPU and no Python in the
 // process: it can be built with -fsanitize=address,undefined and run as it is.
-// Built with -DCS_CG_EMU_W=N (a power of two up to 64; -pthread) the fill runs its N-lane instantiation -- the wave kernel's -- on N
-// threads in lockstep: a shuffle is an exchange through a shared array between two barriers.
-// Every job's fill score must be banded_global_score's (dedup_scan.hpp; the one-lane build asks), no walk may leave its band, and the writing call must count
+// Built with -DCS_EMU_W=N (lockstep.hpp) the fill runs its N-lane instantiation -- the wave kernel's -- on N threads in lockstep.
+// Every job's fill score must be banded_global_score's (band_align.hpp; the one-lane build asks), no walk may leave its band, and the writing call must count
 // what the counting call counted: exit status 1 otherwise.
 //   cigar_scan_check DIR
 //   in:  meta.bin (int64: n_reads n_regs l_pac a b o_del e_del o_ins e_ins w n_ctg budget), reg_off.bin, regs.bin, read_off.bin, bases.bin,
 //        pac.bin, ctg_off.bin
 //   out: alns.bin (cs_aln_t), cigar.bin (uint32), md.bin, stat.bin (uint64: dp_jobs nodp_jobs retries rejected cells chunks)
 //   exit status 3: the input fails check_read (the library's CS_EINVAL)
-#ifdef CS_CG_EMU_W
-#include <pthread.h>
-#include <cstdint>
-namespace emu {
-constexpr int W = CS_CG_EMU_W;
-static pthread_barrier_t bar;
-static long long slot[64];
-static thread_local int lane;
-inline void sync() { pthread_barrier_wait(&bar); }
-inline unsigned long long ballot(bool b)
-{
-	slot[lane] = b; sync();
-	unsigned long long m = 0;
-	for (int k = 0; k < W; ++k) if (slot[k]) m |= 1ull << k;
-	sync();
-	return m;
-}
-template <class T> inline T exchange(T v, int src) { slot[lane] = (long long)v; sync(); const T r = src >= 0 && src < W ? (T)slot[src] : v; sync(); return r; }
-} // namespace emu
-#define CSD_SYNC() emu::sync()
-#define CSD_BALLOT(b) emu::ballot(b)
-#define CSD_SHFL(v, src, W) emu::exchange(v, src)
-#define CSD_SHFL_UP(v, d, W) emu::exchange(v, emu::lane - (d))
-#define CSD_SHFL_XOR(v, d, W) emu::exchange(v, emu::lane ^ (d))
-#endif
+#include "lockstep.hpp"
 #include "../../compseed_amd/csrc/cigar_scan.hpp"
 
-#include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
 
-template <class T> static bool slurp(const std::string &path, std::vector<T> &v)
-{
-	FILE *fp = fopen(path.c_str(), "rb");
-	if (!fp) { fprintf(stderr, "cannot read %s\n", path.c_str()); return false; }
-	fseek(fp, 0, SEEK_END);
-	const long sz = ftell(fp);
-	fseek(fp, 0, SEEK_SET);
-	v.resize((size_t)sz / sizeof(T));
-	const size_t got = v.empty() ? 0 : fread(v.data(), sizeof(T), v.size(), fp);
-	fclose(fp);
-	return got == v.size() && (size_t)sz == v.size() * sizeof(T);
-}
-template <class T> static bool spill(const std::string &path, const std::vector<T> &v)
-{
-	FILE *fp = fopen(path.c_str(), "wb");
-	if (!fp) return false;
-	const size_t put = v.empty() ? 0 : fwrite(v.data(), sizeof(T), v.size(), fp);
-	return fclose(fp) == 0 && put == v.size();
-}
-
-#ifdef CS_CG_EMU_W
-constexpr int LANES = emu::W;
-static_assert(LANES > 1 && LANES <= 64 && (LANES & (LANES - 1)) == 0, "lanes: a power of two up to 64");
-#else
-constexpr int LANES = 1;
-#endif
 
 // the fill of one chunk of jobs: what a grid of waves does, job after job, on LANES lanes
 struct Fill {
@@ -90,7 +36,7 @@ static void fill_lane(Fill &F, int lane)
 		else {
 			const int w = cscg::job_band(*F.o, x, w2), tlen = (int)(x.re - x.rb);
 			score = cscg::global_fill<LANES>(S, tlen, *F.o, w, F.he, F.he + F.rows, F.z + (F.zoff[t] - F.zoff[F.a]), lane);
-#ifdef CS_CG_EMU_W
+#ifdef CS_EMU_W
 			other = score;                                            // (the lockstep build's result is compared with the one-lane build's, byte for byte)
 #else
 			other = csdd::banded_global_score<LANES>(S, tlen, *F.o, w, F.he2, F.he2 + F.rows, lane);
@@ -99,21 +45,6 @@ static void fill_lane(Fill &F, int lane)
 		}
 		if (lane == 0) { F.S->score[g] = score; if (score != other) ++F.differ; }
 	}
-}
-#ifdef CS_CG_EMU_W
-struct LaneArg { Fill *F; int lane; };
-static void *fill_thread(void *arg) { LaneArg *L = (LaneArg *)arg; emu::lane = L->lane; fill_lane(*L->F, L->lane); return nullptr; }
-#endif
-static bool fill_chunk(Fill &F)
-{
-#ifdef CS_CG_EMU_W
-	pthread_t th[64]; LaneArg la[64];
-	for (int x = 0; x < LANES; ++x) { la[x] = {&F, x}; if (pthread_create(&th[x], nullptr, fill_thread, &la[x])) return false; }
-	for (int x = 0; x < LANES; ++x) pthread_join(th[x], nullptr);
-#else
-	fill_lane(F, 0);
-#endif
-	return true;
 }
 
 int main(int argc, char **argv)
@@ -137,9 +68,6 @@ int main(int argc, char **argv)
 	o.a = (int32_t)meta[3]; o.b = (int32_t)meta[4]; o.o_del = (int32_t)meta[5]; o.e_del = (int32_t)meta[6]; o.o_ins = (int32_t)meta[7]; o.e_ins = (int32_t)meta[8]; o.w = (int32_t)meta[9];
 	const cscg::Ref R = {meta[2], pac.data(), ctg_off.data(), (int)ctg_off.size()};
 	const cscg::In D = {reg_off.data(), read_off.data(), regs.data(), bases.data(), n, n_regs};
-#ifdef CS_CG_EMU_W
-	pthread_barrier_init(&emu::bar, nullptr, LANES);
-#endif
 
 	// check: a lane per read
 	std::vector<uint32_t> rd(n_regs + 1, 0);
@@ -176,7 +104,7 @@ int main(int argc, char **argv)
 			++stat[5];
 			z.assign((size_t)(zoff[b] - zoff[a]) + 1, 0xff);
 			Fill F = {&D, &R, &o, &S, active.data(), zoff.data(), a, b, z.data(), he.data(), he2.data(), (int64_t)longest + 1, 0, 0};
-			if (!fill_chunk(F)) return 2;
+			if (!run_lanes([&F](int lane) { fill_lane(F, lane); })) return 2;
 			stat[4] += F.cells; differ += F.differ;
 			// the counting walk and the retry decision: a lane per job
 			std::vector<cscg::Counts> cnt(b - a); std::vector<uint64_t> coff(b - a + 1, 0), moff(b - a + 1, 0);

@@ -4,65 +4,18 @@
 // reads' input offsets as the device keeps them, and with the patch alignment's rows in a small array ("LDS", 2 * LDS_ROWS words) when they
 // fit and in a large one ("HBM", 2 * (longest read + 1) words) otherwise.  tests/test_dedup_pass_cpu.py writes the inputs (the files of
 // dedup_scan_check.cpp) and compares the outputs with the host call and the reference's goldens.  No GPU and no Python in the process:
-// it can be built with -fsanitize=address,undefined and run as it is.  -DCS_DDP_EMU_W=N: the heavy reads by N lanes on N lockstep
-// threads, as in dedup_scan_check.cpp.
+// it can be built with -fsanitize=address,undefined and run as it is.  -DCS_EMU_W=N (lockstep.hpp): the heavy reads by N lanes on N
+// lockstep threads.
 //   dedup_pass_check DIR [LDS_ROWS]          (LDS_ROWS: default csdp::LDS_ROWS; 0: every alignment's rows in the large array)
 //   in:  meta.bin, reg_off.bin, regs.bin, read_off.bin, bases.bin, pac.bin   (see dedup_scan_check.cpp)
 //   out: out_off.bin, out_regs.bin, out_nc.bin, out_stat.bin (uint64: alignments, merges, heavy reads, regions out, heavy reads whose
 //        alignments used the small rows, ... the large rows)
 //   exit status 3: the check body refused the input (nothing followed an offset)
-#ifdef CS_DDP_EMU_W
-#include <pthread.h>
-#include <cstdint>
-namespace emu {
-constexpr int W = CS_DDP_EMU_W;
-static pthread_barrier_t bar;
-static long long slot[64];
-static thread_local int lane;
-inline void sync() { pthread_barrier_wait(&bar); }
-inline unsigned long long ballot(bool b)
-{
-	slot[lane] = b; sync();
-	unsigned long long m = 0;
-	for (int k = 0; k < W; ++k) if (slot[k]) m |= 1ull << k;
-	sync();
-	return m;
-}
-template <class T> inline T exchange(T v, int src) { slot[lane] = (long long)v; sync(); const T r = src >= 0 && src < W ? (T)slot[src] : v; sync(); return r; }
-} // namespace emu
-#define CSD_SYNC() emu::sync()
-#define CSD_BALLOT(b) emu::ballot(b)
-#define CSD_SHFL(v, src, W) emu::exchange(v, src)
-#define CSD_SHFL_UP(v, d, W) emu::exchange(v, emu::lane - (d))
-#define CSD_SHFL_XOR(v, d, W) emu::exchange(v, emu::lane ^ (d))
-#endif
+#include "lockstep.hpp"
 #include "../../compseed_amd/csrc/dedup_pass.hpp"
 
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
-
-template <class T> static bool slurp(const std::string &path, std::vector<T> &v)
-{
-	FILE *fp = fopen(path.c_str(), "rb");
-	if (!fp) { fprintf(stderr, "cannot read %s\n", path.c_str()); return false; }
-	fseek(fp, 0, SEEK_END);
-	const long sz = ftell(fp);
-	fseek(fp, 0, SEEK_SET);
-	v.resize((size_t)sz / sizeof(T));
-	const size_t got = v.empty() ? 0 : fread(v.data(), sizeof(T), v.size(), fp);
-	fclose(fp);
-	return got == v.size() && (size_t)sz == v.size() * sizeof(T);
-}
-template <class T> static bool spill(const std::string &path, const std::vector<T> &v)
-{
-	FILE *fp = fopen(path.c_str(), "wb");
-	if (!fp) return false;
-	const size_t put = v.empty() ? 0 : fwrite(v.data(), sizeof(T), v.size(), fp);
-	return fclose(fp) == 0 && put == v.size();
-}
 
 constexpr int32_t SENTINEL = 0x7f7f7f7f;                              // in word 0 of both row arrays before a heavy read: an alignment leaves H[0] <= 0 there
 
@@ -119,28 +72,20 @@ int main(int argc, char **argv)
 	for (int64_t r = 0; r < n; ++r) ctr[csdp::C_HEAVY] += (uint64_t)csdp::light_read(D, S, r);
 	// ---- dd_wave_kernel
 	Heavy H = {&D, &P, &S, &lds, &hbm, lds_rows, {}, 0, 0};
-#ifdef CS_DDP_EMU_W
-	constexpr int W = emu::W;
-	static_assert(W > 1 && W <= 64 && (W & (W - 1)) == 0, "lanes: a power of two up to 64");
-	pthread_barrier_init(&emu::bar, nullptr, W);
-	struct Lane { Heavy *H; int lane; } lanes[64];
-	auto body = [](void *arg) -> void * {
-		Lane *L = (Lane *)arg; Heavy &H = *L->H;
-		emu::lane = L->lane;
+#ifdef CS_EMU_W
+	constexpr int W = LANES;
+	auto body = [&H](int lane) {
 		const csdd::Work wk = {H.lds->data(), H.lds_rows, H.hbm->data()};
 		for (int64_t r = 0; r < H.D->n_reads; ++r) {
 			if (!H.S->heavy[r]) continue;
-			if (L->lane == 0) before_read(H);
+			if (lane == 0) before_read(H);
 			emu::sync();
-			csdp::heavy_read<W>(*H.D, *H.P, *H.S, r, L->lane, wk, H.st[L->lane]);
+			csdp::heavy_read<W>(*H.D, *H.P, *H.S, r, lane, wk, H.st[lane]);
 			emu::sync();
-			if (L->lane == 0) after_read(H);
+			if (lane == 0) after_read(H);
 		}
-		return nullptr;
 	};
-	pthread_t th[64];
-	for (int x = 0; x < W; ++x) { lanes[x] = {&H, x}; if (pthread_create(&th[x], nullptr, body, &lanes[x])) return 2; }
-	for (int x = 0; x < W; ++x) pthread_join(th[x], nullptr);
+	if (!run_lanes(body)) return 2;
 	for (int x = 1; x < W; ++x) if (H.st[x].aligns != H.st[0].aligns || H.st[x].merges != H.st[0].merges) { fprintf(stderr, "the lanes count different events\n"); return 1; }
 #else
 	{

@@ -2,64 +2,15 @@
 // that runs a lane or a wave per read) as a plain C++ program: tests/test_dedup_scan_cpu.py writes a set's regions, reads and the packed reference as
 // flat binary files into a directory, runs this over them and compares what it writes with the reference's own regions (tests/golden/ddp1,
 // aln2).  No GPU and no Python in the process: it can be built with -fsanitize=address,undefined and run as it is.
-// Built with -DCS_DDP_EMU_W=N (a power of two up to 64; -pthread) the program runs the N-lane instantiation -- the wave kernel's -- on N
-// threads in lockstep: a ballot or a shuffle is an exchange through a shared array between two barriers, so lanes that reach different
-// collectives, or a different number of them, never finish (the test's time limit) or differ in what they return.
+// Built with -DCS_EMU_W=N (lockstep.hpp) the program runs the N-lane instantiation -- the wave kernel's -- on N threads in lockstep.
 //   dedup_scan_check DIR
 //   in:  meta.bin (int64: n_reads n_regs l_pac a b o_del e_del o_ins e_ins w max_chain_gap, then the bits of mask_level_redun),
 //        reg_off.bin, regs.bin, read_off.bin, bases.bin, pac.bin
 //   out: out_off.bin (uint64, n_reads + 1), out_regs.bin (cs_alnreg_t), out_nc.bin (int32), out_stat.bin (uint64: alignments, merges)
-#ifdef CS_DDP_EMU_W
-#include <pthread.h>
-#include <cstdint>
-namespace emu {
-constexpr int W = CS_DDP_EMU_W;
-static pthread_barrier_t bar;
-static long long slot[64];
-static thread_local int lane;
-inline void sync() { pthread_barrier_wait(&bar); }
-inline unsigned long long ballot(bool b)
-{
-	slot[lane] = b; sync();
-	unsigned long long m = 0;
-	for (int k = 0; k < W; ++k) if (slot[k]) m |= 1ull << k;
-	sync();
-	return m;
-}
-template <class T> inline T exchange(T v, int src) { slot[lane] = (long long)v; sync(); const T r = src >= 0 && src < W ? (T)slot[src] : v; sync(); return r; }
-} // namespace emu
-#define CSD_SYNC() emu::sync()
-#define CSD_BALLOT(b) emu::ballot(b)
-#define CSD_SHFL(v, src, W) emu::exchange(v, src)
-#define CSD_SHFL_UP(v, d, W) emu::exchange(v, emu::lane - (d))
-#define CSD_SHFL_XOR(v, d, W) emu::exchange(v, emu::lane ^ (d))
-#endif
+#include "lockstep.hpp"
 #include "../../compseed_amd/csrc/dedup_scan.hpp"
 
-#include <cstdio>
 #include <cstring>
-#include <string>
-#include <vector>
-
-template <class T> static bool slurp(const std::string &path, std::vector<T> &v)
-{
-	FILE *fp = fopen(path.c_str(), "rb");
-	if (!fp) { fprintf(stderr, "cannot read %s\n", path.c_str()); return false; }
-	fseek(fp, 0, SEEK_END);
-	const long sz = ftell(fp);
-	fseek(fp, 0, SEEK_SET);
-	v.resize((size_t)sz / sizeof(T));
-	const size_t got = v.empty() ? 0 : fread(v.data(), sizeof(T), v.size(), fp);
-	fclose(fp);
-	return got == v.size() && (size_t)sz == v.size() * sizeof(T);
-}
-template <class T> static bool spill(const std::string &path, const std::vector<T> &v)
-{
-	FILE *fp = fopen(path.c_str(), "wb");
-	if (!fp) return false;
-	const size_t put = v.empty() ? 0 : fwrite(v.data(), sizeof(T), v.size(), fp);
-	return fclose(fp) == 0 && put == v.size();
-}
 
 int main(int argc, char **argv)
 {
@@ -87,30 +38,25 @@ int main(int argc, char **argv)
 	std::vector<uint64_t> out_off((size_t)n + 1, 0), stat(2, 0); std::vector<cs_alnreg_t> out_regs; std::vector<int32_t> out_nc;
 	std::vector<cs_alnreg_t> a, o; std::vector<int32_t> nc, onc, ws; std::vector<csdd::SRec> srt;
 	csdd::Stat st;
-#ifdef CS_DDP_EMU_W
-	constexpr int W = emu::W;
-	static_assert(W > 1 && W <= 64 && (W & (W - 1)) == 0, "lanes: a power of two up to 64");
-	pthread_barrier_init(&emu::bar, nullptr, W);
+#ifdef CS_EMU_W
+	constexpr int W = LANES;
 	struct Shared { const csdd::Par *P; const std::vector<uint64_t> *reg_off, *read_off; const std::vector<cs_alnreg_t> *regs; const std::vector<uint8_t> *bases;
 	                std::vector<cs_alnreg_t> *a, *o, *out_regs; std::vector<int32_t> *nc, *onc, *ws, *out_nc; std::vector<csdd::SRec> *srt; std::vector<uint64_t> *out_off;
 	                int64_t n; int k[64]; csdd::Stat st[64]; int bad; } S = {&P, &reg_off, &read_off, &regs, &bases, &a, &o, &out_regs, &nc, &onc, &ws, &out_nc, &srt, &out_off, n, {}, {}, 0};
-	struct Lane { Shared *S; int lane; } lanes[64];
-	auto body = [](void *arg) -> void * {
-		Lane *L = (Lane *)arg; Shared &S = *L->S;
-		emu::lane = L->lane;
+	auto body = [&S](int lane) {
 		for (int64_t r = 0; r < S.n; ++r) {
 			const uint64_t g0 = (*S.reg_off)[(size_t)r], g1 = (*S.reg_off)[(size_t)r + 1];
 			const size_t cnt = (size_t)(g1 - g0), l_query = (size_t)((*S.read_off)[(size_t)r + 1] - (*S.read_off)[(size_t)r]);
-			if (L->lane == 0) {
+			if (lane == 0) {
 				S.a->assign(cnt + 1, cs_alnreg_t()); S.o->assign(cnt + 1, cs_alnreg_t()); S.nc->assign(cnt + 1, 0); S.onc->assign(cnt + 1, 0); S.srt->assign(cnt + 1, csdd::SRec());
 				S.ws->assign((l_query + 1) * 2, 0);
 			}
 			emu::sync();
 			const csdd::Work wk = {nullptr, 0, S.ws->data()};
-			S.k[L->lane] = csdd::dedup_read<W>(*S.P, S.regs->data() + g0, (int)cnt, S.bases->data() + (*S.read_off)[(size_t)r], L->lane, S.a->data(), S.nc->data(), S.srt->data(), wk, true,
-			                                  S.o->data(), S.onc->data(), S.st[L->lane]);
+			S.k[lane] = csdd::dedup_read<W>(*S.P, S.regs->data() + g0, (int)cnt, S.bases->data() + (*S.read_off)[(size_t)r], lane, S.a->data(), S.nc->data(), S.srt->data(), wk, true,
+			                                  S.o->data(), S.onc->data(), S.st[lane]);
 			emu::sync();
-			if (L->lane == 0) {
+			if (lane == 0) {
 				const int k = S.k[0];
 				for (int x = 1; x < W; ++x) if (S.k[x] != k) S.bad = 1;          // (every lane returns the read's count)
 				if (k < 0 || (size_t)k > cnt) { S.bad = 1; } else { S.out_regs->insert(S.out_regs->end(), S.o->begin(), S.o->begin() + k); S.out_nc->insert(S.out_nc->end(), S.onc->begin(), S.onc->begin() + k); }
@@ -118,11 +64,8 @@ int main(int argc, char **argv)
 			}
 			emu::sync();
 		}
-		return nullptr;
 	};
-	pthread_t th[64];
-	for (int x = 0; x < W; ++x) { lanes[x] = {&S, x}; if (pthread_create(&th[x], nullptr, body, &lanes[x])) return 2; }
-	for (int x = 0; x < W; ++x) pthread_join(th[x], nullptr);
+	if (!run_lanes(body)) return 2;
 	for (int x = 1; x < W; ++x) if (S.st[x].aligns != S.st[0].aligns || S.st[x].merges != S.st[0].merges) S.bad = 1;   // (... and counts the same events)
 	if (S.bad) { fprintf(stderr, "the lanes disagree, or a read came back with an impossible count\n"); return 1; }
 	st = S.st[0];

@@ -33,7 +33,7 @@ def exe(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def lanes_exe(tmp_path_factory):
-    return {n: _build(str(tmp_path_factory.mktemp("dedup_pass_%d" % n) / "dedup_pass_check"), "-DCS_DDP_EMU_W=%d" % n) for n in (64, 8)}
+    return {n: _build(str(tmp_path_factory.mktemp("dedup_pass_%d" % n) / "dedup_pass_check"), "-DCS_EMU_W=%d" % n) for n in (64, 8)}
 
 
 def _write(d, reg_off, regs, bases, off, ap, dp):

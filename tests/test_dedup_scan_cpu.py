@@ -33,7 +33,7 @@ def lanes_exe(tmp_path_factory):
     out = {}
     for n in (64, 8):
         out[n] = str(tmp_path_factory.mktemp("dedup_scan_%d" % n) / "dedup_scan_check")
-        c = subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off", "-pthread", "-DCS_DDP_EMU_W=%d" % n, "-o", out[n],
+        c = subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off", "-pthread", "-DCS_EMU_W=%d" % n, "-o", out[n],
                             os.path.join(HERE, "cpp", "dedup_scan_check.cpp")], capture_output=True, text=True)
         assert c.returncode == 0 and not c.stderr, c.stderr
     return out
