@@ -22,7 +22,7 @@ SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", 
            "cs_device_download", "cs_device_sync", "cs_packed_seed_rbeg", "cs_engine_check_index",
            "cs_ext_params_default", "cs_extender_create", "cs_extender_destroy", "cs_extend_batch", "cs_extend_batch_device", "cs_extender_stats",
            "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_extend_chains_device", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats",
-           "cs_regions_cigar", "cs_cigar_stats"]
+           "cs_regions_cigar", "cs_cigar_stats", "cs_mark_params_default", "cs_regions_mark", "cs_mark_stats"]
 
 
 class CSError(RuntimeError):
@@ -210,6 +210,27 @@ class CCigarResult(C.Structure):
 
 class CigarStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("regions", "dp_jobs", "nodp_jobs", "retries", "rejected", "cells", "launches")] + [("kernel_ms", C.c_double)]
+
+
+class MarkParams(C.Structure):
+    """cs_mark_params_t: the mem_opt_t fields marking, MAPQ and line selection read; T is the caller's to scale by -A"""
+    _fields_ = [(n, C.c_int32) for n in ("T", "mapq_coef_len", "max_xa_hits", "max_xa_hits_alt", "min_seed_len")] + [(n, C.c_float) for n in ("mask_level", "drop_ratio", "xa_drop_ratio")]
+
+    def __init__(self, T=30, mapq_coef_len=50, max_xa_hits=5, max_xa_hits_alt=200, min_seed_len=19, mask_level=0.5, drop_ratio=0.5, xa_drop_ratio=0.8):
+        super().__init__(T, mapq_coef_len, max_xa_hits, max_xa_hits_alt, min_seed_len, mask_level, drop_ratio, xa_drop_ratio)
+
+
+# cs_mark_t: what cs_regions_mark decides about a region
+MARK_DT = np.dtype([(n, "<i4") for n in ("reg", "is_alt", "secondary", "secondary_all", "sub", "sub_n", "alt_sc", "mapq", "xs", "flag", "line", "xa_of")])
+MARK_ALL, MARK_NO_MULTI, MARK_KEEP_SUPP_MAPQ, MARK_NO_LIGHT_PATH, MARK_FROM_HBM = 1, 2, 4, 0x100, 0x200
+
+
+class CMarkResult(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("n_regs", C.c_uint64), ("n_lines", C.c_uint64), ("marks", C.c_void_p), ("line_off", C.c_void_p), ("cigar_regs", CAlnResult), ("cigar_src", C.c_void_p)]
+
+
+class MarkStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "regions", "lines", "xa_members", "cigar_regions", "light_reads", "wave_reads", "hbm_reads", "launches")] + [("kernel_ms", C.c_double)]
 
 
 class IndexCheck(C.Structure):
@@ -419,6 +440,10 @@ def load_library():
     L.cs_dedup_regions.argtypes = [vp, C.POINTER(DedupParams), C.POINTER(CAlnResult), vp, vp, C.POINTER(CAlnResult), C.POINTER(vp)]
     L.cs_regions_cigar.argtypes = [vp, C.POINTER(CAlnResult), vp, vp, C.c_uint32, C.POINTER(CCigarResult)]
     L.cs_cigar_stats.argtypes = [vp, C.POINTER(CigarStats)]
+    L.cs_mark_params_default.argtypes = [C.POINTER(MarkParams)]
+    L.cs_mark_params_default.restype = None
+    L.cs_regions_mark.argtypes = [vp, C.POINTER(MarkParams), C.POINTER(CAlnResult), vp, C.c_int64, C.c_uint32, C.POINTER(CMarkResult)]
+    L.cs_mark_stats.argtypes = [vp, C.POINTER(MarkStats)]
     _lib = L
     return L
 
@@ -1054,7 +1079,7 @@ class Aligner:
         return dict(reg_off=_view(out.reg_off, "<u8", int(out.n_reads) + 1, copy), regs=_view(out.regs, ALNREG_DT, int(out.n_regs), copy), n_comp=_view(nc.value, "<i4", int(out.n_regs), copy))
 
     def regions_cigar(self, reg_off, regs, bases, read_offsets, flags=0):
-        """cs_regions_cigar (mem_reg2aln without primary marking, MAPQ and SAM text): regions as extend_chains or dedup_regions return them ->
+        """cs_regions_cigar (mem_reg2aln without SAM text; marking and MAPQ are regions_mark's): regions as extend_chains, dedup_regions or regions_mark return them ->
         dict(alns: one ALN_DT record per region, cigar: uint32 in BAM coding, md: the NUL-terminated strings), copies.  Regions that
         bridge the strands come back empty with nm = -1 and the call raises CSError(-1) AFTER the others were made: the exception
         carries them as `.result`."""
@@ -1076,6 +1101,25 @@ class Aligner:
         st = CigarStats()
         _check(self.L.cs_cigar_stats(self.h, C.byref(st)))
         return {n: (float(getattr(st, n)) if n == "kernel_ms" else int(getattr(st, n))) for n, _ in CigarStats._fields_}
+
+    def regions_mark(self, reg_off, regs, read_offsets, params=None, id_base=0, flags=0):
+        """cs_regions_mark (mem_mark_primary_se, mem_approx_mapq_se, the selection of mem_reg2sam, mem_gen_alt's membership rule): regions
+        as dedup_regions returns them -> dict(marks: one MARK_DT record per region in rank order, CSR by reg_off; line_off; cigar_reg_off /
+        cigar_regs: the regions with line >= 0 or xa_of >= 0, regions_cigar's input; cigar_src: their indices into marks), copies.
+        flags: MARK_ALL (-a), MARK_NO_MULTI (-M), MARK_KEEP_SUPP_MAPQ (-q)"""
+        params = params or MarkParams()
+        reg_off = np.ascontiguousarray(reg_off, dtype=np.uint64); regs = np.ascontiguousarray(regs, dtype=ALNREG_DT); ro = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+        cin = CAlnResult(reg_off.size - 1, regs.size, reg_off.ctypes.data, regs.ctypes.data if regs.size else None)
+        out = CMarkResult()
+        _check(self.L.cs_regions_mark(self.h, C.byref(params), C.byref(cin), ro.ctypes.data, int(id_base), int(flags), C.byref(out)))
+        n, nc = int(out.n_reads), int(out.cigar_regs.n_regs)
+        return dict(marks=_view(out.marks, MARK_DT, int(out.n_regs), True), line_off=_view(out.line_off, "<u8", n + 1, True), cigar_reg_off=_view(out.cigar_regs.reg_off, "<u8", n + 1, True),
+                    cigar_regs=_view(out.cigar_regs.regs, ALNREG_DT, nc, True), cigar_src=_view(out.cigar_src, "<u4", nc, True))
+
+    def mark_stats(self):
+        st = MarkStats()
+        _check(self.L.cs_mark_stats(self.h, C.byref(st)))
+        return {n: (float(getattr(st, n)) if n == "kernel_ms" else int(getattr(st, n))) for n, _ in MarkStats._fields_}
 
     def stats(self):
         st = AlnStats()

@@ -23,6 +23,7 @@ struct cs_aligner {
 	std::vector<uint64_t> dd_off; std::vector<cs_alnreg_t> dd_regs; std::vector<int32_t> dd_ncomp;   // cs_dedup_regions' result
 	cs_aln_stats_t st{};
 	cs_cigar_gpu *cig = nullptr;          // the device side of cs_regions_cigar (cigar_gpu.hip), with its result
+	cs_mark_gpu *mrk = nullptr;           // the device side of cs_regions_mark (mark_gpu.hip), with its result
 };
 
 
@@ -67,6 +68,7 @@ extern "C" void cs_aligner_destroy(cs_aligner_t *A)
 	if (!A) return;
 	if (A->gpu) cs_aligner_gpu_release_(A->gpu);
 	if (A->cig) cs_cigar_gpu_release_(A->cig);
+	if (A->mrk) cs_mark_gpu_release_(A->mrk);
 	if (A->ext) cs_extender_destroy(A->ext);
 	delete A;
 }
@@ -133,6 +135,31 @@ extern "C" int cs_cigar_stats(const cs_aligner_t *A, cs_cigar_stats_t *st)
 {
 	if (!A || !st) return cs_fail_(CS_EINVAL, "null argument");
 	return cs_cigar_gpu_stats_(A->cig, st);
+}
+
+// marking, MAPQ, line selection and XA membership (mark_gpu.hip): only what the host can know is checked here, the arrays by a kernel
+extern "C" void cs_mark_params_default(cs_mark_params_t *p)
+{
+	if (!p) return;
+	// mem_opt_init (comp_seed.cpp:26-58)
+	p->T = 30; p->mapq_coef_len = 50; p->max_xa_hits = 5; p->max_xa_hits_alt = 200; p->min_seed_len = 19; p->mask_level = 0.50f; p->drop_ratio = 0.50f; p->xa_drop_ratio = 0.80f;
+}
+extern "C" int cs_regions_mark(cs_aligner_t *A, const cs_mark_params_t *par, const cs_aln_result_t *regs, const uint64_t *read_offsets, int64_t id_base, uint32_t flags, cs_mark_result_t *out)
+{
+	if (!A || !par || !regs || !out) return cs_fail_(CS_EINVAL, "cs_regions_mark: null argument");
+	if (flags & ~(CS_MARK_ALL | CS_MARK_NO_MULTI | CS_MARK_KEEP_SUPP_MAPQ | CS_MARK_NO_LIGHT_PATH | CS_MARK_FROM_HBM)) return cs_fail_(CS_EINVAL, "cs_regions_mark: unknown flags");
+	if (regs->n_reads < 0 || (regs->n_reads > 0 && (!regs->reg_off || !read_offsets)) || (regs->n_regs > 0 && !regs->regs)) return cs_fail_(CS_EINVAL, "cs_regions_mark: bad argument");
+	if (par->mapq_coef_len <= 0) return cs_fail_(CS_EINVAL, "cs_regions_mark: mapq_coef_len <= 0 (that MAPQ formula stays the caller's)");
+	if (par->min_seed_len < 0 || par->max_xa_hits < 0 || par->max_xa_hits_alt < 0 || id_base < 0) return cs_fail_(CS_EINVAL, "cs_regions_mark: bad parameters");
+	if (A->device < 0) return cs_fail_(CS_EDEVICE, "cs_regions_mark: this aligner was created without a device (device -1): the marks are made on the GPU only");
+	if (regs->n_regs >= 0xffffffffull || regs->n_reads >= 0xffffffffll) return cs_fail_(CS_ERANGE, "cs_regions_mark: 2^32 regions or reads or more in one call");
+	if (par->mapq_coef_len > 131072) return cs_fail_(CS_ERANGE, "cs_regions_mark: mapq_coef_len above 131,072");
+	return cs_regions_mark_gpu_(&A->mrk, A->device, A->ref, A->par, *par, regs, read_offsets, id_base, flags, out);
+}
+extern "C" int cs_mark_stats(const cs_aligner_t *A, cs_mark_stats_t *st)
+{
+	if (!A || !st) return cs_fail_(CS_EINVAL, "null argument");
+	return cs_mark_gpu_stats_(A->mrk, st);
 }
 
 extern "C" int cs_aligner_stats(const cs_aligner_t *A, cs_aln_stats_t *st)

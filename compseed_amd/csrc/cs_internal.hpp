@@ -78,6 +78,12 @@ void cs_cigar_gpu_release_(cs_cigar_gpu *g);
 int cs_cigar_gpu_stats_(const cs_cigar_gpu *g, cs_cigar_stats_t *st);
 int cs_regions_cigar_gpu_(cs_cigar_gpu **gp, int device, const cs_refseq_view &R, const std::vector<uint8_t> &pac, const cs_aln_params_t &o, const cs_aln_result_t *regs,
                           const uint8_t *bases, const uint64_t *read_offsets, uint32_t flags, cs_cigar_result_t *out);
+// ... and of cs_regions_mark (mark_gpu.hip): marking, MAPQ, line selection and XA membership, with the state it keeps between calls
+struct cs_mark_gpu;
+void cs_mark_gpu_release_(cs_mark_gpu *g);
+int cs_mark_gpu_stats_(const cs_mark_gpu *g, cs_mark_stats_t *st);
+int cs_regions_mark_gpu_(cs_mark_gpu **gp, int device, const cs_refseq_view &R, const cs_aln_params_t &o, const cs_mark_params_t &par, const cs_aln_result_t *regs,
+                         const uint64_t *read_offsets, int64_t id_base, uint32_t flags, cs_mark_result_t *out);
 
 // ---- the host passes' work sharing: fn(k) for k in [0, n_chunks) on T threads, chunks of reads handed out by a counter.  (A read inside a
 // repeat costs a hundred times the average in the quadratic passes -- chain filter, dedup --; equal shares left fifteen threads waiting for

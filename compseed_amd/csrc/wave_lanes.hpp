@@ -1,5 +1,5 @@
-// wave_lanes.hpp -- the W lanes (1 or 64) that the per-read and per-job bodies of chain_filter_scan.hpp, dedup_scan.hpp and cigar_scan.hpp
-// are written for: shuffles and ballots of a wave, or nothing at all.  A plain C++ program may define the CSD_ macros before it includes
+// wave_lanes.hpp -- the W lanes (1 or 64) that the per-read and per-job bodies of chain_filter_scan.hpp, dedup_scan.hpp, cigar_scan.hpp
+// and mark_scan.hpp are written for: shuffles and ballots of a wave, or nothing at all.  A plain C++ program may define the CSD_ macros before it includes
 // this header and run the W > 1 instantiations on lanes of its own (tests/cpp/lockstep.hpp: threads in lockstep); in device code they are
 // the wave's own, for a block of one wave.  With W = 1 every primitive is the identity, so a body written once for W lanes is the
 // sequential routine when one lane runs it.  The namespace stays csdd, where these primitives began (dedup_scan.hpp), so that no caller

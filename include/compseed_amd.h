@@ -502,7 +502,7 @@ int  cs_dedup_regions(cs_aligner_t *a, const cs_dedup_params_t *par, const cs_al
                       cs_aln_result_t *out, const int32_t **n_comp);
 int  cs_aligner_stats(const cs_aligner_t *a, cs_aln_stats_t *st);
 /* From regions to alignments on the GPU: what the reference does with every region it reports (mem_reg2aln, comp_seed.cpp:811-880, without
- * primary marking, MAPQ and SAM text, which stay the caller's) -- the band inferred from the region, the banded global alignment with
+ * primary marking and MAPQ, which are cs_regions_mark's below, and SAM text, which stays the caller's) -- the band inferred from the region, the banded global alignment with
  * backtrack (bwa_gen_cigar2 / ksw_global2) up to three times with a doubled band, NM and MD, a leading or else a trailing deletion
  * squeezed out, the soft clips, and the position in contig coordinates.  Host arrays in (`regs`: cs_extend_chains' or cs_dedup_regions'
  * result, or the caller's regions in that form; `bases` / `read_offsets`: the reads); host arrays owned by the aligner out, valid until
@@ -523,6 +523,44 @@ typedef struct { uint64_t n_regs, n_cigar, md_bytes; const cs_aln_t *alns; const
 typedef struct { uint64_t regions, dp_jobs, nodp_jobs, retries, rejected, cells, launches; double kernel_ms; } cs_cigar_stats_t;
 int  cs_regions_cigar(cs_aligner_t *a, const cs_aln_result_t *regs, const uint8_t *bases, const uint64_t *read_offsets, uint32_t flags, cs_cigar_result_t *out);
 int  cs_cigar_stats(const cs_aligner_t *a, cs_cigar_stats_t *st);
+/* Between de-duplication and the CIGAR stage, on the GPU: which regions of a read become SAM lines, with which flag and MAPQ, and which
+ * ones a line lists as XA alternatives -- mem_mark_primary_se (comp_seed.cpp:711-774; the ALT branch included, is_alt from the aligner's
+ * <prefix>.alt as comp_seed.cpp:2405 sets it), mem_approx_mapq_se (:686-709, for mapq_coef_len > 0), the selection loop of mem_reg2sam
+ * (:1089-1106) and the membership rule of mem_gen_alt (:1026-1054).  `regs`: cs_dedup_regions' result, or the caller's regions in that
+ * form -- a purged (qe <= qb) or unmapped region is refused, the reference marks after mem_sort_dedup_patch, where none exist;
+ * `read_offsets`: the reads' offsets (only the lengths are used); `id_base`: the number of reads before this batch (the hash that breaks
+ * ties is hash_64 of id_base + read + i, comp_seed.cpp:743, 2410).  Scoring a / b / o / e are the aligner's cs_aln_params_t.  Host arrays
+ * in; host arrays owned by the aligner out, valid until its next cs_regions_mark.  `marks`: one cs_mark_t per region, per read in the
+ * reference's order after its sorts (rank order), CSR by the input's reg_off; `reg` the region's index within its read in input order;
+ * secondary / secondary_all / sub / sub_n / alt_sc as mem_alnreg_t has them after marking (secondary and secondary_all are ranks);
+ * `line` the index of the region's SAM line within the read or -1, `flag` that line's 0x10 | 0x100 | 0x800 bits, `mapq` its MAPQ (0 for
+ * a secondary), `xs` its XS (-1: none); without CS_MARK_ALL `xa_of` is the rank of the primary whose XA list the region joins, or -1.
+ * `line_off`: a read's lines; a read with none gets the caller's unmapped record.  `cigar_regs` / `cigar_src`: the regions with
+ * line >= 0 or xa_of >= 0 in rank order -- the input of cs_regions_cigar as it is -- and each one's index into marks.  Still the
+ * caller's: SAM text, the -5 reordering (mem_reorder_primary5), paired-end, and the MAPQ formula of mapq_coef_len <= 0.  Errors, in this
+ * order: a NULL `a`, `par`, `regs` or `out`, or unknown flag bits CS_EINVAL; NULL arrays where the counts say there are entries
+ * CS_EINVAL; mapq_coef_len <= 0 or other bad parameters CS_EINVAL; an aligner created with device -1 CS_EDEVICE; 2^32 regions or reads
+ * or more, or mapq_coef_len above 131,072, CS_ERANGE; a read with 65,536 regions or more, or a region spanning more than 131,072 bases,
+ * CS_ERANGE; inconsistent input -- reg_off / read_offsets that are not CSR offset arrays from 0, a region that is purged, unmapped,
+ * outside its read or outside [0, 2 l_pac), a contig index outside the contig table, a negative score -- CS_EINVAL, found by a checking
+ * kernel before any kernel follows an offset.  After any error the aligner is usable for the next call. */
+typedef struct { int32_t T, mapq_coef_len, max_xa_hits, max_xa_hits_alt, min_seed_len; float mask_level, drop_ratio, xa_drop_ratio; } cs_mark_params_t;
+      /* mem_opt_t: T 30 (the caller scales it by -A as fastmap.c:146 does), 50, 5, 200, 19, 0.50, 0.50, 0.80; scoring a/b/o/e are the aligner's */
+#define CS_MARK_ALL 1u              /* -a: secondaries become lines too; no XA lists */
+#define CS_MARK_NO_MULTI 2u         /* -M: a supplementary line is flagged 0x100 instead of 0x800 */
+#define CS_MARK_KEEP_SUPP_MAPQ 4u   /* -q: a supplementary line keeps its own MAPQ */
+#define CS_MARK_NO_LIGHT_PATH 0x100u   /* tests: every read with regions goes through the wave kernel; the same result */
+#define CS_MARK_FROM_HBM 0x200u        /* tests: the wave kernel keeps every read's lists in HBM scratch instead of LDS; the same result */
+typedef struct { int32_t reg /* index within its read, input order */, is_alt, secondary, secondary_all, sub, sub_n, alt_sc, mapq, xs, flag, line, xa_of; } cs_mark_t;
+typedef struct { int64_t n_reads; uint64_t n_regs, n_lines;
+                 const cs_mark_t *marks;        /* per read in the reference's order after its sorts, CSR by the input's reg_off */
+                 const uint64_t *line_off;      /* n_reads + 1: a read's lines; a read with none gets the caller's unmapped record */
+                 cs_aln_result_t cigar_regs;    /* the regions with line >= 0 or xa_of >= 0, rank order, CSR per read: the CIGAR stage's input as it is */
+                 const uint32_t *cigar_src; }   /* per entry of cigar_regs: its index into marks */ cs_mark_result_t;
+typedef struct { uint64_t reads, regions, lines, xa_members, cigar_regions, light_reads, wave_reads, hbm_reads, launches; double kernel_ms; } cs_mark_stats_t;
+void cs_mark_params_default(cs_mark_params_t *p);
+int  cs_regions_mark(cs_aligner_t *a, const cs_mark_params_t *par, const cs_aln_result_t *regs, const uint64_t *read_offsets, int64_t id_base, uint32_t flags, cs_mark_result_t *out);
+int  cs_mark_stats(const cs_aligner_t *a, cs_mark_stats_t *st);
 
 /* ---- the result of the LAST device-variant call, without moving it: an order-sensitive 64-bit digest per array
  *      (sum over the array's 64-bit words w[i] of splitmix64(w[i] + i * 0x9E3779B97F4A7C15), mod 2^64), so that two runs over

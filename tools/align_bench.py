@@ -8,6 +8,9 @@ Beside the host extend_chains row: cs_extend_chains_device on the device filter'
 left behind (CS_ALN_DEV_COMPACT), each with the time download_regions takes; checked equal to the host call's regions / its regions with qe > qb.
 Behind dedup_regions: "regions -> CIGAR", cs_regions_cigar over the de-duplicated regions (host arrays in and out), wall time as ms per million
 reads, with the device span and the job counts of cs_cigar_stats; nothing in the reference is timed separately to compare it with.
+Behind that: "regions -> marks", cs_regions_mark over the de-duplicated regions in default mode and under CS_MARK_ALL, and cs_regions_cigar
+three ways -- over the marks' cigar_regs in either mode, and over all regions as a caller without marks has to -- each as the median, the
+minimum and the maximum of seven calls after a warm-up one, ms per million reads.
 usage: align_bench.py [reads] [--synth-mbp M]"""
 import gzip, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,6 +104,27 @@ def run(n=200000, synth_mbp=0.0):
         assert xc["n_regs"] == int(live.sum()) and same(xcr, {"reg_off": live_off, "regs": hr[live]}, ("reg_off", "regs")), "the compacted regions differ from cs_extend_chains' regions with qe > qb"
         t12 = time.perf_counter(); fg = chd.filter_gpu(c["chain_off"], c["chains"], c["cseed_off"], c["cseeds"], bases, off, copy=False); t13 = time.perf_counter()
         assert same(fg, f, FK), "cs_chain_filter_gpu differs from cs_chain_filter"
+    # marking, MAPQ and line selection (cs_regions_mark), and the CIGAR stage three ways: over cigar_regs in default mode and under
+    # CS_MARK_ALL, and over all de-duplicated regions, which is what a caller without marks has to do.  One warm-up call each, then
+    # MARK_RUNS timed calls: median, min and max wall time as ms per million reads
+    MARK_RUNS = 7
+    def timed(fn):
+        fn()
+        ts = []
+        for _ in range(MARK_RUNS):
+            ta = time.perf_counter(); r = fn(); ts.append((time.perf_counter() - ta) * 1e3 * 1e6 / n)
+        return r, {"runs": MARK_RUNS, "median_ms_per_million_reads": float(np.median(ts)), "min": min(ts), "max": max(ts)}
+    d_off, d_regs = np.array(d["reg_off"]), np.array(d["regs"])
+    for label, mflags in (("default", 0), ("CS_MARK_ALL", ca.MARK_ALL)):
+        ms0 = al.mark_stats(); mk, tm = timed(lambda: al.regions_mark(d_off, d_regs, off, flags=mflags)); ms1 = al.mark_stats()
+        _, tcg = timed(lambda: al.regions_cigar(mk["cigar_reg_off"], mk["cigar_regs"], bases, off))
+        md = {k: (ms1[k] - ms0[k]) / (MARK_RUNS + 1) for k in ms1}
+        out["regions -> marks (%s)" % label] = dict(tm, device_span_ms=md["kernel_ms"], regions=int(d_regs.size), lines=int(mk["line_off"][-1]), xa_members=int((mk["marks"]["xa_of"] >= 0).sum()),
+                                                    cigar_regions=int(mk["cigar_regs"].size), light_reads=int(md["light_reads"]), wave_reads=int(md["wave_reads"]), hbm_reads=int(md["hbm_reads"]),
+                                                    launches=int(md["launches"]), note="host arrays in and out, the binding's copies of the result included")
+        out["marked regions -> CIGAR (%s)" % label] = dict(tcg, regions=int(mk["cigar_regs"].size))
+    _, tca = timed(lambda: al.regions_cigar(d_off, d_regs, bases, off))
+    out["all regions -> CIGAR"] = dict(tca, regions=int(d_regs.size), note="what a caller without cs_regions_mark has to do")
     for name, a, b in (("seed (host call)", t0, t1), ("chain", t1, t2), ("chain_filter", t2, t3), ("extend_chains", t3, t4), ("dedup_regions", t4, t5)):
         out[name] = {"ms": 1e3 * (b - a), "reads_per_s": n / (b - a)}
     kms = sd1["kernel_ms"] - sd0["kernel_ms"]
