@@ -28,6 +28,13 @@
 namespace csa {
 constexpr int32_t UNSET = -99;            // the reference's H0_ (mapping/macro.h:44): a coordinate that has not been set yet
 
+// The counter words: pairs on the left / right list, pairs sent back for the wider band, chains whose first seed lies outside the reference,
+// purged regions, chains on the list of region_big_kernel, reads on the list of purge_big_kernel and that kernel's ticket.  Two words serve
+// twice in cs_extend_chains_device: its checks count into the first two before the core clears the block, and the long chains' count has
+// served when the compaction writes the number of live regions in its place.
+enum { C_LEFT, C_RIGHT, C_RETRY, C_BAD_CHAIN, C_PURGED, C_BIG_CHAINS, C_BIG_READS, C_TICKET, C_COUNT,
+       C_REFUSED = C_LEFT, C_N_BASES = C_RIGHT, C_LIVE = C_BIG_CHAINS };
+
 struct Args {
 	const uint64_t *chain_off, *cseed_off, *read_off; const cs_chain_t *chains; const cs_seed_t *cseeds; const int32_t *score; const uint8_t *bases;
 	int64_t n_reads, n_chains, n_seeds, l_pac; uint64_t n_bases;
@@ -38,7 +45,7 @@ struct Args {
 	cs_ext_pair_t *lp, *rp;
 	int32_t small_chain, light_max, purge_cap;   // SMALL_CHAIN / 64 / PURGE_CAP unless cs_aln_params_t.flags says otherwise (A/B tests)
 	uint32_t *big, *big_reads;             // chains of more than SMALL_CHAIN seeds / reads of more than 64 regions: lists for the *_big kernels
-	unsigned long long *ctr;               // [0] left pairs [1] right pairs [2] retries [3] bad chains [4] purged [5] long chains [6] long reads
+	unsigned long long *ctr;               // the C_* words
 };
 
 __device__ __forceinline__ int affordable_gap(const cs_aln_params_t &o, int qlen) // cal_max_gap (comp_seed.cpp:415-421)
@@ -92,7 +99,7 @@ __global__ void window_kernel(const Args A)
 		const int64_t mid_f = rev ? (l_pac << 1) - 1 - mid : mid;
 		int lo = 0, hi = A.n_ctg;                                         // last contig whose offset is <= mid_f
 		while (hi - lo > 1) { const int m = (lo + hi) >> 1; if (A.ctg_off[m] <= mid_f) lo = m; else hi = m; }
-		if (mid_f < 0 || mid_f >= l_pac || !(w0 <= mid && mid < w1)) { atomicAdd(A.ctr + 3, 1ull); continue; }
+		if (mid_f < 0 || mid_f >= l_pac || !(w0 <= mid && mid < w1)) { atomicAdd(A.ctr + C_BAD_CHAIN, 1ull); continue; }
 		int64_t far_b = A.ctg_off[lo], far_e = far_b + A.ctg_len[lo];
 		if (rev) { const int64_t x = far_b; far_b = (l_pac << 1) - far_e; far_e = (l_pac << 1) - x; }
 		w0 = w0 > far_b ? w0 : far_b; w1 = w1 < far_e ? w1 : far_e;
@@ -177,7 +184,7 @@ __global__ void region_kernel(const Args A)
 		if (ci < A.n_chains) {
 			const uint64_t s0 = A.cseed_off[ci];
 			ns = (int)(A.cseed_off[ci + 1] - s0);
-			if (ns > A.small_chain) A.big[atomicAdd(A.ctr + 5, 1ull)] = (uint32_t)ci;
+			if (ns > A.small_chain) A.big[atomicAdd(A.ctr + C_BIG_CHAINS, 1ull)] = (uint32_t)ci;
 			else if (ns > 0) {
 				mine = true; X = chain_ctx(A, ci); sd = A.cseeds + s0;
 				for (int i = 0; i < ns; ++i) { const cs_seed_t s = sd[i]; nl += s.qbeg != 0; nr += s.qbeg + s.len != X.l_query; }
@@ -186,7 +193,7 @@ __global__ void region_kernel(const Args A)
 		uint32_t tl, tr;
 		const uint32_t el = wave_excl_scan(nl, lane, tl), er = wave_excl_scan(nr, lane, tr);
 		unsigned long long bl = 0, br = 0;
-		if (lane == 0) { if (tl) bl = atomicAdd(A.ctr + 0, (unsigned long long)tl); if (tr) br = atomicAdd(A.ctr + 1, (unsigned long long)tr); }
+		if (lane == 0) { if (tl) bl = atomicAdd(A.ctr + C_LEFT, (unsigned long long)tl); if (tr) br = atomicAdd(A.ctr + C_RIGHT, (unsigned long long)tr); }
 		bl = __shfl(bl, 0); br = __shfl(br, 0);
 		if (mine) {
 			uint64_t ls = bl + el, rs = br + er;
@@ -206,7 +213,7 @@ __global__ void region_big_kernel(const Args A)
 	const int lane = threadIdx.x & 63;
 	const uint64_t lt = (1ull << lane) - 1ull;
 	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-	const uint64_t n_big = A.ctr[5];
+	const uint64_t n_big = A.ctr[C_BIG_CHAINS];
 	for (uint64_t e = wave; e < n_big; e += n_waves) {
 		const int64_t ci = (int64_t)A.big[e];
 		const ChainCtx X = chain_ctx(A, ci);
@@ -219,7 +226,7 @@ __global__ void region_big_kernel(const Args A)
 			if (i < ns) { s = sd[i]; k = seed_rank(sd, sc, ns, i); left = s.qbeg != 0; right = s.qbeg + s.len != X.l_query; }
 			const uint64_t ml = __ballot(left), mr = __ballot(right);
 			unsigned long long bl = 0, br = 0;
-			if (lane == 0) { if (ml) bl = atomicAdd(A.ctr + 0, (unsigned long long)__popcll(ml)); if (mr) br = atomicAdd(A.ctr + 1, (unsigned long long)__popcll(mr)); }
+			if (lane == 0) { if (ml) bl = atomicAdd(A.ctr + C_LEFT, (unsigned long long)__popcll(ml)); if (mr) br = atomicAdd(A.ctr + C_RIGHT, (unsigned long long)__popcll(mr)); }
 			bl = __shfl(bl, 0); br = __shfl(br, 0);
 			if (i < ns) emit_region(A, X, s, i, k, left, right, bl + (uint64_t)__popcll(ml & lt), br + (uint64_t)__popcll(mr & lt));
 		}
@@ -250,7 +257,7 @@ __global__ void apply_kernel(const Args A, const cs_ext_pair_t *pairs, const cs_
 				else { const uint32_t r = A.chain_read[A.reg_ci[g]]; a.qe = (int32_t)(A.read_off[r + 1] - A.read_off[r]); a.re += x.gtle; a.truesc += x.gscore - pr.h0; }
 			}
 			a.w = a.w > w ? a.w : w;
-		} else retry[atomicAdd(A.ctr + 2, 1ull)] = pr;
+		} else retry[atomicAdd(A.ctr + C_RETRY, 1ull)] = pr;
 		A.regs[g] = a;
 	}
 }
@@ -309,7 +316,7 @@ __global__ void purge_kernel(const Args A)
 	for (int64_t r = wave; r < A.n_reads; r += n_waves) {
 		const uint64_t g0 = A.cseed_off[A.chain_off[r]], g1 = A.cseed_off[A.chain_off[r + 1]];
 		if (g1 - g0 < 2) continue;                                  // (a read's first region has nothing in front of it)
-		if (g1 - g0 > (uint64_t)A.light_max) { if (lane == 0) A.big_reads[atomicAdd(A.ctr + 6, 1ull)] = (uint32_t)r; continue; }
+		if (g1 - g0 > (uint64_t)A.light_max) { if (lane == 0) A.big_reads[atomicAdd(A.ctr + C_BIG_READS, 1ull)] = (uint32_t)r; continue; }
 		const int G = (int)(g1 - g0), l_query = (int)(A.read_off[r + 1] - A.read_off[r]);
 		PReg p = {0, 0, 0, 0, 0, 0}; cs_seed_t s = {0, 0, 0}; int first = 0;
 		if (lane < G) purge_load(A, g0, g0 + (uint64_t)lane, p, s, first);
@@ -327,7 +334,7 @@ __global__ void purge_kernel(const Args A)
 		if ((gone >> lane) & 1ull) { A.regs[g0 + (uint64_t)lane].qb = -1; A.regs[g0 + (uint64_t)lane].qe = -1; }
 		if (lane == 0) my += (unsigned long long)__popcll(gone);
 	}
-	if (lane == 0 && my) atomicAdd(A.ctr + 4, my);
+	if (lane == 0 && my) atomicAdd(A.ctr + C_PURGED, my);
 }
 // a read of any size straight from HBM (the fallback of purge_big_kernel): which regions are purged so far is a byte array that is read
 // around the L1 (volatile) -- lane 0 writes, the whole wave reads in the next step.  Every step is a chain of HBM round trips.
@@ -386,12 +393,12 @@ __global__ __launch_bounds__(PB) void purge_big_kernel(const Args A, uint8_t *pf
 	__shared__ uint32_t l_vote[2][PB / 64];
 	const cs_aln_params_t &o = A.o;
 	const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	const uint64_t n_big = A.ctr[6];
+	const uint64_t n_big = A.ctr[C_BIG_READS];
 	unsigned long long my = 0;
 	for (int x = tid; x < PURGE_GAPS; x += PB) l_gap[x] = affordable_gap(o, x);
 	for (;;) {
 		__syncthreads();                                            // (the previous read's last LDS reads are done)
-		if (tid == 0) l_ticket = atomicAdd(A.ctr + 7, 1ull);
+		if (tid == 0) l_ticket = atomicAdd(A.ctr + C_TICKET, 1ull);
 		__syncthreads();
 		const uint64_t e = l_ticket;
 		if (e >= n_big) break;
@@ -418,7 +425,7 @@ __global__ __launch_bounds__(PB) void purge_big_kernel(const Args A, uint8_t *pf
 		}
 		for (int i = tid; i < G; i += PB) if (!l_alive[i]) { A.regs[g0 + (uint64_t)i].qb = -1; A.regs[g0 + (uint64_t)i].qe = -1; }
 	}
-	if (lane == 0 && my) atomicAdd(A.ctr + 4, my);
+	if (lane == 0 && my) atomicAdd(A.ctr + C_PURGED, my);
 }
 
 // ---- cs_extend_chains_device.  The caller's arrays are device memory that no host loop has seen, so what cs_extend_chains' host loops
@@ -451,21 +458,16 @@ __global__ void reg_off_kernel(const DevIn D, uint64_t *reg_off) // a read's reg
 // scan, scatter_kernel and reg_off_live_kernel are compact.hpp's (a device de-duplication would compact its survivors the same way: dedup_pass.hpp).
 } // namespace csa
 
-namespace {
-enum { B_CHAIN_OFF, B_CSEED_OFF, B_READ_OFF, B_CHAINS, B_CSEEDS, B_SCORE, B_BASES, B_PAC, B_CTG_OFF, B_CTG_LEN, B_CHAIN_READ, B_W0, B_WLEN2, B_TB0, B_QBUF, B_TBUF, B_ORD, B_REGS,
-       B_REG_CI, B_LP, B_RP, B_RETRY, B_RES, B_CTR, B_SCAN, B_PFLAG, B_BIG, B_BIG_READS,
-       B_O_REG_OFF, B_O_REGS, B_LIVE, B_LSCAN,   // cs_extend_chains_device: reg_off, the compacted regions, the live flags and their scan
-       B_COUNT };
-} // namespace
+struct cs_aligner_gpu : cs_dev_stage {
+	DevBuf<uint8_t> pac; DevBuf<int64_t> ctg_off; DevBuf<int32_t> ctg_len;                   // the packed reference and the contig table: once
+	DevBuf<uint64_t> chain_off, cseed_off, read_off; DevBuf<cs_chain_t> chains; DevBuf<cs_seed_t> cseeds; DevBuf<int32_t> score; DevBuf<uint8_t> bases;   // cs_extend_chains' uploads
+	DevBuf<uint32_t> chain_read, big, big_reads; DevBuf<int64_t> w0; DevBuf<uint64_t> wlen2, tb0; DevBuf<uint8_t> qbuf, tbuf, pflag;
+	DevBuf<uint32_t> ord, reg_ci; DevBuf<cs_alnreg_t> regs; DevBuf<cs_ext_pair_t> lp, rp, retry; DevBuf<cs_ext_result_t> res; DevBuf<unsigned long long> ctr;
+	DevBuf<uint64_t> o_reg_off; DevBuf<cs_alnreg_t> o_regs; DevBuf<uint32_t> live, lscan;     // cs_extend_chains_device: reg_off, the compacted regions, the live flags and their scan
+};
+static_assert(csa::C_COUNT <= cs_aligner_gpu::N_CTR, "the stage's pinned counter block holds the pass's counters");
 
-struct cs_aligner_gpu : cs_dev_stage<B_COUNT> { bool pac_up = false; };
-
-void cs_aligner_gpu_release_(cs_aligner_gpu *g)
-{
-	if (!g) return;
-	g->release();
-	delete g;
-}
+void cs_aligner_gpu_release_(cs_aligner_gpu *g) { cs_dev_stage_delete_(g); }
 
 namespace {
 // -DCS_ALIGN_TIMING: the laps of a call on stderr (each one waits for the stream)
@@ -481,23 +483,16 @@ struct Lap {
 };
 
 // the aligner's device state, made by its first call; the packed reference and the contig table go up once
-int gpu_state_(cs_aligner_gpu **gp, int device)
+int gpu_state_(cs_aligner_gpu **gp, int device, const cs_refseq_view &R, const std::vector<uint8_t> &pac)
 {
-	if (*gp) { HIP_TRY(hipSetDevice(device)); return CS_OK; }
-	cs_aligner_gpu *g = new cs_aligner_gpu();
-	if (int rc = g->init(device, false)) { cs_aligner_gpu_release_(g); return rc; }
-	*gp = g;
-	return CS_OK;
-}
-int ref_up_(cs_aligner_gpu &G, const cs_refseq_view &R, const std::vector<uint8_t> &pac)
-{
-	if (G.pac_up) return CS_OK;
-	std::vector<int64_t> co(R.offset.begin(), R.offset.end()); std::vector<int32_t> cl(R.len.begin(), R.len.end());
-	if (int rc = G.up(B_PAC, pac.data(), pac.size())) return rc;
-	if (int rc = G.up(B_CTG_OFF, co.data(), co.size() * 8)) return rc;
-	if (int rc = G.up(B_CTG_LEN, cl.data(), cl.size() * 4)) return rc;
-	HIP_TRY(hipStreamSynchronize(G.s));          // (co / cl are locals)
-	G.pac_up = true;
+	if (int rc = cs_dev_stage_make_(gp, device, false, [&](cs_aligner_gpu &g) {
+		if (int rc = g.up(g.pac, pac.data(), pac.size())) return rc;
+		if (int rc = g.up(g.ctg_off, R.offset.data(), R.offset.size())) return rc;
+		if (int rc = g.up(g.ctg_len, R.len.data(), R.len.size())) return rc;
+		HIP_TRY(hipStreamSynchronize(g.s));          // (a failed copy is this call's error, not a later one's)
+		return CS_OK;
+	})) return rc;
+	HIP_TRY(hipSetDevice((*gp)->device));
 	return CS_OK;
 }
 
@@ -506,34 +501,32 @@ struct DevBatch { const uint64_t *chain_off, *cseed_off, *read_off; const cs_cha
                   int64_t n, nc, ns; uint64_t n_bases; };
 
 // The stage itself, device pointers in: windows, regions, both sides' extensions, seed coverage, purge.  On return the regions lie in
-// B_REGS in the reference's order (the purge kernels may still be running on the stream) and ctr[4] counts the purged ones; the offsets
-// were found consistent by the caller (host loops or checking kernels), ns > 0 and the reference is up.
+// G.regs in the reference's order (the purge kernels may still be running on the stream) and C_PURGED counts the purged ones; the offsets
+// were found consistent by the caller (host loops or checking kernels) and ns > 0.
 int extend_core_(cs_aligner_gpu &G, cs_extender_t *ext, const cs_refseq_view &R, const cs_aln_params_t &o, const DevBatch &in, cs_aln_stats_t &st, Lap &lap, const char *who)
 {
 	hipStream_t s = G.s;
 	const int64_t n = in.n, nc = in.nc, ns = in.ns;
 	const uint64_t n_bases = in.n_bases;
-	for (int which : {B_CHAIN_READ, B_BIG}) if (int rc = G.ensure(which, (size_t)nc * 4 + 64)) return rc;
-	if (int rc = G.ensure(B_BIG_READS, (size_t)n * 4 + 64)) return rc;
-	for (int which : {B_W0, B_WLEN2, B_TB0}) if (int rc = G.ensure(which, ((size_t)nc + 1) * 8 + 64)) return rc;
-	if (int rc = G.ensure(B_QBUF, (size_t)n_bases * 2 + 64)) return rc;
-	for (int which : {B_ORD, B_REG_CI}) if (int rc = G.ensure(which, (size_t)ns * 4 + 64)) return rc;
-	if (int rc = G.ensure(B_REGS, (size_t)ns * sizeof(cs_alnreg_t) + 64)) return rc;
-	for (int which : {B_LP, B_RP, B_RETRY}) if (int rc = G.ensure(which, (size_t)ns * sizeof(cs_ext_pair_t) + 64)) return rc;
-	if (int rc = G.ensure(B_RES, (size_t)ns * sizeof(cs_ext_result_t) + 64)) return rc;
-	if (int rc = G.ensure(B_CTR, 8 * sizeof(unsigned long long))) return rc;
-	HIP_TRY(hipMemsetAsync(G.b[B_CTR].p, 0, 8 * sizeof(unsigned long long), s));
+	if (int rc = cs_ensure_each_((size_t)nc, 64, G.chain_read, G.big)) return rc;
+	if (int rc = G.big_reads.ensure((size_t)n, 64)) return rc;
+	if (int rc = cs_ensure_each_((size_t)nc + 1, 64, G.w0, G.wlen2, G.tb0)) return rc;
+	if (int rc = G.qbuf.ensure((size_t)n_bases * 2, 64)) return rc;
+	if (int rc = cs_ensure_each_((size_t)ns, 64, G.ord, G.reg_ci, G.regs, G.lp, G.rp, G.retry, G.res)) return rc;
+	if (int rc = G.ctr.ensure(G.N_CTR)) return rc;
+	unsigned long long *h = G.h_ctr.p;
+	HIP_TRY(hipMemsetAsync(G.ctr.p, 0, G.N_CTR * sizeof *G.ctr.p, s));
 
 	csa::Args A;
 	A.chain_off = in.chain_off; A.cseed_off = in.cseed_off; A.read_off = in.read_off;
 	A.chains = in.chains; A.cseeds = in.cseeds; A.score = in.score;
 	A.bases = in.bases; A.n_reads = n; A.n_chains = nc; A.n_seeds = ns; A.l_pac = R.l_pac; A.n_bases = n_bases;
-	A.pac = G.at<uint8_t>(B_PAC); A.ctg_off = G.at<int64_t>(B_CTG_OFF); A.ctg_len = G.at<int32_t>(B_CTG_LEN); A.n_ctg = (int32_t)R.offset.size();
+	A.pac = G.pac.p; A.ctg_off = G.ctg_off.p; A.ctg_len = G.ctg_len.p; A.n_ctg = (int32_t)R.offset.size();
 	A.o = o;
-	A.chain_read = G.at<uint32_t>(B_CHAIN_READ); A.w0 = G.at<int64_t>(B_W0); A.wlen2 = G.at<uint64_t>(B_WLEN2); A.tb0 = G.at<uint64_t>(B_TB0);
-	A.qbuf = G.at<uint8_t>(B_QBUF); A.tbuf = nullptr; A.ord = G.at<uint32_t>(B_ORD); A.regs = G.at<cs_alnreg_t>(B_REGS); A.reg_ci = G.at<uint32_t>(B_REG_CI);
-	A.lp = G.at<cs_ext_pair_t>(B_LP); A.rp = G.at<cs_ext_pair_t>(B_RP); A.ctr = G.at<unsigned long long>(B_CTR);
-	A.big = G.at<uint32_t>(B_BIG); A.big_reads = G.at<uint32_t>(B_BIG_READS);
+	A.chain_read = G.chain_read.p; A.w0 = G.w0.p; A.wlen2 = G.wlen2.p; A.tb0 = G.tb0.p;
+	A.qbuf = G.qbuf.p; A.tbuf = nullptr; A.ord = G.ord.p; A.regs = G.regs.p; A.reg_ci = G.reg_ci.p;
+	A.lp = G.lp.p; A.rp = G.rp.p; A.ctr = G.ctr.p;
+	A.big = G.big.p; A.big_reads = G.big_reads.p;
 	A.small_chain = (o.flags & CS_ALN_NO_LIGHT_PATHS) ? 0 : csa::SMALL_CHAIN; A.light_max = (o.flags & CS_ALN_NO_LIGHT_PATHS) ? 1 : 64;
 	A.purge_cap = (o.flags & CS_ALN_PURGE_FROM_HBM) ? 0 : csa::PURGE_CAP;
 
@@ -543,41 +536,41 @@ int extend_core_(cs_aligner_gpu &G, cs_extender_t *ext, const cs_refseq_view &R,
 	hipLaunchKernelGGL(csa::window_kernel, G.grid(nc), dim3(256), 0, s, A);
 	HIP_TRY(hipGetLastError());
 	{ // every window's place in the target buffer: exclusive scan of 2 x length (one element more: the total)
-		HIP_TRY(hipMemsetAsync(A.wlen2 + nc, 0, 8, s));
-		if (int rc = G.scan<uint64_t>(B_SCAN, A.wlen2, A.tb0, (size_t)nc + 1, 0)) return rc;
+		HIP_TRY(hipMemsetAsync(A.wlen2 + nc, 0, sizeof *A.wlen2, s));
+		if (int rc = G.scan<uint64_t>(A.wlen2, A.tb0, (size_t)nc + 1, 0)) return rc;
 	}
-	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.tb0 + nc, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(G.h_ctr + 1, A.ctr + 3, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, A.tb0 + nc, sizeof *h, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h + 1, A.ctr + csa::C_BAD_CHAIN, sizeof *h, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	if (G.h_ctr[1]) return cs_fail_(CS_EINVAL, std::string(who) + ": a chain's first seed lies outside the reference");
+	const uint64_t t_bytes = h[0], n_bad_chains = h[1];
+	if (n_bad_chains) return cs_fail_(CS_EINVAL, std::string(who) + ": a chain's first seed lies outside the reference");
 	lap("queries, windows, scan");
-	const uint64_t t_bytes = G.h_ctr[0];
-	if (int rc = G.ensure(B_TBUF, (size_t)t_bytes + 64)) return rc;
-	A.tbuf = G.at<uint8_t>(B_TBUF);
+	if (int rc = G.tbuf.ensure((size_t)t_bytes, 64)) return rc;
+	A.tbuf = G.tbuf.p;
 	hipLaunchKernelGGL(csa::fill_kernel, G.grid(nc * 64), dim3(256), 0, s, A);
 	lap("fill");
 	hipLaunchKernelGGL(csa::region_kernel, G.grid(nc), dim3(256), 0, s, A);
 	hipLaunchKernelGGL(csa::region_big_kernel, dim3((unsigned)G.n_cu * 8), dim3(256), 0, s, A);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.ctr, 2 * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, A.ctr, 2 * sizeof *h, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	const uint64_t n_left = G.h_ctr[0], n_right = G.h_ctr[1];
+	const uint64_t n_left = h[csa::C_LEFT], n_right = h[csa::C_RIGHT];
 	lap("regions");
 
 	// ---- the dynamic programming (extend.hip), each side: band w, then 2w for the pairs whose path came close to the band's edge
 	auto run_side = [&](cs_ext_pair_t *pairs, uint64_t cnt, bool is_left, int pen_clip) -> int {
-		cs_ext_pair_t *cur = pairs, *nxt = G.at<cs_ext_pair_t>(B_RETRY);
+		cs_ext_pair_t *cur = pairs, *nxt = G.retry.p;
 		for (int attempt = 0; attempt < 2 && cnt; ++attempt) { // MAX_BAND_TRY (comp_seed.cpp:423)
 			const int w = o.w << attempt;
-			const int rc = cs_extend_batch_device(ext, (int64_t)cnt, cur, A.qbuf, n_bases * 2, A.tbuf, t_bytes, w, G.at<cs_ext_result_t>(B_RES));
+			const int rc = cs_extend_batch_device(ext, (int64_t)cnt, cur, A.qbuf, n_bases * 2, A.tbuf, t_bytes, w, G.res.p);
 			if (rc != CS_OK) return rc;
 			st.pairs += cnt; st.launches++;
-			HIP_TRY(hipMemsetAsync(A.ctr + 2, 0, 8, s));
-			hipLaunchKernelGGL(csa::apply_kernel, G.grid((int64_t)cnt), dim3(256), 0, s, A, (const cs_ext_pair_t *)cur, G.at<cs_ext_result_t>(B_RES), cnt, w, attempt, is_left ? 1 : 0, pen_clip, nxt);
+			HIP_TRY(hipMemsetAsync(A.ctr + csa::C_RETRY, 0, sizeof *A.ctr, s));
+			hipLaunchKernelGGL(csa::apply_kernel, G.grid((int64_t)cnt), dim3(256), 0, s, A, (const cs_ext_pair_t *)cur, (const cs_ext_result_t *)G.res.p, cnt, w, attempt, is_left ? 1 : 0, pen_clip, nxt);
 			HIP_TRY(hipGetLastError());
-			HIP_TRY(hipMemcpyAsync(G.h_ctr, A.ctr + 2, 8, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipMemcpyAsync(h, A.ctr + csa::C_RETRY, sizeof *h, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
-			cnt = G.h_ctr[0]; st.retries += cnt;
+			cnt = h[0]; st.retries += cnt;
 			std::swap(cur, nxt);
 		}
 		return CS_OK;
@@ -590,11 +583,11 @@ int extend_core_(cs_aligner_gpu &G, cs_extender_t *ext, const cs_refseq_view &R,
 	lap("right side");
 	hipLaunchKernelGGL(csa::seedcov_kernel, G.grid(ns), dim3(256), 0, s, A);
 	lap("seedcov");
-	if (int rc = G.ensure(B_PFLAG, (size_t)ns + 64)) return rc;
-	HIP_TRY(hipMemsetAsync(G.b[B_PFLAG].p, 0, (size_t)ns, s));
+	if (int rc = G.pflag.ensure((size_t)ns, 64)) return rc;
+	HIP_TRY(hipMemsetAsync(G.pflag.p, 0, (size_t)ns, s));
 	hipLaunchKernelGGL(csa::purge_kernel, G.grid(n * 64), dim3(256), 0, s, A);
 	lap("purge, light reads");
-	hipLaunchKernelGGL(csa::purge_big_kernel, dim3((unsigned)G.n_cu), dim3(csa::PB), 0, s, A, G.at<uint8_t>(B_PFLAG));
+	hipLaunchKernelGGL(csa::purge_big_kernel, dim3((unsigned)G.n_cu), dim3(csa::PB), 0, s, A, G.pflag.p);
 	HIP_TRY(hipGetLastError());
 	lap("purge");
 	return CS_OK;
@@ -606,7 +599,7 @@ int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, c
                           const cs_chain_result_t *chains, const int32_t *cseed_score, const uint8_t *bases, const uint64_t *read_offsets,
                           std::vector<uint64_t> &reg_off, std::vector<cs_alnreg_t> &regs, cs_aln_stats_t &st)
 {
-	if (int rc = gpu_state_(gp, device)) return rc;
+	if (int rc = gpu_state_(gp, device, R, pac)) return rc;
 	cs_aligner_gpu &G = **gp;
 	hipStream_t s = G.s;
 	Lap lap(s, "cs_extend_chains");
@@ -617,25 +610,24 @@ int cs_extend_chains_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t *ext, c
 	if (ns == 0) { regs.clear(); return CS_OK; }
 	if (ns >= 0x7fffffffll || nc >= 0xffffffffll) return cs_fail_(CS_ERANGE, "cs_extend_chains: more than 2^31 regions in one call");
 	const uint64_t n_bases = read_offsets[n];
-	if (int rc = G.up(B_CHAIN_OFF, chains->chain_off, ((size_t)n + 1) * 8)) return rc;
-	if (int rc = G.up(B_CSEED_OFF, chains->cseed_off, ((size_t)nc + 1) * 8)) return rc;
-	if (int rc = G.up(B_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
-	if (int rc = G.up(B_CHAINS, chains->chains, (size_t)nc * sizeof(cs_chain_t))) return rc;
-	if (int rc = G.up(B_CSEEDS, chains->cseeds, (size_t)ns * sizeof(cs_seed_t))) return rc;
-	if (cseed_score) { if (int rc = G.up(B_SCORE, cseed_score, (size_t)ns * 4)) return rc; }
-	if (int rc = G.up(B_BASES, bases, (size_t)n_bases)) return rc;
-	if (int rc = ref_up_(G, R, pac)) return rc;
+	if (int rc = G.up(G.chain_off, chains->chain_off, (size_t)n + 1)) return rc;
+	if (int rc = G.up(G.cseed_off, chains->cseed_off, (size_t)nc + 1)) return rc;
+	if (int rc = G.up(G.read_off, read_offsets, (size_t)n + 1)) return rc;
+	if (int rc = G.up(G.chains, chains->chains, (size_t)nc)) return rc;
+	if (int rc = G.up(G.cseeds, chains->cseeds, (size_t)ns)) return rc;
+	if (cseed_score) { if (int rc = G.up(G.score, cseed_score, (size_t)ns)) return rc; }
+	if (int rc = G.up(G.bases, bases, (size_t)n_bases)) return rc;
 	lap("uploads");
-	const DevBatch in = {G.at<uint64_t>(B_CHAIN_OFF), G.at<uint64_t>(B_CSEED_OFF), G.at<uint64_t>(B_READ_OFF), G.at<cs_chain_t>(B_CHAINS),
-	                     G.at<cs_seed_t>(B_CSEEDS), cseed_score ? G.at<int32_t>(B_SCORE) : nullptr, G.at<uint8_t>(B_BASES), n, nc, ns, n_bases};
+	const DevBatch in = {G.chain_off.p, G.cseed_off.p, G.read_off.p, G.chains.p, G.cseeds.p, cseed_score ? G.score.p : nullptr, G.bases.p, n, nc, ns, n_bases};
 	if (int rc = extend_core_(G, ext, R, o, in, st, lap, "cs_extend_chains")) return rc;
 	regs.resize((size_t)ns);
 	lap("host resize");
-	HIP_TRY(hipMemcpyAsync(regs.data(), G.b[B_REGS].p, (size_t)ns * sizeof(cs_alnreg_t), hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(G.h_ctr, G.at<unsigned long long>(B_CTR) + 4, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(regs.data(), G.regs.p, (size_t)ns * sizeof(cs_alnreg_t), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.h_ctr.p, G.ctr.p + csa::C_PURGED, sizeof *G.ctr.p, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
+	const uint64_t n_purged = G.h_ctr.p[0];
 	lap("download");
-	st.purged += G.h_ctr[0]; st.regions += (uint64_t)ns;
+	st.purged += n_purged; st.regions += (uint64_t)ns;
 	return CS_OK;
 }
 
@@ -645,55 +637,55 @@ int cs_extend_chains_device_gpu_(cs_aligner_gpu **gp, int device, cs_extender_t 
                                  const cs_chain_result_t *d_chains, const int32_t *d_cseed_score, const uint8_t *d_bases, const uint64_t *d_read_offsets, uint32_t flags,
                                  cs_aln_result_t *d_out, cs_aln_stats_t &st)
 {
-	if (int rc = gpu_state_(gp, device)) return rc;
+	if (int rc = gpu_state_(gp, device, R, pac)) return rc;
 	cs_aligner_gpu &G = **gp;
 	hipStream_t s = G.s;
 	Lap lap(s, "cs_extend_chains_device");
 	const int64_t n = d_chains->n_reads, nc = (int64_t)d_chains->n_chains, ns = (int64_t)d_chains->n_seeds;
-	if (int rc = G.ensure(B_O_REG_OFF, ((size_t)n + 1) * 8)) return rc;
-	if (int rc = G.ensure(B_CTR, 8 * sizeof(unsigned long long))) return rc;
-	unsigned long long *ctr = G.at<unsigned long long>(B_CTR);
-	uint64_t *reg_off = G.at<uint64_t>(B_O_REG_OFF);
+	if (int rc = G.o_reg_off.ensure((size_t)n + 1)) return rc;
+	if (int rc = G.ctr.ensure(G.N_CTR)) return rc;
+	unsigned long long *ctr = G.ctr.p, *h = G.h_ctr.p;
+	uint64_t *reg_off = G.o_reg_off.p;
 	if ((n == 0 && nc > 0) || (nc == 0 && ns > 0)) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: chains without reads or seeds without chains");
 	const csa::DevIn D = {d_chains->chain_off, d_chains->cseed_off, d_read_offsets, d_chains->chains, n, (uint64_t)nc, (uint64_t)ns};
-	// [0] what the checks refuse, [1] n_bases = read_offsets[n_reads]: one small copy, one wait
-	HIP_TRY(hipMemsetAsync(ctr, 0, 8 * sizeof(unsigned long long), s));
-	if (n > 0) hipLaunchKernelGGL(csa::check_reads_kernel, G.grid(n), dim3(256), 0, s, D, ctr);
-	if (nc > 0) hipLaunchKernelGGL(csa::check_chains_kernel, G.grid(nc), dim3(256), 0, s, D, ctr);
+	// C_REFUSED: what the checks refuse, C_N_BASES: read_offsets[n_reads]; one small copy, one wait
+	HIP_TRY(hipMemsetAsync(ctr, 0, G.N_CTR * sizeof *ctr, s));
+	if (n > 0) hipLaunchKernelGGL(csa::check_reads_kernel, G.grid(n), dim3(256), 0, s, D, ctr + csa::C_REFUSED);
+	if (nc > 0) hipLaunchKernelGGL(csa::check_chains_kernel, G.grid(nc), dim3(256), 0, s, D, ctr + csa::C_REFUSED);
 	HIP_TRY(hipGetLastError());
-	if (n > 0) HIP_TRY(hipMemcpyAsync(ctr + 1, d_read_offsets + n, 8, hipMemcpyDeviceToDevice, s));
-	HIP_TRY(hipMemcpyAsync(G.h_ctr, ctr, 2 * 8, hipMemcpyDeviceToHost, s));
+	if (n > 0) HIP_TRY(hipMemcpyAsync(ctr + csa::C_N_BASES, d_read_offsets + n, sizeof *ctr, hipMemcpyDeviceToDevice, s));
+	HIP_TRY(hipMemcpyAsync(h, ctr, 2 * sizeof *ctr, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	if (G.h_ctr[0]) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: chain_off / cseed_off are not CSR offset arrays from 0 to n_chains / n_seeds that match the chains' seed counts, read_offsets do not start at 0 or decrease, or a read with chains has 65,536 bases or more");
-	const uint64_t n_bases = G.h_ctr[1];
+	const uint64_t n_refused = h[csa::C_REFUSED], n_bases = h[csa::C_N_BASES];
+	if (n_refused) return cs_fail_(CS_EINVAL, "cs_extend_chains_device: chain_off / cseed_off are not CSR offset arrays from 0 to n_chains / n_seeds that match the chains' seed counts, read_offsets do not start at 0 or decrease, or a read with chains has 65,536 bases or more");
 	lap("checks");
 	if (n > 0 && nc > 0) { hipLaunchKernelGGL(csa::reg_off_kernel, G.grid(n + 1), dim3(256), 0, s, D, reg_off); HIP_TRY(hipGetLastError()); }
-	else HIP_TRY(hipMemsetAsync(reg_off, 0, ((size_t)n + 1) * 8, s));
+	else HIP_TRY(hipMemsetAsync(reg_off, 0, ((size_t)n + 1) * sizeof *reg_off, s));
 	st.reads += (uint64_t)n;
-	d_out->n_reads = n; d_out->n_regs = 0; d_out->reg_off = reg_off; d_out->regs = G.at<cs_alnreg_t>(B_REGS);
+	d_out->n_reads = n; d_out->n_regs = 0; d_out->reg_off = reg_off; d_out->regs = G.regs.p;
 	if (ns == 0) { HIP_TRY(hipStreamSynchronize(s)); return CS_OK; }
-	if (int rc = ref_up_(G, R, pac)) return rc;
 	const DevBatch in = {d_chains->chain_off, d_chains->cseed_off, d_read_offsets, d_chains->chains, d_chains->cseeds, d_cseed_score, d_bases, n, nc, ns, n_bases};
 	if (int rc = extend_core_(G, ext, R, o, in, st, lap, "cs_extend_chains_device")) return rc;
-	ctr = G.at<unsigned long long>(B_CTR);
-	const cs_alnreg_t *regs = G.at<cs_alnreg_t>(B_REGS);
+	const cs_alnreg_t *regs = G.regs.p;
 	if (flags & CS_ALN_DEV_COMPACT) {
-		for (int which : {B_LIVE, B_LSCAN}) if (int rc = G.ensure(which, ((size_t)ns + 1) * 4)) return rc;
-		if (int rc = G.ensure(B_O_REGS, (size_t)ns * sizeof(cs_alnreg_t))) return rc;
-		uint32_t *live = G.at<uint32_t>(B_LIVE), *scan = G.at<uint32_t>(B_LSCAN);
+		if (int rc = cs_ensure_each_((size_t)ns + 1, 0, G.live, G.lscan)) return rc;
+		if (int rc = G.o_regs.ensure((size_t)ns)) return rc;
+		uint32_t *live = G.live.p, *scan = G.lscan.p;
 		hipLaunchKernelGGL(csa::live_kernel, G.grid(ns + 1), dim3(256), 0, s, regs, (uint64_t)ns, live);
 		HIP_TRY(hipGetLastError());
-		if (int rc = G.scan<uint32_t>(B_SCAN, live, scan, (size_t)ns + 1, 0)) return rc;
-		hipLaunchKernelGGL(csa::scatter_kernel, G.grid(ns * csa::REG_WORDS), dim3(256), 0, s, (const uint64_t *)regs, (uint64_t)ns, (const uint32_t *)live, (const uint32_t *)scan, G.at<uint64_t>(B_O_REGS));
-		hipLaunchKernelGGL(csa::reg_off_live_kernel, G.grid(n + 1), dim3(256), 0, s, reg_off, n, (const uint32_t *)scan, (uint64_t)ns, ctr + 5);   // ([5], the long chains' count, has served)
+		if (int rc = G.scan<uint32_t>(live, scan, (size_t)ns + 1, 0)) return rc;
+		hipLaunchKernelGGL(csa::scatter_kernel, G.grid(ns * csa::REG_WORDS), dim3(256), 0, s, (const uint64_t *)regs, (uint64_t)ns, (const uint32_t *)live, (const uint32_t *)scan, (uint64_t *)G.o_regs.p);
+		hipLaunchKernelGGL(csa::reg_off_live_kernel, G.grid(n + 1), dim3(256), 0, s, reg_off, n, (const uint32_t *)scan, (uint64_t)ns, ctr + csa::C_LIVE);   // (the long chains' count, the same word, has served)
 		HIP_TRY(hipGetLastError());
 		lap("compaction");
 	}
-	HIP_TRY(hipMemcpyAsync(G.h_ctr, ctr + 4, 2 * 8, hipMemcpyDeviceToHost, s));   // [4] purged, [5] live regions
+	static_assert(csa::C_LIVE == csa::C_PURGED + 1, "one copy fetches both");
+	HIP_TRY(hipMemcpyAsync(h, ctr + csa::C_PURGED, 2 * sizeof *ctr, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
+	const uint64_t n_purged = h[0], n_live = h[1];
 	lap("counters");
-	st.purged += G.h_ctr[0]; st.regions += (uint64_t)ns;
-	if (flags & CS_ALN_DEV_COMPACT) { d_out->n_regs = G.h_ctr[1]; d_out->regs = G.at<cs_alnreg_t>(B_O_REGS); }
+	st.purged += n_purged; st.regions += (uint64_t)ns;
+	if (flags & CS_ALN_DEV_COMPACT) { d_out->n_regs = n_live; d_out->regs = G.o_regs.p; }
 	else { d_out->n_regs = (uint64_t)ns; d_out->regs = regs; }
 	return CS_OK;
 }

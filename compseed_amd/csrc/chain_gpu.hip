@@ -34,6 +34,9 @@ constexpr int STACK = 32;                  // traversal stack: a tree of height 
 struct Chain { int64_t pos; int32_t rid, n; cs_seed_t head, tail; uint32_t first, last; };   // chain.cpp's Chain
 struct Node { int32_t n, internal; int64_t pos[BMAX]; int32_t id[BMAX]; int32_t kid[BMAX + 1]; };
 
+// the counter words: reads on the wave list, reads on the tree list, arena nodes reserved, reads with inconsistent offsets, arena overflows
+enum { C_WAVE, C_TREE, C_NODES, C_BAD, C_OVERFLOW, C_COUNT };
+
 struct Args {
 	const uint64_t *mem_off, *seed_off, *read_off; const cs_intv_t *mems; const cs_seed_t *seeds;
 	int64_t n_reads; uint64_t n_mems, n_seeds; int64_t l_pac;
@@ -44,7 +47,7 @@ struct Args {
 	uint64_t *nch, *nsd;                                           // per read: counts (n + 1, the last 0), scanned into chain_off / sbase
 	uint32_t *wave_list, *tree_list; uint64_t *tree_node0;         // reads for the wave kernel / the tree kernel (with their arena start)
 	Node *arena;
-	unsigned long long *ctr;   // [0] wave reads [1] tree reads [2] arena nodes [3] inconsistent offsets [4] arena overflow
+	unsigned long long *ctr;   // the C_* words
 	uint64_t *chain_off, *sbase, *cseed_off; cs_chain_t *chains; cs_seed_t *cseeds;
 };
 
@@ -112,9 +115,9 @@ __device__ __forceinline__ void append_seed(const Args &A, uint64_t b, int32_t i
 }
 __device__ __forceinline__ void push_tree(const Args &A, int64_t r, uint64_t n_seeds)
 {
-	const unsigned long long t = atomicAdd(A.ctr + 1, 1ull);
+	const unsigned long long t = atomicAdd(A.ctr + C_TREE, 1ull);
 	A.tree_list[t] = (uint32_t)r;
-	A.tree_node0[t] = atomicAdd(A.ctr + 2, (unsigned long long)(n_seeds / 4 + 2));
+	A.tree_node0[t] = atomicAdd(A.ctr + C_NODES, (unsigned long long)(n_seeds / 4 + 2));
 }
 
 // number of keys <= k in the ascending key[0..n): W = 1 a binary search, W = 64 a 64-ary one (lanes probe, a ballot counts)
@@ -195,18 +198,18 @@ __global__ void __launch_bounds__(256) fast_kernel(Args A)
 	for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < A.n_reads; r += (int64_t)gridDim.x * blockDim.x) {
 		const uint64_t b = A.seed_off[r], e = A.seed_off[r + 1];
 		A.nch[r] = 0; A.nsd[r] = 0;
-		if (e < b || e > A.n_seeds || A.mem_off[r + 1] < A.mem_off[r] || A.mem_off[r + 1] > A.n_mems) { atomicAdd(A.ctr + 3, 1ull); continue; }
+		if (e < b || e > A.n_seeds || A.mem_off[r + 1] < A.mem_off[r] || A.mem_off[r + 1] > A.n_mems) { atomicAdd(A.ctr + C_BAD, 1ull); continue; }
 		const int len = (int)(A.read_off[r + 1] - A.read_off[r]);
 		if (A.flags & CS_CHAIN_TREE_ONLY) { push_tree(A, r, e - b); continue; }
 		if (len < A.o.min_seed_len) continue;
-		if (e - b > (uint64_t)WAVE_MIN) { A.wave_list[atomicAdd(A.ctr + 0, 1ull)] = (uint32_t)r; continue; }
+		if (e - b > (uint64_t)WAVE_MIN) { A.wave_list[atomicAdd(A.ctr + C_WAVE, 1ull)] = (uint32_t)r; continue; }
 		if (!chain_fast<1>(A, r, 0)) push_tree(A, r, e - b);
 	}
 }
 
 __global__ void __launch_bounds__(64) fast_wave_kernel(Args A)
 {
-	const unsigned long long n = A.ctr[0];
+	const unsigned long long n = A.ctr[C_WAVE];
 	const int lane = threadIdx.x;
 	for (unsigned long long w = blockIdx.x; w < n; w += gridDim.x) {
 		const int64_t r = A.wave_list[w];
@@ -216,7 +219,7 @@ __global__ void __launch_bounds__(64) fast_wave_kernel(Args A)
 	}
 }
 
-// chain.cpp's Tree with the nodes in the arena; false = the arena reserve ran out (cannot happen: counted in ctr[4])
+// chain.cpp's Tree with the nodes in the arena; false = the arena reserve ran out (cannot happen: counted in C_OVERFLOW)
 struct Tree {
 	Node *nd; int cap, cnt, root, size;
 	__device__ void init(Node *p, int c) { nd = p; cap = c; cnt = 1; root = 0; size = 0; nd[0].n = 0; nd[0].internal = 0; }
@@ -288,7 +291,7 @@ struct Tree {
 
 __global__ void __launch_bounds__(256) tree_kernel(Args A)
 {
-	const unsigned long long n_tree = A.ctr[1];
+	const unsigned long long n_tree = A.ctr[C_TREE];
 	for (unsigned long long t = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; t < n_tree; t += (unsigned long long)gridDim.x * blockDim.x) {
 		const int64_t r = A.tree_list[t];
 		const uint64_t b = A.seed_off[r], e = A.seed_off[r + 1];
@@ -314,7 +317,7 @@ __global__ void __launch_bounds__(256) tree_kernel(Args A)
 			}
 			if (add) { new_chain(A, b, n, s, rid, li); ok = T.put(s.rbeg, n); ++n; }
 		}
-		if (!ok) { atomicAdd(A.ctr + 4, 1ull); continue; }
+		if (!ok) { atomicAdd(A.ctr + C_OVERFLOW, 1ull); continue; }
 		const float frac = frac_rep_of(A, r, len);
 		uint32_t nc = 0, ns = 0;
 		if (T.size) {   // in-order traversal: entry (x, j): j = 2i -> descend into kid[i] first, j = 2i + 1 -> emit key i
@@ -333,7 +336,7 @@ __global__ void __launch_bounds__(256) tree_kernel(Args A)
 				if (i < T.nd[x].n) { emit_chain(A, b, frac, T.nd[x].id[i], nc, ns); sj[sp - 1] = j + 1; } else --sp;
 			}
 		}
-		if (!ok) { atomicAdd(A.ctr + 4, 1ull); nc = ns = 0; }
+		if (!ok) { atomicAdd(A.ctr + C_OVERFLOW, 1ull); nc = ns = 0; }
 		A.nch[r] = nc; A.nsd[r] = ns;
 	}
 }
@@ -352,20 +355,17 @@ __global__ void __launch_bounds__(256) compact_kernel(Args A)
 }
 } // namespace csc
 
-namespace {
-enum { B_CTG_OFF, B_IS_ALT, B_KEY, B_CID, B_POOL, B_NEXT, B_TCH, B_TSD, B_NCH, B_NSD, B_WAVE, B_TREE, B_NODE0, B_ARENA, B_CTR, B_SCAN,
-       B_CHAIN_OFF, B_SBASE, B_CSEED_OFF, B_CHAINS, B_CSEEDS,
-       B_IN_MEM_OFF, B_IN_MEMS, B_IN_SEED_OFF, B_IN_SEEDS, B_IN_READ_OFF, B_COUNT };   // B_IN_*: cs_chain_batch_gpu's uploads
-} // namespace
+struct cs_chainer_gpu : cs_dev_stage {
+	int n_ctg = 0; cs_chain_stats_t st = {};
+	DevBuf<int64_t> ctg_off; DevBuf<int32_t> is_alt;                                          // contig offsets and ALT flags: once
+	DevBuf<int64_t> key; DevBuf<int32_t> cid; DevBuf<csc::Chain> pool; DevBuf<uint32_t> next_of; DevBuf<cs_chain_t> tch, chains; DevBuf<cs_seed_t> tsd, cseeds;   // per seed
+	DevBuf<uint64_t> cseed_off, nch, nsd, tree_node0, chain_off, sbase; DevBuf<uint32_t> wave_list, tree_list;   // cseed_off per seed, the rest per read
+	DevBuf<csc::Node> arena; DevBuf<unsigned long long> ctr;
+	DevBuf<uint64_t> in_mem_off, in_seed_off, in_read_off; DevBuf<cs_intv_t> in_mems; DevBuf<cs_seed_t> in_seeds;   // cs_chain_batch_gpu's uploads
+};
+static_assert(csc::C_COUNT <= cs_chainer_gpu::N_CTR, "the stage's pinned counter block holds the pass's counters");
 
-struct cs_chainer_gpu : cs_dev_stage<B_COUNT> { int n_ctg = 0; cs_chain_stats_t st = {}; };
-
-void cs_chainer_gpu_release_(cs_chainer_gpu *g)
-{
-	if (!g) return;
-	g->release();
-	delete g;
-}
+void cs_chainer_gpu_release_(cs_chainer_gpu *g) { cs_dev_stage_delete_(g); }
 
 int cs_chainer_gpu_device_(const cs_chainer_gpu *g) { return g->device; }
 
@@ -376,83 +376,81 @@ int gpu_init(cs_chainer *c, int device)
 	const hipError_t he = hipGetDeviceCount(&ndev);
 	if (he != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return cs_fail_(CS_EDEVICE, "no HIP device: the device chainer has no CPU path"); }
 	if (device < 0 || device >= ndev) return cs_fail_(CS_EINVAL, "cs_chainer_create_device: no such device");
-	cs_chainer_gpu *g = new cs_chainer_gpu(); c->gpu = g;   // (released with the chainer, whatever fails below)
-	if (int rc = g->init(device, true)) return rc;
-	const cs_refseq_view &R = c->ref;   // contig offsets and ALT flags, once
-	g->n_ctg = (int)R.offset.size();
-	std::vector<int32_t> alt(R.is_alt.begin(), R.is_alt.end());
-	if (int rc = g->ensure(B_CTG_OFF, R.offset.size() * 8 + 8)) return rc;
-	if (int rc = g->ensure(B_IS_ALT, alt.size() * 4 + 4)) return rc;
-	HIP_TRY(hipMemcpy(g->b[B_CTG_OFF].p, R.offset.data(), R.offset.size() * 8, hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(g->b[B_IS_ALT].p, alt.data(), alt.size() * 4, hipMemcpyHostToDevice));
-	return CS_OK;
+	return cs_dev_stage_make_(&c->gpu, device, true, [&](cs_chainer_gpu &g) {
+		const cs_refseq_view &R = c->ref;   // contig offsets and ALT flags, once
+		g.n_ctg = (int)R.offset.size();
+		std::vector<int32_t> alt(R.is_alt.begin(), R.is_alt.end());
+		if (int rc = g.ctg_off.ensure(R.offset.size(), 8)) return rc;
+		if (int rc = g.is_alt.ensure(alt.size(), 4)) return rc;
+		HIP_TRY(hipMemcpy(g.ctg_off.p, R.offset.data(), R.offset.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(g.is_alt.p, alt.data(), alt.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+		return CS_OK;
+	});
 }
 
 // the whole chain pass over a device-resident batch; the result stays in the chainer's device buffers
 int chain_device_(cs_chainer *c, const cs_chain_params_t &o, const cs_result_t &S, const uint64_t *d_ro, uint32_t flags, cs_chain_result_t &out)
 {
 	cs_chainer_gpu &G = *c->gpu;
-	constexpr int N_CTR = cs_chainer_gpu::N_CTR;
 	HIP_TRY(hipSetDevice(G.device));
 	hipStream_t s = G.s;
 	const int64_t n = S.n_reads;
 	const uint64_t ns = S.n_seeds;
 	if (n >= 0xffffffffll) return cs_fail_(CS_ERANGE, "cs_chain_batch_device: more than 2^32 reads in one call");
 	const size_t per_seed = (size_t)ns + 1, per_read = (size_t)n + 1;
-	struct { int which; size_t bytes; } need[] = {
-		{B_KEY, per_seed * 8}, {B_CID, per_seed * 4}, {B_POOL, per_seed * sizeof(csc::Chain)}, {B_NEXT, per_seed * 4}, {B_TCH, per_seed * sizeof(cs_chain_t)},
-		{B_TSD, per_seed * sizeof(cs_seed_t)}, {B_NCH, per_read * 8}, {B_NSD, per_read * 8}, {B_WAVE, per_read * 4}, {B_TREE, per_read * 4}, {B_NODE0, per_read * 8},
-		{B_CTR, N_CTR * 8}, {B_CHAIN_OFF, per_read * 8}, {B_SBASE, per_read * 8}, {B_CSEED_OFF, per_seed * 8}, {B_CHAINS, per_seed * sizeof(cs_chain_t)},
-		{B_CSEEDS, per_seed * sizeof(cs_seed_t)}};
-	for (auto &q : need) if (int rc = G.ensure(q.which, q.bytes)) return rc;
+	if (int rc = cs_ensure_each_(per_seed, 0, G.key, G.cid, G.pool, G.next_of, G.tch, G.tsd, G.cseed_off, G.chains, G.cseeds)) return rc;
+	if (int rc = cs_ensure_each_(per_read, 0, G.nch, G.nsd, G.wave_list, G.tree_list, G.tree_node0, G.chain_off, G.sbase)) return rc;
+	if (int rc = G.ctr.ensure(G.N_CTR)) return rc;
 	csc::Args A;
 	A.mem_off = S.mem_off; A.seed_off = S.seed_off; A.read_off = d_ro; A.mems = S.mems; A.seeds = S.seeds;
 	A.n_reads = n; A.n_mems = S.n_mems; A.n_seeds = ns; A.l_pac = c->ref.l_pac;
-	A.ctg_off = G.at<int64_t>(B_CTG_OFF); A.is_alt = G.at<int32_t>(B_IS_ALT); A.n_ctg = G.n_ctg; A.flags = flags; A.o = o;
-	A.key = G.at<int64_t>(B_KEY); A.cid = G.at<int32_t>(B_CID); A.pool = G.at<csc::Chain>(B_POOL); A.next_of = G.at<uint32_t>(B_NEXT);
-	A.tch = G.at<cs_chain_t>(B_TCH); A.tsd = G.at<cs_seed_t>(B_TSD); A.nch = G.at<uint64_t>(B_NCH); A.nsd = G.at<uint64_t>(B_NSD);
-	A.wave_list = G.at<uint32_t>(B_WAVE); A.tree_list = G.at<uint32_t>(B_TREE); A.tree_node0 = G.at<uint64_t>(B_NODE0); A.arena = nullptr;
-	A.ctr = G.at<unsigned long long>(B_CTR);
-	A.chain_off = G.at<uint64_t>(B_CHAIN_OFF); A.sbase = G.at<uint64_t>(B_SBASE); A.cseed_off = G.at<uint64_t>(B_CSEED_OFF);
-	A.chains = G.at<cs_chain_t>(B_CHAINS); A.cseeds = G.at<cs_seed_t>(B_CSEEDS);
+	A.ctg_off = G.ctg_off.p; A.is_alt = G.is_alt.p; A.n_ctg = G.n_ctg; A.flags = flags; A.o = o;
+	A.key = G.key.p; A.cid = G.cid.p; A.pool = G.pool.p; A.next_of = G.next_of.p;
+	A.tch = G.tch.p; A.tsd = G.tsd.p; A.nch = G.nch.p; A.nsd = G.nsd.p;
+	A.wave_list = G.wave_list.p; A.tree_list = G.tree_list.p; A.tree_node0 = G.tree_node0.p; A.arena = nullptr;
+	A.ctr = G.ctr.p;
+	A.chain_off = G.chain_off.p; A.sbase = G.sbase.p; A.cseed_off = G.cseed_off.p;
+	A.chains = G.chains.p; A.cseeds = G.cseeds.p;
+	unsigned long long *h = G.h_ctr.p;
 	out.n_reads = n; out.chain_off = A.chain_off; out.chains = A.chains; out.cseed_off = A.cseed_off; out.cseeds = A.cseeds;
 	G.st.reads += (uint64_t)n;
 	if (n == 0) {
 		out.n_chains = 0; out.n_seeds = 0;
 		return G.empty_csr(A.chain_off, A.cseed_off);
 	}
-	HIP_TRY(hipMemsetAsync(A.ctr, 0, N_CTR * 8, s));
-	HIP_TRY(hipMemsetAsync(A.nch + n, 0, 8, s));
-	HIP_TRY(hipMemsetAsync(A.nsd + n, 0, 8, s));
+	HIP_TRY(hipMemsetAsync(A.ctr, 0, G.N_CTR * sizeof *A.ctr, s));
+	HIP_TRY(hipMemsetAsync(A.nch + n, 0, sizeof *A.nch, s));
+	HIP_TRY(hipMemsetAsync(A.nsd + n, 0, sizeof *A.nsd, s));
 	HIP_TRY(hipEventRecord(G.ev[0], s));
 	hipLaunchKernelGGL(csc::fast_kernel, G.grid(n, 256), dim3(256), 0, s, A);
 	hipLaunchKernelGGL(csc::fast_wave_kernel, dim3((unsigned)G.n_cu * 8), dim3(64), 0, s, A);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(G.ev[1], s));
-	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.ctr, N_CTR * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, A.ctr, G.N_CTR * sizeof *A.ctr, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	if (G.h_ctr[3]) return cs_fail_(CS_EINVAL, "cs_chain_batch_device: mem_off / seed_off disagree with n_mems / n_seeds");
-	const uint64_t n_tree = G.h_ctr[1], n_nodes = G.h_ctr[2];
+	const uint64_t n_bad = h[csc::C_BAD], n_tree = h[csc::C_TREE], n_nodes = h[csc::C_NODES];
+	if (n_bad) return cs_fail_(CS_EINVAL, "cs_chain_batch_device: mem_off / seed_off disagree with n_mems / n_seeds");
 	unsigned launches = 2;
 	HIP_TRY(hipEventRecord(G.ev[2], s));
 	if (n_tree) {
-		if (int rc = G.ensure(B_ARENA, (size_t)n_nodes * sizeof(csc::Node))) return rc;
-		A.arena = G.at<csc::Node>(B_ARENA);
+		if (int rc = G.arena.ensure((size_t)n_nodes)) return rc;
+		A.arena = G.arena.p;
 		hipLaunchKernelGGL(csc::tree_kernel, G.grid((int64_t)n_tree, 256), dim3(256), 0, s, A);
 		++launches;
 	}
 	// chain_off and the per-read seed bases: exclusive scans over n + 1 counts (the last one 0: the totals)
-	if (int rc = G.scan<uint64_t>(B_SCAN, A.nch, A.chain_off, A.nsd, A.sbase, (size_t)n + 1, 0)) return rc;
+	if (int rc = G.scan<uint64_t>(A.nch, A.chain_off, A.nsd, A.sbase, (size_t)n + 1, 0)) return rc;
 	hipLaunchKernelGGL(csc::compact_kernel, G.grid(n, 256), dim3(256), 0, s, A);
 	HIP_TRY(hipGetLastError());
 	launches += 3;
 	HIP_TRY(hipEventRecord(G.ev[3], s));
-	HIP_TRY(hipMemcpyAsync(G.h_ctr, A.chain_off + n, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(G.h_ctr + 1, A.sbase + n, 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(G.h_ctr + 2, A.ctr + 4, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, A.chain_off + n, sizeof *h, hipMemcpyDeviceToHost, s));   // three totals into the first pinned words
+	HIP_TRY(hipMemcpyAsync(h + 1, A.sbase + n, sizeof *h, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h + 2, A.ctr + csc::C_OVERFLOW, sizeof *h, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	if (G.h_ctr[2]) return cs_fail_(CS_EDEVICE, "cs_chain_batch_device: a tree outgrew its arena reserve");
-	out.n_chains = G.h_ctr[0]; out.n_seeds = G.h_ctr[1];
+	const uint64_t n_chains = h[0], n_cseeds = h[1], n_overflow = h[2];
+	if (n_overflow) return cs_fail_(CS_EDEVICE, "cs_chain_batch_device: a tree outgrew its arena reserve");
+	out.n_chains = n_chains; out.n_seeds = n_cseeds;
 	G.add_kernel_ms(G.st.kernel_ms);
 	G.st.seeds += ns; G.st.chains += out.n_chains; G.st.tree_reads += n_tree; G.st.launches += launches;
 	return CS_OK;
@@ -498,22 +496,21 @@ extern "C" int cs_chain_batch_gpu(cs_chainer_t *c, const cs_chain_params_t *par,
 	cs_result_t d = *seeds;
 	d.n_mems = n_mems; d.n_seeds = n_seeds;
 	if (n > 0) {
-		if (int rc = G.up(B_IN_MEM_OFF, seeds->mem_off, ((size_t)n + 1) * 8)) return rc;
-		if (int rc = G.up(B_IN_MEMS, seeds->mems, (size_t)n_mems * sizeof(cs_intv_t))) return rc;
-		if (int rc = G.up(B_IN_SEED_OFF, seeds->seed_off, ((size_t)n + 1) * 8)) return rc;
-		if (int rc = G.up(B_IN_SEEDS, seeds->seeds, (size_t)n_seeds * sizeof(cs_seed_t))) return rc;
-		if (int rc = G.up(B_IN_READ_OFF, read_offsets, ((size_t)n + 1) * 8)) return rc;
-		d.mem_off = G.at<uint64_t>(B_IN_MEM_OFF); d.mems = G.at<cs_intv_t>(B_IN_MEMS);
-		d.seed_off = G.at<uint64_t>(B_IN_SEED_OFF); d.seeds = G.at<cs_seed_t>(B_IN_SEEDS);
+		if (int rc = G.up(G.in_mem_off, seeds->mem_off, (size_t)n + 1)) return rc;
+		if (int rc = G.up(G.in_mems, seeds->mems, (size_t)n_mems)) return rc;
+		if (int rc = G.up(G.in_seed_off, seeds->seed_off, (size_t)n + 1)) return rc;
+		if (int rc = G.up(G.in_seeds, seeds->seeds, (size_t)n_seeds)) return rc;
+		if (int rc = G.up(G.in_read_off, read_offsets, (size_t)n + 1)) return rc;
+		d.mem_off = G.in_mem_off.p; d.mems = G.in_mems.p;
+		d.seed_off = G.in_seed_off.p; d.seeds = G.in_seeds.p;
 	}
 	cs_chain_result_t dr;
-	if (int rc = chain_device_(c, *par, d, n > 0 ? G.at<uint64_t>(B_IN_READ_OFF) : nullptr, flags, dr)) return rc;
+	if (int rc = chain_device_(c, *par, d, n > 0 ? G.in_read_off.p : nullptr, flags, dr)) return rc;
 	return cs_download_chains_(G.s, dr, nullptr, c->chain_off, c->chains, c->cseed_off, c->cseeds, nullptr, out);
 }
 
 extern "C" int cs_chainer_stats(const cs_chainer_t *c, cs_chain_stats_t *st)
 {
 	if (!c || !st) return cs_fail_(CS_EINVAL, "cs_chainer_stats: null argument");
-	if (c->gpu) *st = c->gpu->st; else memset(st, 0, sizeof *st);
-	return CS_OK;
+	return cs_dev_stage_stats_(c->gpu, st);
 }

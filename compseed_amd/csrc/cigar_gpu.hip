@@ -113,53 +113,35 @@ __global__ void finish_kernel(Args A)
 }
 } // namespace cscg
 
-namespace {
-enum { B_PAC, B_CTG, B_REG_OFF, B_READ_OFF, B_REGS, B_BASES, B_RD, B_CLS, B_W2, B_TRIES, B_SCORE, B_LAST, B_ALNS, B_CTR, B_FLAG, B_SLOT, B_JOBS, B_ZB, B_ZOFF, B_SCAN,
-       B_Z, B_HBM, B_CNT, B_NC, B_NMD, B_COFF, B_MOFF, B_CIGAR, B_MD, B_COUNT };
 static_assert(sizeof(cs_aln_t) == 56 && sizeof(cs_aln_t) % 8 == 0, "cs_aln_t is seven 8-byte words");
-} // namespace
 
-struct cs_cigar_gpu : cs_dev_stage<B_COUNT> {
+struct cs_cigar_gpu : cs_dev_stage {
 	cs_cigar_stats_t st = {};
 	std::vector<cs_aln_t> alns; std::vector<uint32_t> cigar; std::vector<char> md; std::vector<uint64_t> zoff;   // the result, and a try's matrix offsets
+	DevBuf<uint8_t> pac; DevBuf<int64_t> ctg;                                                  // the packed reference and the contig offsets: once
+	DevBuf<uint64_t> reg_off, read_off; DevBuf<cs_alnreg_t> regs; DevBuf<uint8_t> bases;      // the call's input
+	DevBuf<uint32_t> rd; DevBuf<uint8_t> cls; DevBuf<int32_t> w2, tries, score, last_sc; DevBuf<cs_aln_t> d_alns; DevBuf<unsigned long long> ctr;   // per region
+	DevBuf<uint32_t> flag, slot, jobs; DevBuf<uint64_t> zb, d_zoff;                            // per try
+	DevBuf<uint8_t> z; DevBuf<int32_t> hbm; DevBuf<cscg::Counts> cnt; DevBuf<uint64_t> nc, nmd, coff, moff; DevBuf<uint32_t> d_cigar; DevBuf<char> d_md;   // per chunk
 };
 constexpr int N_CTRW = cs_cigar_gpu::N_CTR;
 static_assert(cscg::C_COUNT <= N_CTRW, "the stage's pinned counter block holds the pass's counters");
 
-void cs_cigar_gpu_release_(cs_cigar_gpu *g)
-{
-	if (!g) return;
-	g->release();
-	delete g;
-}
-int cs_cigar_gpu_stats_(const cs_cigar_gpu *g, cs_cigar_stats_t *st)
-{
-	if (g) *st = g->st; else memset(st, 0, sizeof *st);
-	return CS_OK;
-}
-
-namespace {
-int cigar_init(cs_cigar_gpu **gp, int device, const cs_refseq_view &R, const std::vector<uint8_t> &pac)
-{
-	if (*gp) return CS_OK;
-	cs_cigar_gpu *g = new cs_cigar_gpu();
-	*gp = g;                                                          // (released with the aligner, whatever fails below)
-	if (int rc = g->init(device, true)) return rc;
-	if (int rc = g->ensure(B_PAC, pac.size() + 64)) return rc;
-	if (int rc = g->ensure(B_CTG, R.offset.size() * 8 + 8)) return rc;
-	HIP_TRY(hipMemcpy(g->b[B_PAC].p, pac.data(), pac.size(), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(g->b[B_CTG].p, R.offset.data(), R.offset.size() * 8, hipMemcpyHostToDevice));
-	return CS_OK;
-}
-} // namespace
+void cs_cigar_gpu_release_(cs_cigar_gpu *g) { cs_dev_stage_delete_(g); }
+int cs_cigar_gpu_stats_(const cs_cigar_gpu *g, cs_cigar_stats_t *st) { return cs_dev_stage_stats_(g, st); }
 
 int cs_regions_cigar_gpu_(cs_cigar_gpu **gp, int device, const cs_refseq_view &R, const std::vector<uint8_t> &pac, const cs_aln_params_t &o, const cs_aln_result_t *regs,
                           const uint8_t *bases, const uint64_t *read_offsets, uint32_t flags, cs_cigar_result_t *out)
 {
 	using namespace cscg;
-	if (int rc = cigar_init(gp, device, R, pac)) return rc;
+	if (int rc = cs_dev_stage_make_(gp, device, true, [&](cs_cigar_gpu &g) {
+		if (int rc = g.pac.ensure(pac.size(), 64)) return rc;
+		if (int rc = g.ctg.ensure(R.offset.size(), 8)) return rc;
+		HIP_TRY(hipMemcpy(g.pac.p, pac.data(), pac.size(), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(g.ctg.p, R.offset.data(), R.offset.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+		return CS_OK;
+	})) return rc;
 	cs_cigar_gpu &G = **gp;
-	if (!G.h_ctr) return cs_fail_(CS_EDEVICE, "cs_regions_cigar: the device state was not created");
 	HIP_TRY(hipSetDevice(G.device));
 	hipStream_t s = G.s;
 	const int64_t n = regs->n_reads;
@@ -167,36 +149,29 @@ int cs_regions_cigar_gpu_(cs_cigar_gpu **gp, int device, const cs_refseq_view &R
 	G.alns.assign((size_t)n_regs, cs_aln_t()); G.cigar.clear(); G.md.assign(1, 0);
 	auto deliver = [&]() { out->n_regs = n_regs; out->n_cigar = G.cigar.size(); out->md_bytes = G.md.size(); out->alns = G.alns.data(); out->cigar = G.cigar.data(); out->md = G.md.data(); };
 	deliver();
-	if (n == 0 || n_regs == 0) {
-		if (n == 0 && n_regs) return cs_fail_(CS_EINVAL, "cs_regions_cigar: regions without reads");
-		if (n && (regs->reg_off[0] != 0 || read_offsets[0] != 0)) return cs_fail_(CS_EINVAL, "cs_regions_cigar: the offsets do not start at 0");
-		for (int64_t r = 0; r < n; ++r) if (regs->reg_off[r + 1] != 0 || read_offsets[r + 1] < read_offsets[r]) return cs_fail_(CS_EINVAL, "cs_regions_cigar: reg_off / read_offsets are not CSR offset arrays");
-		return CS_OK;
-	}
+	if (n == 0 || n_regs == 0) return cs_check_no_regions_("cs_regions_cigar", regs, read_offsets);
 	const uint64_t n_bases = read_offsets[n];
 	const size_t per_reg = (size_t)n_regs + 1, per_read = (size_t)n + 1;
-	struct { int which; size_t bytes; } need[] = {
-		{B_RD, per_reg * 4}, {B_CLS, per_reg}, {B_W2, per_reg * 4}, {B_TRIES, per_reg * 4}, {B_SCORE, per_reg * 4}, {B_LAST, per_reg * 4}, {B_ALNS, per_reg * sizeof(cs_aln_t)},
-		{B_CTR, N_CTRW * 8}, {B_FLAG, per_reg * 4}, {B_SLOT, per_reg * 4}, {B_JOBS, per_reg * 4}, {B_ZB, per_reg * 8}, {B_ZOFF, per_reg * 8}};
-	for (auto &q : need) if (int rc = G.ensure(q.which, q.bytes)) return rc;
-	if (int rc = G.up(B_REG_OFF, regs->reg_off, per_read * 8)) return rc;
-	if (int rc = G.up(B_READ_OFF, read_offsets, per_read * 8)) return rc;
-	if (int rc = G.up(B_REGS, regs->regs, (size_t)n_regs * sizeof(cs_alnreg_t))) return rc;
-	if (int rc = G.up(B_BASES, bases, (size_t)n_bases)) return rc;
+	if (int rc = cs_ensure_each_(per_reg, 0, G.rd, G.cls, G.w2, G.tries, G.score, G.last_sc, G.d_alns, G.flag, G.slot, G.jobs, G.zb, G.d_zoff)) return rc;
+	if (int rc = G.ctr.ensure(N_CTRW)) return rc;
+	if (int rc = G.up(G.reg_off, regs->reg_off, per_read)) return rc;
+	if (int rc = G.up(G.read_off, read_offsets, per_read)) return rc;
+	if (int rc = G.up(G.regs, regs->regs, (size_t)n_regs)) return rc;
+	if (int rc = G.up(G.bases, bases, (size_t)n_bases)) return rc;
 	Args A = {};
-	A.D = {G.at<uint64_t>(B_REG_OFF), G.at<uint64_t>(B_READ_OFF), G.at<cs_alnreg_t>(B_REGS), G.at<uint8_t>(B_BASES), n, n_regs};
-	A.R = {R.l_pac, G.at<uint8_t>(B_PAC), G.at<int64_t>(B_CTG), (int)R.offset.size()};
+	A.D = {G.reg_off.p, G.read_off.p, G.regs.p, G.bases.p, n, n_regs};
+	A.R = {R.l_pac, G.pac.p, G.ctg.p, (int)R.offset.size()};
 	A.o = o;
-	A.S = {G.at<uint32_t>(B_RD), G.at<uint8_t>(B_CLS), G.at<int32_t>(B_W2), G.at<int32_t>(B_TRIES), G.at<int32_t>(B_SCORE), G.at<int32_t>(B_LAST)};
-	A.alns = G.at<cs_aln_t>(B_ALNS); A.ctr = G.at<unsigned long long>(B_CTR);
-	A.flag = G.at<uint32_t>(B_FLAG); A.slot = G.at<uint32_t>(B_SLOT); A.jobs = G.at<uint32_t>(B_JOBS); A.zb = G.at<uint64_t>(B_ZB); A.zoff = G.at<uint64_t>(B_ZOFF);
-	unsigned long long *h = G.h_ctr;
+	A.S = {G.rd.p, G.cls.p, G.w2.p, G.tries.p, G.score.p, G.last_sc.p};
+	A.alns = G.d_alns.p; A.ctr = G.ctr.p;
+	A.flag = G.flag.p; A.slot = G.slot.p; A.jobs = G.jobs.p; A.zb = G.zb.p; A.zoff = G.d_zoff.p;
+	unsigned long long *h = G.h_ctr.p;
 	uint64_t launches = 0;
-	HIP_TRY(hipMemsetAsync(A.ctr, 0, N_CTRW * 8, s));
+	HIP_TRY(hipMemsetAsync(A.ctr, 0, N_CTRW * sizeof *A.ctr, s));
 	HIP_TRY(hipEventRecord(G.ev[0], s));
 	hipLaunchKernelGGL(check_kernel, G.grid(n, 256), dim3(256), 0, s, A); ++launches;
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(h, A.ctr, N_CTRW * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, A.ctr, N_CTRW * sizeof *A.ctr, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));                                  // the verdict, before any kernel follows an offset
 	if (h[C_BAD]) return cs_fail_(CS_EINVAL, "cs_regions_cigar: reg_off / read_offsets are not CSR offset arrays from 0, a read with regions has 65,536 bases or more, or a region lies outside its read or the reference");
 	const int64_t rows = (int64_t)h[C_LONGEST] + 1;
@@ -206,49 +181,49 @@ int cs_regions_cigar_gpu_(cs_cigar_gpu **gp, int device, const cs_refseq_view &R
 	HIP_TRY(hipGetLastError());
 	const uint64_t budget = (flags & CS_CIGAR_SMALL_SCRATCH) ? SMALL_BUDGET : SCRATCH_BUDGET;
 	for (int pass = 0; pass < 3; ++pass) {
-		if (int rc = G.scan<uint32_t>(B_SCAN, A.flag, A.slot, per_reg, 0u)) return rc;
-		HIP_TRY(hipMemcpyAsync(h, A.slot + n_regs, 4, hipMemcpyDeviceToHost, s));
+		if (int rc = G.scan<uint32_t>(A.flag, A.slot, per_reg, 0u)) return rc;
+		HIP_TRY(hipMemcpyAsync(h, A.slot + n_regs, sizeof *A.slot, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		const uint64_t nj = *(const uint32_t *)h;
 		if (nj == 0) break;
 		hipLaunchKernelGGL(list_kernel, G.grid((int64_t)n_regs, 256), dim3(256), 0, s, A); ++launches;
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemsetAsync(A.zb + nj, 0, 8, s));
-		if (int rc = G.scan<uint64_t>(B_SCAN, A.zb, A.zoff, (size_t)nj + 1, 0ull)) return rc;
+		HIP_TRY(hipMemsetAsync(A.zb + nj, 0, sizeof *A.zb, s));
+		if (int rc = G.scan<uint64_t>(A.zb, A.zoff, (size_t)nj + 1, 0ull)) return rc;
 		G.zoff.resize((size_t)nj + 1);
-		HIP_TRY(hipMemcpyAsync(G.zoff.data(), A.zoff, ((size_t)nj + 1) * 8, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(G.zoff.data(), A.zoff, ((size_t)nj + 1) * sizeof *A.zoff, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		const std::vector<uint64_t> &zoff = G.zoff;
 		for (uint64_t a = 0; a < nj; ) {                               // chunks under the budget; a job above it has a chunk of its own
 			uint64_t b = a + 1;
 			while (b < nj && zoff[b + 1] - zoff[a] <= budget) ++b;
 			const uint64_t nb = b - a;
-			struct { int which; size_t bytes; } cneed[] = {{B_Z, (size_t)(zoff[b] - zoff[a]) + 64}, {B_CNT, (size_t)nb * sizeof(Counts)}, {B_NC, (size_t)(nb + 1) * 8},
-			                                               {B_NMD, (size_t)(nb + 1) * 8}, {B_COFF, (size_t)(nb + 1) * 8}, {B_MOFF, (size_t)(nb + 1) * 8}};
-			for (auto &q : cneed) if (int rc = G.ensure(q.which, q.bytes)) return rc;
+			if (int rc = G.z.ensure((size_t)(zoff[b] - zoff[a]), 64)) return rc;
+			if (int rc = G.cnt.ensure((size_t)nb)) return rc;
+			if (int rc = cs_ensure_each_((size_t)nb + 1, 0, G.nc, G.nmd, G.coff, G.moff)) return rc;
 			const unsigned fill_blocks = (unsigned)std::min<uint64_t>(nb, fill_blocks_max);
 			// H and E beyond the LDS rows: 2 x (longest read + 1) words for each block of THIS chunk's fill
-			if (rows > LDS_ROWS) { if (int rc = G.ensure(B_HBM, (size_t)fill_blocks * 2 * (size_t)rows * 4)) return rc; }
-			A.hbm = G.at<int32_t>(B_HBM);
-			A.a = a; A.b = b; A.z = G.at<uint8_t>(B_Z); A.cnt = G.at<Counts>(B_CNT);
-			A.nc = G.at<uint64_t>(B_NC); A.nmd = G.at<uint64_t>(B_NMD); A.coff = G.at<uint64_t>(B_COFF); A.moff = G.at<uint64_t>(B_MOFF);
-			HIP_TRY(hipMemsetAsync(A.nc + nb, 0, 8, s));
-			HIP_TRY(hipMemsetAsync(A.nmd + nb, 0, 8, s));
+			if (rows > LDS_ROWS) { if (int rc = G.hbm.ensure((size_t)fill_blocks * 2 * (size_t)rows)) return rc; }
+			A.hbm = G.hbm.p;
+			A.a = a; A.b = b; A.z = G.z.p; A.cnt = G.cnt.p;
+			A.nc = G.nc.p; A.nmd = G.nmd.p; A.coff = G.coff.p; A.moff = G.moff.p;
+			HIP_TRY(hipMemsetAsync(A.nc + nb, 0, sizeof *A.nc, s));
+			HIP_TRY(hipMemsetAsync(A.nmd + nb, 0, sizeof *A.nmd, s));
 			hipLaunchKernelGGL(fill_kernel, dim3(fill_blocks), dim3(64), 0, s, A);
 			hipLaunchKernelGGL(count_kernel, G.grid((int64_t)nb, 64), dim3(64), 0, s, A); launches += 2;
 			HIP_TRY(hipGetLastError());
-			if (int rc = G.scan<uint64_t>(B_SCAN, A.nc, A.coff, A.nmd, A.moff, (size_t)nb + 1, 0ull)) return rc;
-			HIP_TRY(hipMemcpyAsync(h, A.coff + nb, 8, hipMemcpyDeviceToHost, s));
-			HIP_TRY(hipMemcpyAsync(h + 1, A.moff + nb, 8, hipMemcpyDeviceToHost, s));
+			if (int rc = G.scan<uint64_t>(A.nc, A.coff, A.nmd, A.moff, (size_t)nb + 1, 0ull)) return rc;
+			HIP_TRY(hipMemcpyAsync(h, A.coff + nb, sizeof *h, hipMemcpyDeviceToHost, s));
+			HIP_TRY(hipMemcpyAsync(h + 1, A.moff + nb, sizeof *h, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
 			const uint64_t tc = h[0], tm = h[1];
-			if (int rc = G.ensure(B_CIGAR, (size_t)tc * 4 + 64)) return rc;
-			if (int rc = G.ensure(B_MD, (size_t)tm + 64)) return rc;
-			A.cigar = G.at<uint32_t>(B_CIGAR); A.md = G.at<char>(B_MD); A.c0 = G.cigar.size(); A.m0 = G.md.size();
+			if (int rc = G.d_cigar.ensure((size_t)tc, 64)) return rc;
+			if (int rc = G.d_md.ensure((size_t)tm, 64)) return rc;
+			A.cigar = G.d_cigar.p; A.md = G.d_md.p; A.c0 = G.cigar.size(); A.m0 = G.md.size();
 			hipLaunchKernelGGL(finish_kernel, G.grid((int64_t)nb, 64), dim3(64), 0, s, A); ++launches;
 			HIP_TRY(hipGetLastError());
 			G.cigar.resize((size_t)(A.c0 + tc)); G.md.resize((size_t)(A.m0 + tm));
-			if (tc) HIP_TRY(hipMemcpyAsync(G.cigar.data() + A.c0, A.cigar, (size_t)tc * 4, hipMemcpyDeviceToHost, s));
+			if (tc) HIP_TRY(hipMemcpyAsync(G.cigar.data() + A.c0, A.cigar, (size_t)tc * sizeof *A.cigar, hipMemcpyDeviceToHost, s));
 			if (tm) HIP_TRY(hipMemcpyAsync(G.md.data() + A.m0, A.md, (size_t)tm, hipMemcpyDeviceToHost, s));
 			HIP_TRY(hipStreamSynchronize(s));
 			a = b;
@@ -256,7 +231,7 @@ int cs_regions_cigar_gpu_(cs_cigar_gpu **gp, int device, const cs_refseq_view &R
 	}
 	HIP_TRY(hipEventRecord(G.ev[1], s));
 	HIP_TRY(hipMemcpyAsync(G.alns.data(), A.alns, (size_t)n_regs * sizeof(cs_aln_t), hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(h, A.ctr, N_CTRW * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, A.ctr, N_CTRW * sizeof *A.ctr, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	deliver();
 	float ms = 0.f;

@@ -34,7 +34,8 @@ CS_HD inline uint8_t cs_base_code_(uint8_t c)
 	switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; case '-': return 5; default: return 4; }
 }
 
-// The device stage states: what they have in common (device, stream, events, pinned counters, buffers) is cs_dev_stage of dev_stage.hpp.
+// The device stage states: what they have in common (device, stream, events, pinned counters, rocPRIM's scratch) is cs_dev_stage of
+// dev_stage.hpp, whose cs_dev_stage_delete_ is the body of every cs_*_gpu_release_ below.
 // the device side of a chainer (chain_gpu.hip: cs_chain_batch_device / cs_chain_batch_gpu)
 struct cs_chainer_gpu;
 void cs_chainer_gpu_release_(cs_chainer_gpu *g);

@@ -507,24 +507,22 @@ __global__ void max_qlen_kernel(const cs_ext_pair_t *pairs, int64_t n, unsigned 
 
 } // namespace cse
 
-namespace {
-enum { B_PAIRS, B_Q, B_T, B_OUT, B_SCRATCH,              // the host forms' pairs, sequences and results; the band state of queries too long for LDS
-       B_KEYS, B_KEYS2, B_IDX, B_IDX2, B_SORT,            // lane kernel: sort keys and pair indices, both with their sorted copies, rocPRIM's scratch
-       B_CTR, B_CLS,                                      // 8 words: [0] skipped pairs [1] cells [2] rows [3] longest query, [4..7] hold the matrix; 16 words: pairs per query-length class of the lane kernel
-       B_COUNT };
-} // namespace
-
-// the stage's ev[0] / ev[1] stand around a call's kernels (kernel_ms); its h_ctr receives the first four words of B_CTR
-struct cs_extender : cs_dev_stage<B_COUNT> {
+// the stage's ev[0] / ev[1] stand around a call's kernels (kernel_ms); its h_ctr receives the first four words of ctr; its scratch is the sort's
+struct cs_extender : cs_dev_stage {
 	cse::ExtParams P{};
 	bool packed16 = true;                 // the two-columns-per-lane int16 kernel may be used (parameters fit; not switched off)
 	int min_qlen16 = 64;
 	bool lanes = true;                    // short queries go through extend_lanes_kernel (one pair per lane)
 	bool qin = false;                     // ... with the query base inside the cell (CS_EXT_LANES_QIN: experiment)
 	HipStream side[2]; HipEvent ev_fork, ev_join[2]; // the lane kernel's class launches run side by side
-	PinBuf<unsigned long long> h_cls;     // B_CLS as the host reads it
-	uint64_t res_q = 0, res_t = 0;        // bytes of the sequences resident in B_Q / B_T (the last host-form call's or cs_extender_upload's)
+	PinBuf<unsigned long long> h_cls;     // cls as the host reads it
+	uint64_t res_q = 0, res_t = 0;        // bytes of the sequences resident in q / t (the last host-form call's or cs_extender_upload's)
 	cs_ext_stats_t st{};
+	DevBuf<cs_ext_pair_t> pairs; DevBuf<uint8_t> q, t; DevBuf<cs_ext_result_t> out;   // the host forms' pairs, sequences and results
+	DevBuf<int32_t> band;                 // the band state of queries too long for LDS
+	DevBuf<uint32_t> keys, keys2, idx, idx2;   // lane kernel: sort keys and pair indices, both with their sorted copies
+	DevBuf<unsigned long long> ctr, cls;  // 8 words: [0] skipped pairs [1] cells [2] rows [3] longest query, [4..7] hold the matrix; 16 words: pairs per query-length class of the lane kernel
+	void drain() const { for (const HipStream &k : side) if (k) (void)hipStreamSynchronize(k); cs_dev_stage::drain(); }
 };
 
 extern "C" void cs_ext_params_default(cs_ext_params_t *p)
@@ -535,16 +533,15 @@ extern "C" void cs_ext_params_default(cs_ext_params_t *p)
 	p->o_del = p->o_ins = 6; p->e_del = p->e_ins = 1; p->zdrop = 100; p->end_bonus = 5; p->flags = 0;
 }
 
-// what cs_extender_create makes on the device; whatever this returns, cs_extender_destroy copes with it
-static int extender_init(cs_extender *x, int device, const int8_t *mat)
+// what cs_extender_create makes on the device, on a stage init has made; whatever this returns, cs_extender_destroy copes with it
+static int extender_setup(cs_extender *x, const int8_t *mat)
 {
-	if (int rc = x->init(device, true)) return rc;
 	for (int k = 0; k < 2; ++k) { HIP_TRY(hipStreamCreateWithFlags(&x->side[k].h, hipStreamNonBlocking)); HIP_TRY(hipEventCreateWithFlags(&x->ev_join[k].h, hipEventDisableTiming)); }
 	HIP_TRY(hipEventCreateWithFlags(&x->ev_fork.h, hipEventDisableTiming));
-	if (int rc = x->ensure(B_CTR, 8 * sizeof(unsigned long long))) return rc;
-	if (int rc = x->ensure(B_CLS, 16 * sizeof(unsigned long long))) return rc;
+	if (int rc = x->ctr.ensure(x->N_CTR)) return rc;
+	if (int rc = x->cls.ensure(16)) return rc;
 	if (int rc = x->h_cls.reserve(16)) return rc;
-	HIP_TRY(hipMemcpy(x->at<unsigned long long>(B_CTR) + 4, mat, 25, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(x->ctr.p + 4, mat, 25, hipMemcpyHostToDevice));
 	return CS_OK;
 }
 
@@ -572,19 +569,14 @@ extern "C" int cs_extender_create(int device, const cs_ext_params_t *par, cs_ext
 	              par->mat[0] >= 0 && par->mat[0] <= 100 && par->mat[1] <= 0 && par->mat[1] >= -100;
 	x->lanes = !x->packed16 && !(par->flags & CS_EXT_NO_LANES);
 	x->qin = (par->flags & CS_EXT_LANES_QIN) != 0;
-	if (int rc = extender_init(x, device, par->mat)) { cs_extender_destroy(x); return rc; }
+	int rc = x->init(device, true);
+	if (rc == CS_OK) rc = extender_setup(x, par->mat);
+	if (rc != CS_OK) { cs_extender_destroy(x); return rc; }
 	*out = x;
 	return CS_OK;
 }
 
-extern "C" void cs_extender_destroy(cs_extender_t *x)
-{
-	if (!x) return;
-	(void)hipSetDevice(x->device);
-	for (const HipStream &t : x->side) if (t) (void)hipStreamSynchronize(t);
-	x->release();
-	delete x;
-}
+extern "C" void cs_extender_destroy(cs_extender_t *x) { cs_dev_stage_delete_(x); }
 
 // The kernels of a call, from the first timing event to the wait for the main stream.  The lane kernel's class launches fork onto the two
 // side streams and join the main stream again; a failure in here may return with kernels running on any of the three (extend_device waits).
@@ -592,18 +584,18 @@ static int extend_launches(cs_extender *x, cse::ExtArgs &A, size_t sort_bytes)
 {
 	hipStream_t s = x->s;
 	const int64_t n = A.n;
-	unsigned long long *d_ctr = x->at<unsigned long long>(B_CTR), *d_cls = x->at<unsigned long long>(B_CLS), *h_cls = x->h_cls.p;
+	unsigned long long *d_ctr = x->ctr.p, *d_cls = x->cls.p, *h_cls = x->h_cls.p;
 	const size_t per_wave = ((size_t)2 * (A.max_qlen + 2) + ((A.max_qlen + 3) >> 2)) * 4; // bytes of LDS per wave
 	HIP_TRY(hipEventRecord(x->ev[0], s));
 	A.packed16 = 0; A.min_qlen16 = x->min_qlen16;
 	int64_t n_lanes = 0;
 	if (x->lanes && n < (1ll << 32)) { // short queries: one pair per lane, pairs sorted by (query-length class, target length, query length)
-		uint32_t *keys = x->at<uint32_t>(B_KEYS), *keys2 = x->at<uint32_t>(B_KEYS2), *idx = x->at<uint32_t>(B_IDX), *idx2 = x->at<uint32_t>(B_IDX2);
+		uint32_t *keys = x->keys.p, *keys2 = x->keys2.p, *idx = x->idx.p, *idx2 = x->idx2.p;
 		HIP_TRY(hipMemsetAsync(d_cls, 0, 16 * sizeof(unsigned long long), s));
 		hipLaunchKernelGGL(cse::lanes_keys_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)x->n_cu * 8)), dim3(256), 0, s, A, keys, idx, d_cls);
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(h_cls, d_cls, 2 * cse::LANES_NCLASS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-		HIP_TRY(rocprim::radix_sort_pairs(x->b[B_SORT].p, sort_bytes, keys, keys2, idx, idx2, (size_t)n, 0u, 32u, s));
+		HIP_TRY(rocprim::radix_sort_pairs(x->scratch.p, sort_bytes, keys, keys2, idx, idx2, (size_t)n, 0u, 32u, s));
 		HIP_TRY(hipStreamSynchronize(s));
 		int64_t first = 0;
 		// one launch per class (its LDS size), the largest first, spread over three streams: the tail of one class is filled by the next
@@ -648,13 +640,13 @@ static int extend_launches(cs_extender *x, cse::ExtArgs &A, size_t sort_bytes)
 			hipLaunchKernelGGL(cse::extend_kernel<true>, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(64 * wpb), per_wave * wpb, s, A);
 		} else { // long queries: the band state in HBM
 			const int64_t blocks = std::min<int64_t>((n + 3) / 4, (int64_t)x->n_cu * 4);
-			A.scratch = x->at<int32_t>(B_SCRATCH);
+			A.scratch = x->band.p;
 			hipLaunchKernelGGL(cse::extend_kernel<false>, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0, s, A);
 		}
 		HIP_TRY(hipGetLastError());
 	}
 	HIP_TRY(hipEventRecord(x->ev[1], s));
-	HIP_TRY(hipMemcpyAsync(x->h_ctr, d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(x->h_ctr.p, d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	return CS_OK;
 }
@@ -666,19 +658,19 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
                          int32_t w, cs_ext_result_t *d_out)
 {
 	hipStream_t s = x->s;
-	unsigned long long *d_ctr = x->at<unsigned long long>(B_CTR);
+	unsigned long long *d_ctr = x->ctr.p; const unsigned long long *h = x->h_ctr.p;
 	size_t sort_bytes = 0;
 	if (x->lanes && n < (1ll << 32)) {
-		for (int which : {B_KEYS, B_KEYS2, B_IDX, B_IDX2}) if (int rc = x->ensure(which, (size_t)n * 4)) return rc;
-		HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, x->at<uint32_t>(B_KEYS), x->at<uint32_t>(B_KEYS2), x->at<uint32_t>(B_IDX), x->at<uint32_t>(B_IDX2), (size_t)n, 0u, 32u, s));
-		if (int rc = x->ensure(B_SORT, sort_bytes + 16)) return rc;
+		if (int rc = cs_ensure_each_((size_t)n, 0, x->keys, x->keys2, x->idx, x->idx2)) return rc;
+		HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, x->keys.p, x->keys2.p, x->idx.p, x->idx2.p, (size_t)n, 0u, 32u, s));
+		if (int rc = x->scratch.ensure(sort_bytes, 16)) return rc;
 	}
 	HIP_TRY(hipMemsetAsync(d_ctr, 0, 4 * sizeof(unsigned long long), s));
 	hipLaunchKernelGGL(cse::max_qlen_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)x->n_cu * 8)), dim3(256), 0, s, d_pairs, n, d_ctr + 3);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(x->h_ctr, d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(x->h_ctr.p, d_ctr, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	const int64_t max_q = (int64_t)x->h_ctr[3];
+	const int64_t max_q = (int64_t)h[3];
 	if (max_q > 65535) return cs_fail_(CS_ERANGE, "cs_extend_batch: a query is longer than 65535 bases (MAX_READ_LEN, mapping/comp_seed.h:39)");
 	if ((int64_t)x->P.best * max_q > (1 << 29)) return cs_fail_(CS_ERANGE, "cs_extend_batch: scores would not fit the kernel's 30-bit range");
 	cse::ExtArgs A;
@@ -686,17 +678,17 @@ static int extend_device(cs_extender *x, int64_t n, const cs_ext_pair_t *d_pairs
 	A.P = x->P; A.mat = (const int8_t *)(d_ctr + 4); A.scratch = nullptr; A.err = d_ctr; A.stat = d_ctr + 1;
 	if (((size_t)2 * (A.max_qlen + 2) + ((A.max_qlen + 3) >> 2)) * 4 > 60 * 1024) { // too long for LDS: extend_kernel<false>'s band state, per wave of its grid
 		const int64_t blocks = std::min<int64_t>((n + 3) / 4, (int64_t)x->n_cu * 4);
-		if (int rc = x->ensure(B_SCRATCH, (size_t)std::max<int64_t>(blocks, 1) * 4 * 2 * (A.max_qlen + 2) * sizeof(int32_t))) return rc;
+		if (int rc = x->band.ensure((size_t)std::max<int64_t>(blocks, 1) * 4 * 2 * (A.max_qlen + 2))) return rc;
 	}
-	if (int rc = extend_launches(x, A, sort_bytes)) { // nothing of a failed call stays in flight: the next call clears B_CTR and may free what these kernels use
+	if (int rc = extend_launches(x, A, sort_bytes)) { // nothing of a failed call stays in flight: the next call clears ctr and may free what these kernels use
 		for (int k = 0; k < 2; ++k) (void)hipStreamSynchronize(x->side[k]);
 		(void)hipStreamSynchronize(s);
 		return rc;
 	}
 	float ms = 0.f;
 	HIP_TRY(hipEventElapsedTime(&ms, x->ev[0], x->ev[1]));
-	x->st.pairs += (uint64_t)n; x->st.cells += x->h_ctr[1]; x->st.rows += x->h_ctr[2]; x->st.kernel_ms += ms; x->st.launches++;
-	if (x->h_ctr[0]) return cs_fail_(CS_EINVAL, "cs_extend_batch: " + std::to_string(x->h_ctr[0]) + " pair(s) with qlen < 1, tlen < 0 or offsets outside the sequence buffers (their results are zero)");
+	x->st.pairs += (uint64_t)n; x->st.cells += h[1]; x->st.rows += h[2]; x->st.kernel_ms += ms; x->st.launches++;
+	if (h[0]) return cs_fail_(CS_EINVAL, "cs_extend_batch: " + std::to_string(h[0]) + " pair(s) with qlen < 1, tlen < 0 or offsets outside the sequence buffers (their results are zero)");
 	return CS_OK;
 }
 
@@ -715,8 +707,8 @@ extern "C" int cs_extend_batch_device(cs_extender_t *x, int64_t n_pairs, const c
 static int seqs_up(cs_extender *x, const uint8_t *qbuf, uint64_t q_bytes, const uint8_t *tbuf, uint64_t t_bytes)
 {
 	x->res_q = x->res_t = 0;              // (a growth that fails leaves its buffer empty)
-	int rc = x->up(B_Q, qbuf, (size_t)q_bytes);
-	if (!rc) rc = x->up(B_T, tbuf, (size_t)t_bytes);
+	int rc = x->up(x->q, qbuf, (size_t)q_bytes);
+	if (!rc) rc = x->up(x->t, tbuf, (size_t)t_bytes);
 	if (rc) { (void)hipStreamSynchronize(x->s); return rc; }   // (the first copy may be on its way)
 	x->res_q = q_bytes; x->res_t = t_bytes;
 	return CS_OK;
@@ -724,13 +716,13 @@ static int seqs_up(cs_extender *x, const uint8_t *qbuf, uint64_t q_bytes, const 
 // pairs up, the kernels over the resident sequences, results down; what the kernels reported is raised again behind the download
 static int extend_resident(cs_extender *x, int64_t n_pairs, const cs_ext_pair_t *pairs, int32_t w, cs_ext_result_t *out)
 {
-	int rc = x->ensure(B_OUT, (size_t)n_pairs * sizeof(cs_ext_result_t));
-	if (!rc) rc = x->up(B_PAIRS, pairs, (size_t)n_pairs * sizeof(cs_ext_pair_t));
+	int rc = x->out.ensure((size_t)n_pairs);
+	if (!rc) rc = x->up(x->pairs, pairs, (size_t)n_pairs);
 	if (rc) { (void)hipStreamSynchronize(x->s); return rc; }   // (cs_extend_batch's sequences may be on their way)
-	rc = extend_device(x, n_pairs, x->at<cs_ext_pair_t>(B_PAIRS), x->at<uint8_t>(B_Q), x->res_q, x->at<uint8_t>(B_T), x->res_t, w, x->at<cs_ext_result_t>(B_OUT));
+	rc = extend_device(x, n_pairs, x->pairs.p, x->q.p, x->res_q, x->t.p, x->res_t, w, x->out.p);
 	const std::string keep = rc != CS_OK ? std::string(cs_last_error()) : std::string();
 	if (rc == CS_OK || rc == CS_EINVAL) { // (CS_EINVAL from skipped pairs: the other results are valid and are delivered)
-		hipError_t e = hipMemcpyAsync(out, x->b[B_OUT].p, (size_t)n_pairs * sizeof(cs_ext_result_t), hipMemcpyDeviceToHost, x->s);
+		hipError_t e = hipMemcpyAsync(out, x->out.p, (size_t)n_pairs * sizeof(cs_ext_result_t), hipMemcpyDeviceToHost, x->s);
 		if (e == hipSuccess) e = hipStreamSynchronize(x->s);
 		if (e != hipSuccess) { (void)hipGetLastError(); return cs_fail_(CS_EDEVICE, hipGetErrorString(e)); }
 	}

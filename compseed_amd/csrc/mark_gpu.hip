@@ -94,53 +94,34 @@ __global__ void cigar_kernel(Args A)
 }
 } // namespace csmk
 
-namespace {
-enum { B_ALT, B_LOG, B_REG_OFF, B_READ_OFF, B_REGS, B_CTR, B_MARKS, B_RANKED, B_NEED, B_NSLOT, B_NL, B_LINE_OFF, B_FLAG, B_SLOT, B_HEAVY, B_HBM, B_SCAN, B_CIG_OFF, B_CIG_SRC, B_CIG_REGS, B_COUNT };
-} // namespace
-
-struct cs_mark_gpu : cs_dev_stage<B_COUNT> {
+struct cs_mark_gpu : cs_dev_stage {
 	cs_mark_stats_t st = {};
 	std::vector<cs_mark_t> marks; std::vector<uint64_t> line_off, cig_off; std::vector<cs_alnreg_t> cig_regs; std::vector<uint32_t> cig_src;   // the result
+	DevBuf<uint8_t> alt; DevBuf<double> logtab;                                              // the ALT flags and the host's logarithms: once
+	DevBuf<uint64_t> reg_off, read_off; DevBuf<cs_alnreg_t> regs; DevBuf<unsigned long long> ctr;   // the call's input, the counters
+	DevBuf<cs_mark_t> d_marks; DevBuf<cs_alnreg_t> ranked, d_cig_regs; DevBuf<uint32_t> need, nslot, d_cig_src; DevBuf<int32_t> hbm;   // per region
+	DevBuf<uint64_t> nl, d_line_off, d_cig_off; DevBuf<uint32_t> flag, slot, heavy;          // per read
 };
 static_assert(csmk::C_COUNT <= cs_mark_gpu::N_CTR, "the stage's pinned counter block holds the pass's counters");
 static_assert(sizeof(cs_mark_t) == 48, "cs_mark_t is twelve 4-byte words");
 
-void cs_mark_gpu_release_(cs_mark_gpu *g)
-{
-	if (!g) return;
-	g->release();
-	delete g;
-}
-int cs_mark_gpu_stats_(const cs_mark_gpu *g, cs_mark_stats_t *st)
-{
-	if (g) *st = g->st; else memset(st, 0, sizeof *st);
-	return CS_OK;
-}
-
-namespace {
-int mark_init(cs_mark_gpu **gp, int device, const cs_refseq_view &R)
-{
-	if (*gp) return CS_OK;
-	cs_mark_gpu *g = new cs_mark_gpu();
-	*gp = g;                                                          // (released with the aligner, whatever fails below)
-	if (int rc = g->init(device, true)) return rc;
-	std::vector<double> logtab((size_t)csmk::LOG_N);                  // the host's logarithms: what the reference's libm calls return
-	for (int k = 0; k < csmk::LOG_N; ++k) logtab[(size_t)k] = std::log((double)k);
-	if (int rc = g->ensure(B_ALT, R.is_alt.size() + 64)) return rc;
-	if (int rc = g->ensure(B_LOG, logtab.size() * 8)) return rc;
-	HIP_TRY(hipMemcpy(g->b[B_ALT].p, R.is_alt.data(), R.is_alt.size(), hipMemcpyHostToDevice));
-	HIP_TRY(hipMemcpy(g->b[B_LOG].p, logtab.data(), logtab.size() * 8, hipMemcpyHostToDevice));
-	return CS_OK;
-}
-} // namespace
+void cs_mark_gpu_release_(cs_mark_gpu *g) { cs_dev_stage_delete_(g); }
+int cs_mark_gpu_stats_(const cs_mark_gpu *g, cs_mark_stats_t *st) { return cs_dev_stage_stats_(g, st); }
 
 int cs_regions_mark_gpu_(cs_mark_gpu **gp, int device, const cs_refseq_view &R, const cs_aln_params_t &o, const cs_mark_params_t &par, const cs_aln_result_t *regs,
                          const uint64_t *read_offsets, int64_t id_base, uint32_t flags, cs_mark_result_t *out)
 {
 	using namespace csmk;
-	if (int rc = mark_init(gp, device, R)) return rc;
+	if (int rc = cs_dev_stage_make_(gp, device, true, [&](cs_mark_gpu &g) {
+		std::vector<double> logs((size_t)LOG_N);                          // the host's logarithms: what the reference's libm calls return
+		for (int k = 0; k < LOG_N; ++k) logs[(size_t)k] = std::log((double)k);
+		if (int rc = g.alt.ensure(R.is_alt.size(), 64)) return rc;
+		if (int rc = g.logtab.ensure(logs.size())) return rc;
+		HIP_TRY(hipMemcpy(g.alt.p, R.is_alt.data(), R.is_alt.size(), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(g.logtab.p, logs.data(), logs.size() * sizeof(double), hipMemcpyHostToDevice));
+		return CS_OK;
+	})) return rc;
 	cs_mark_gpu &G = **gp;
-	if (!G.h_ctr) return cs_fail_(CS_EDEVICE, "cs_regions_mark: the device state was not created");
 	HIP_TRY(hipSetDevice(G.device));
 	hipStream_t s = G.s;
 	const int64_t n = regs->n_reads;
@@ -153,42 +134,39 @@ int cs_regions_mark_gpu_(cs_mark_gpu **gp, int device, const cs_refseq_view &R, 
 	};
 	deliver();
 	if (n == 0 || n_regs == 0) {
-		if (n == 0 && n_regs) return cs_fail_(CS_EINVAL, "cs_regions_mark: regions without reads");
-		if (n && (regs->reg_off[0] != 0 || read_offsets[0] != 0)) return cs_fail_(CS_EINVAL, "cs_regions_mark: the offsets do not start at 0");
-		for (int64_t r = 0; r < n; ++r) if (regs->reg_off[r + 1] != 0 || read_offsets[r + 1] < read_offsets[r]) return cs_fail_(CS_EINVAL, "cs_regions_mark: reg_off / read_offsets are not CSR offset arrays");
+		if (int rc = cs_check_no_regions_("cs_regions_mark", regs, read_offsets)) return rc;
 		G.st.reads += (uint64_t)n;
 		return CS_OK;
 	}
 	const size_t per_reg = (size_t)n_regs + 1, per_read = (size_t)n + 1;
-	struct { int which; size_t bytes; } need[] = {
-		{B_CTR, cs_mark_gpu::N_CTR * 8}, {B_MARKS, per_reg * sizeof(cs_mark_t)}, {B_RANKED, per_reg * sizeof(cs_alnreg_t)}, {B_NEED, per_reg * 4}, {B_NSLOT, per_reg * 4}, {B_NL, per_read * 8},
-		{B_LINE_OFF, per_read * 8}, {B_FLAG, per_read * 4}, {B_SLOT, per_read * 4}, {B_HEAVY, per_read * 4}, {B_CIG_OFF, per_read * 8}, {B_CIG_SRC, per_reg * 4}, {B_CIG_REGS, per_reg * sizeof(cs_alnreg_t)}};
-	for (auto &q : need) if (int rc = G.ensure(q.which, q.bytes)) return rc;
-	if (int rc = G.up(B_REG_OFF, regs->reg_off, per_read * 8)) return rc;
-	if (int rc = G.up(B_READ_OFF, read_offsets, per_read * 8)) return rc;
-	if (int rc = G.up(B_REGS, regs->regs, (size_t)n_regs * sizeof(cs_alnreg_t))) return rc;
+	if (int rc = G.ctr.ensure(cs_mark_gpu::N_CTR)) return rc;
+	if (int rc = cs_ensure_each_(per_reg, 0, G.d_marks, G.ranked, G.need, G.nslot, G.d_cig_src, G.d_cig_regs)) return rc;
+	if (int rc = cs_ensure_each_(per_read, 0, G.nl, G.d_line_off, G.flag, G.slot, G.heavy, G.d_cig_off)) return rc;
+	if (int rc = G.up(G.reg_off, regs->reg_off, per_read)) return rc;
+	if (int rc = G.up(G.read_off, read_offsets, per_read)) return rc;
+	if (int rc = G.up(G.regs, regs->regs, (size_t)n_regs)) return rc;
 	Args A = {};
-	A.D = {G.at<uint64_t>(B_REG_OFF), G.at<uint64_t>(B_READ_OFF), G.at<cs_alnreg_t>(B_REGS), n, n_regs};
-	A.R = {R.l_pac, G.at<uint8_t>(B_ALT), (int)R.offset.size(), G.at<double>(B_LOG)};
+	A.D = {G.reg_off.p, G.read_off.p, G.regs.p, n, n_regs};
+	A.R = {R.l_pac, G.alt.p, (int)R.offset.size(), G.logtab.p};
 	A.P = {par, o.a, o.b, o.o_del, o.e_del, o.o_ins, o.e_ins, flags, id_base};
-	A.ctr = G.at<unsigned long long>(B_CTR);
-	A.marks = G.at<cs_mark_t>(B_MARKS); A.ranked = G.at<cs_alnreg_t>(B_RANKED); A.need = G.at<uint32_t>(B_NEED); A.nslot = G.at<uint32_t>(B_NSLOT);
-	A.nl = G.at<uint64_t>(B_NL); A.line_off = G.at<uint64_t>(B_LINE_OFF); A.flag = G.at<uint32_t>(B_FLAG); A.slot = G.at<uint32_t>(B_SLOT); A.heavy = G.at<uint32_t>(B_HEAVY);
-	A.cig_off = G.at<uint64_t>(B_CIG_OFF); A.cig_src = G.at<uint32_t>(B_CIG_SRC);
-	unsigned long long *h = G.h_ctr;
+	A.ctr = G.ctr.p;
+	A.marks = G.d_marks.p; A.ranked = G.ranked.p; A.need = G.need.p; A.nslot = G.nslot.p;
+	A.nl = G.nl.p; A.line_off = G.d_line_off.p; A.flag = G.flag.p; A.slot = G.slot.p; A.heavy = G.heavy.p;
+	A.cig_off = G.d_cig_off.p; A.cig_src = G.d_cig_src.p;
+	unsigned long long *h = G.h_ctr.p;
 	uint64_t launches = 0;
-	HIP_TRY(hipMemsetAsync(A.ctr, 0, cs_mark_gpu::N_CTR * 8, s));
+	HIP_TRY(hipMemsetAsync(A.ctr, 0, cs_mark_gpu::N_CTR * sizeof *A.ctr, s));
 	HIP_TRY(hipEventRecord(G.ev[0], s));
 	hipLaunchKernelGGL(check_kernel, G.grid(n, 256), dim3(256), 0, s, A); ++launches;
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(h, A.ctr, cs_mark_gpu::N_CTR * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, A.ctr, cs_mark_gpu::N_CTR * sizeof *A.ctr, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));                                  // the verdict, before any kernel follows an offset
 	if (h[C_BAD]) return cs_fail_(CS_EINVAL, "cs_regions_mark: reg_off / read_offsets are not CSR offset arrays from 0, or a region is purged, unmapped, outside its read or the reference, names no contig or scores below 0");
 	if (h[C_RANGE]) return cs_fail_(CS_ERANGE, "cs_regions_mark: a read has 65,536 regions or more, or a region spans more than 131,072 bases");
 	hipLaunchKernelGGL(classify_kernel, G.grid(n + 1, 256), dim3(256), 0, s, A); ++launches;
 	HIP_TRY(hipGetLastError());
-	if (int rc = G.scan<uint32_t>(B_SCAN, A.flag, A.slot, per_read, 0u)) return rc;
-	HIP_TRY(hipMemcpyAsync(h, A.ctr, cs_mark_gpu::N_CTR * 8, hipMemcpyDeviceToHost, s));
+	if (int rc = G.scan<uint32_t>(A.flag, A.slot, per_read, 0u)) return rc;
+	HIP_TRY(hipMemcpyAsync(h, A.ctr, cs_mark_gpu::N_CTR * sizeof *A.ctr, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	const uint64_t n_light = h[C_LIGHT], n_heavy = h[C_WAVE], n_hbm = h[C_HBM];
 	if (n_light) {
@@ -196,30 +174,30 @@ int cs_regions_mark_gpu_(cs_mark_gpu **gp, int device, const cs_refseq_view &R, 
 		HIP_TRY(hipGetLastError());
 	}
 	if (n_heavy) {
-		if (n_hbm) { if (int rc = G.ensure(B_HBM, (size_t)WORK_LISTS * (size_t)n_regs * 4 + 64)) return rc; }
-		A.hbm = G.at<int32_t>(B_HBM); A.n_heavy = n_heavy;
+		if (n_hbm) { if (int rc = G.hbm.ensure((size_t)WORK_LISTS * (size_t)n_regs, 64)) return rc; }
+		A.hbm = G.hbm.p; A.n_heavy = n_heavy;
 		hipLaunchKernelGGL(list_kernel, G.grid(n, 256), dim3(256), 0, s, A);
 		hipLaunchKernelGGL(wave_kernel, dim3((unsigned)std::min<uint64_t>(n_heavy, (uint64_t)G.n_cu * 8)), dim3(64), 0, s, A); launches += 2;
 		HIP_TRY(hipGetLastError());
 	}
-	if (int rc = G.scan<uint64_t>(B_SCAN, A.nl, A.line_off, per_read, 0ull)) return rc;
-	if (int rc = G.scan<uint32_t>(B_SCAN, A.need, A.nslot, per_reg, 0u)) return rc;
-	hipLaunchKernelGGL(csa::scatter_kernel, G.grid((int64_t)n_regs * csa::REG_WORDS, 256), dim3(256), 0, s, (const uint64_t *)A.ranked, n_regs, A.need, A.nslot, G.at<uint64_t>(B_CIG_REGS));
+	if (int rc = G.scan<uint64_t>(A.nl, A.line_off, per_read, 0ull)) return rc;
+	if (int rc = G.scan<uint32_t>(A.need, A.nslot, per_reg, 0u)) return rc;
+	hipLaunchKernelGGL(csa::scatter_kernel, G.grid((int64_t)n_regs * csa::REG_WORDS, 256), dim3(256), 0, s, (const uint64_t *)A.ranked, n_regs, A.need, A.nslot, (uint64_t *)G.d_cig_regs.p);
 	hipLaunchKernelGGL(cigar_kernel, G.grid((int64_t)n_regs + n + 1, 256), dim3(256), 0, s, A); launches += 2;
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(G.ev[1], s));
-	HIP_TRY(hipMemcpyAsync(h, A.nslot + n_regs, 4, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(h + 1, A.ctr + C_XA, 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h, A.nslot + n_regs, sizeof *A.nslot, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h + 1, A.ctr + C_XA, sizeof *h, hipMemcpyDeviceToHost, s));
 	G.marks.resize((size_t)n_regs);
 	HIP_TRY(hipMemcpyAsync(G.marks.data(), A.marks, (size_t)n_regs * sizeof(cs_mark_t), hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(G.line_off.data(), A.line_off, per_read * 8, hipMemcpyDeviceToHost, s));
-	HIP_TRY(hipMemcpyAsync(G.cig_off.data(), A.cig_off, per_read * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.line_off.data(), A.line_off, per_read * sizeof *A.line_off, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(G.cig_off.data(), A.cig_off, per_read * sizeof *A.cig_off, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
 	const uint64_t n_cig = *(const uint32_t *)h, n_xa = h[1];
 	G.cig_regs.resize((size_t)n_cig); G.cig_src.resize((size_t)n_cig);
 	if (n_cig) {
-		HIP_TRY(hipMemcpyAsync(G.cig_regs.data(), G.at<cs_alnreg_t>(B_CIG_REGS), (size_t)n_cig * sizeof(cs_alnreg_t), hipMemcpyDeviceToHost, s));
-		HIP_TRY(hipMemcpyAsync(G.cig_src.data(), A.cig_src, (size_t)n_cig * 4, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(G.cig_regs.data(), G.d_cig_regs.p, (size_t)n_cig * sizeof(cs_alnreg_t), hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipMemcpyAsync(G.cig_src.data(), A.cig_src, (size_t)n_cig * sizeof *A.cig_src, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipStreamSynchronize(s));
 	}
 	deliver();

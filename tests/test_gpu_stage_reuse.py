@@ -1,16 +1,21 @@
 """One Chainer and one Aligner through a sequence of batches that no single stage test states: the largest golden run (the buffers
-grow), an empty batch, the smallest run, a call the checking kernels refuse with CS_EINVAL, the first run again.  The three device stages
-(chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip) keep their state -- stream, events, pinned counters, grow-only buffers -- in one shared
-layer (compseed_amd/csrc/dev_stage.hpp); after every step each stage's result must be, byte for byte, what freshly created handles return
-for the same input and what the host calls cs_chain_batch / cs_chain_filter return, for the host-array forms and for the *_device forms
-chained on the device.  Then the handles close, and so does a chainer whose filter state was never made.  The fourth stage on that layer,
-the Extender (extend.hip), goes through a sequence of its own: its three host forms and the device form on one handle."""
+grow), an empty batch, the smallest run, a call the checking kernels refuse with CS_EINVAL, the first run again.  The device stages keep
+their state in one shared layer (compseed_amd/csrc/dev_stage.hpp): a stream, timing events and pinned counter words that are destroyed
+with the stage, and typed grow-only device buffers (DevBuf<T> members, grown by DevBuf::ensure, which frees before it allocates and keeps
+no contents).  After every step each stage's result must be, byte for byte, what freshly created handles return for the same input.  The
+chainer, the filter and the aligner's extension (chain_gpu.hip, chain_filter_gpu.hip, align_gpu.hip) are also held against the host calls
+cs_chain_batch / cs_chain_filter, for the host-array forms and for the *_device forms chained on the device; then the handles close, and so
+does a chainer whose filter state was never made.  The Extender (extend.hip) goes through a sequence of its own: its three host forms and
+the device form on one handle.  The aligner's two later stages, cs_regions_mark (mark_gpu.hip) and cs_regions_cigar (cigar_gpu.hip), have a
+leg each over the sets their own tests run, with the difference of the stage's statistics across every step compared as well."""
 import functools
 
 import numpy as np
 import pytest
 
+import _cigar
 import _data
+import _mark
 import _oracle
 from test_chain import golden_chains
 from test_gpu_chain_device import _cp, _golden_in
@@ -143,6 +148,10 @@ def test_the_runs_differ_in_size():
     assert BIG == max(_data.golden_runs(), key=lambda run: golden_chains(*run)["pos"].size)
     assert big[0][3].size > 2 * small[0][3].size and golden_chains(*BIG)["pos"].size > 2 * golden_chains(*SMALL)["pos"].size > 0
     assert big[2].size < small[2].size
+    # ... and the later stages' sets: (reads, regions, most regions a read, longest read)
+    shape = lambda x: (x[0].size - 1, x[1].size, int(np.diff(x[0].astype(np.int64)).max()), int(np.diff(x[3].astype(np.int64)).max()))
+    assert shape(_regions("repeat100"))[:3] == (120, 30006, 501) and shape(_regions("main100"))[:2] == (3000, 4561)
+    assert shape(_regions("gap3k"))[:2] == (120, 222) and shape(_regions("gap3k"))[3] == 3712 > 1024 > shape(_regions("main100"))[3]
 
 
 def test_host_array_forms_on_reused_handles(fresh):
@@ -295,3 +304,63 @@ def test_the_extender_on_a_reused_handle(eng):
     assert not x.h
     never_used = ca.Extender(0)
     never_used.close()
+
+
+# ---- the aligner's later stages: cs_regions_mark and cs_regions_cigar on one Aligner each, default parameters throughout
+MARK_STEPS = ["repeat100", None, "main100", "refused", "repeat100"]   # per-region buffers and the wave path grow; then the per-read ones alone (3,000 reads of 4,561 regions)
+CIGAR_STEPS = ["main100", None, "gap3k", "refused", "main100"]        # gap3k: few regions, but H / E rows beyond the LDS rows and the largest backtrack scratch
+
+
+def _regions(name):
+    """reg_off, regs, bases, read offsets of a set, or of the batch without reads"""
+    if name is None:
+        reg_off, regs, bases, off, _ = _cigar.load("main100")
+        return reg_off[:1], regs[:0], bases[:0], off[:1]
+    return _cigar.load(name)[:4]
+
+
+def _reg_off_decreasing(reg_off):
+    """a copy with one entry below its predecessor (the next read takes the regions: nothing reaches beyond n_regs)"""
+    bad = reg_off.copy()
+    r = int(np.nonzero(bad[:-2] > 0)[0][0])
+    bad[r + 1] = bad[r] - np.uint64(1)
+    return bad
+
+
+def _stats_step(before, after):
+    return {k: after[k] - before[k] for k in after if k != "kernel_ms"}   # (kernel_ms is a time)
+
+
+def _later_stage_leg(steps, call, stats, same):
+    """`steps` on one Aligner; after each the result and the step's share of the statistics are a fresh Aligner's"""
+    import compseed_amd as ca
+    al = ca.Aligner(_data.PREFIX, 0)
+    try:
+        for i, name in enumerate(steps):
+            if name == "refused":
+                reg_off, regs, bases, off = _regions(steps[0])
+                _refused(lambda: call(al, _reg_off_decreasing(reg_off), regs, bases, off), "reg_off decreasing")
+                continue
+            before = stats(al)
+            got = call(al, *_regions(name))
+            fresh = ca.Aligner(_data.PREFIX, 0)
+            try:
+                want = call(fresh, *_regions(name))
+                zero = dict.fromkeys(before, 0)                                   # (a stage that has not run reports zeroes)
+                assert _stats_step(before, stats(al)) == _stats_step(zero, stats(fresh)), (i, name)
+            finally:
+                fresh.close()
+            same(got, want, (i, name))
+    finally:
+        al.close()
+
+
+def test_regions_mark_on_a_reused_aligner():
+    _later_stage_leg(MARK_STEPS, lambda al, reg_off, regs, bases, off: al.regions_mark(reg_off, regs, off), lambda al: al.mark_stats(), _mark.same_bytes)
+
+
+def test_regions_cigar_on_a_reused_aligner():
+    def same(got, want, what):
+        for k in ("alns", "cigar", "md"):
+            assert got[k].dtype == want[k].dtype and got[k].tobytes() == want[k].tobytes(), (what, k)
+    _later_stage_leg(CIGAR_STEPS, lambda al, reg_off, regs, bases, off: al.regions_cigar(reg_off, regs, bases, off), lambda al: al.cigar_stats(), same)
