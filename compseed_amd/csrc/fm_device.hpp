@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "occ_math.hpp"
 
 namespace csd {
 
@@ -319,6 +320,37 @@ __device__ __forceinline__ Intv extend1(const DevIndex &ix, const Intv &ik, int 
 	uint64_t yb = xb + ((xa <= ix.primary && xa + ik.x2 - 1 >= ix.primary) ? 1 : 0) + above;
 	Intv o;
 	o.x0 = IS_BACK ? ya : yb; o.x1 = IS_BACK ? yb : ya; o.x2 = (uint64_t)sc;
+	return o;
+}
+
+// extend1<true> for the backward kernels of smem_bwd.hpp, which are bound by VALU issue, not by memory: the same child, assembled by
+// occ_math.hpp (csocc::child1 -- one shift per mask, no A counts, the primary flag from the two row adjustments), with L2[c] + 1 read
+// from a four-entry table in LDS (l2p1, filled once per workgroup: bwd_l2_table, smem_bwd.hpp) instead of a 64-bit select among
+// wave-uniform values, which the compiler turns into divergent branches.  The forward kernels keep extend1.
+// The second record is still requested only where the rows straddle: always requesting it (no selects, a second pair of loads per
+// lane) was measured and is slower.
+template <class WC>
+__device__ __forceinline__ Intv extend1b(const DevIndex &ix, const uint64_t *l2p1, const Intv &ik, int c, WC &W)
+{
+	const uint64_t k = ik.x0 - 1, l = k + ik.x2;
+	uint32_t gek, gel;
+	const uint64_t rk = csocc::row_of(k, ix.primary, gek), rl = csocc::row_of(l, ix.primary, gel);
+	const uint64_t l2c1 = l2p1[c];
+	const bool two = (rk >> OCC_SHIFT) != (rl >> OCC_SHIFT);
+	W.rec(two);
+	W.hist(ik.x2);
+	const Block bk = load_block(ix, rk >> OCC_SHIFT);
+	Block b2;
+	if (two) b2 = load_block(ix, rl >> OCC_SHIFT);
+	uint32_t two_sel = two ? 1u : 0u; // (as in extend1: the select must not be folded into the branch)
+	asm volatile("" : "+v"(two_sel));
+	Block bl;
+	bl.cnt = two_sel ? b2.cnt : bk.cnt; bl.pl = two_sel ? b2.pl : bk.pl;
+	const uint32_t ck[4] = {bk.cnt.x, bk.cnt.y, bk.cnt.z, bk.cnt.w}, cl[4] = {bl.cnt.x, bl.cnt.y, bl.cnt.z, bl.cnt.w};
+	const csocc::Child y = csocc::child1(ck, bk.pl.x, bk.pl.y, bk.pl.z, bk.pl.w, cl, bl.pl.x, bl.pl.y, bl.pl.z, bl.pl.w,
+	                                     (uint32_t)rk, (uint32_t)rl, gek, gel, (uint32_t)c, l2c1, ik.x1);
+	Intv o;
+	o.x0 = y.ya; o.x1 = y.yb; o.x2 = y.y2;
 	return o;
 }
 

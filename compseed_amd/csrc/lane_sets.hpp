@@ -17,7 +17,7 @@
 namespace csls {
 
 CS_HD inline uint64_t below(uint32_t lane) { return (1ull << lane) - 1ull; }                       // the lanes under `lane`
-CS_HD inline uint64_t above(uint32_t lane) { return lane == 63 ? 0ull : ~((2ull << lane) - 1ull); } // the lanes over it (2 << 63 is 0, not 2^64)
+CS_HD inline uint64_t above(uint32_t lane) { return ~1ull << lane; }                               // the lanes over it (one shift; none over lane 63)
 CS_HD inline uint32_t count(uint64_t set) { return (uint32_t)__builtin_popcountll(set); }
 CS_HD inline bool has(uint64_t set, uint32_t lane) { return ((set >> lane) & 1ull) != 0; }
 

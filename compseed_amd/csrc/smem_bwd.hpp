@@ -6,9 +6,30 @@
 
 namespace csd {
 
+// bwd_win_kernel, bwd_wide_kernel and bwd_all_kernel extend through extend1b (fm_device.hpp, occ_math.hpp), which wants L2[c] + 1 in LDS:
+// each fills a four-entry table once per workgroup.  CS_OCC_LEAN = 0 builds them on extend1<true> as before (the table is then unused).
+// bwd_win0_kernel stays on extend1<true>: with extend1b it was no faster and spilled more.
+#ifndef CS_OCC_LEAN
+#define CS_OCC_LEAN 1
+#endif
+__device__ __forceinline__ void bwd_l2_table(const DevIndex &ix, uint64_t *l2p1) // every thread of the workgroup must call it
+{
+	if (threadIdx.x < 4) l2p1[threadIdx.x] = (threadIdx.x == 0 ? ix.L2[0] : threadIdx.x == 1 ? ix.L2[1] : threadIdx.x == 2 ? ix.L2[2] : ix.L2[3]) + 1ull;
+	__syncthreads();
+}
+template <class WC>
+__device__ __forceinline__ Intv bwd_extend(const DevIndex &ix, const uint64_t *l2p1, const Intv &e, int c, WC &W)
+{
+#if CS_OCC_LEAN
+	return extend1b(ix, l2p1, e, c, W);
+#else
+	return extend1<true>(ix, e, c, W);
+#endif
+}
+
 template <int G, class WC>
 __device__ __forceinline__ void bwd_groups_run(const SplitArgs &A, const BTask *bq, uint64_t n_tasks, unsigned long long *ctr, WaveOut &O,
-                                               unsigned long long &my_q, unsigned long long &my_hits, uint4 *sst, WC &W)
+                                               unsigned long long &my_q, unsigned long long &my_hits, uint4 *sst, const uint64_t *l2p1, WC &W)
 {
 	const bool use_sst = A.sst != 0;
 	int slen = SST2_K; uint32_t scode = 0; // this lane's match as a string, while it is short enough for the SST
@@ -90,7 +111,7 @@ __device__ __forceinline__ void bwd_groups_run(const SplitArgs &A, const BTask *
 				if (live) {
 					++my_q;
 					if (cached) ++my_hits;
-					else { y = extend1<true>(ix, e, (int)b, W); if (cacheable) sst_put(sst, A.sst2, slen + 1, ccode, y); }
+					else { y = bwd_extend(ix, l2p1, e, (int)b, W); if (cacheable) sst_put(sst, A.sst2, slen + 1, ccode, y); }
 					if (slen < SST2_K) { scode = ccode; ++slen; }
 				}
 				bool stop = live && y.x2 < min_intv, cand = live && !stop;
@@ -189,16 +210,28 @@ __device__ __forceinline__ bool win_lane_init(const SplitArgs &A, PackedReader &
 #ifndef CS_WIN_RELEASE
 #define CS_WIN_RELEASE 1
 #endif
+// CS_WIN_BOOK: the loop's bookkeeping kept in lane masks -- same ballots in the same places, same rules (0: the loop as it was, for A/B
+// builds: make variant DEFS=-DCS_WIN_BOOK=0).
+#ifndef CS_WIN_BOOK
+#define CS_WIN_BOOK 1
+#endif
+__device__ __forceinline__ uint64_t lane_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); } // __ballot without the trip through a 0/1 register
 template <class WC>
 __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq, uint64_t n_tasks, unsigned long long *ctr, WaveOut &O,
-                                            unsigned long long &my_q, unsigned long long &my_hits, uint8_t *slot_w, WC &W)
+                                            unsigned long long &my_q, unsigned long long &my_hits, uint8_t *slot_w, const uint64_t *l2p1, WC &W)
 {
 	const DevIndex &ix = A.ix;
 	const uint32_t lane = threadIdx.x & 63u;
 	uint64_t gmask = 0;
 	bool walking = false, valid = false;
-	uint32_t r = 0, kind = 0, min_intv = 1, pend = 0;
-	int s = 0, f = 0, ret = 0, xp = 0, clk = 0;
+	// Per-lane state is kept narrow (the kernel runs at the register limit of its six waves per SIMD): the call's pivot and forward end
+	// share a word (both 16 bits), the kind carries in bit 2 whether this lane is NOT its call's rank 0 (WIN_TAIL) -- early release never
+	// takes a call's rank 0, so that is the same lane from placement to the call's end, whatever left the set in between --, a lane that
+	// stops keeps its position in s (a stopped lane's s is the f of the scheme above: nothing moves it any more), and the extensions and
+	// jump-table credits are counted in 32 bits and added to the kernel's 64-bit counters once, at the end.
+	constexpr uint32_t WIN_TAIL = 4u;
+	uint32_t r = 0, kind = 0, min_intv = 1, pend = 0, retx = 0, nq = 0, nh = 0;
+	int s = 0, clk = 0;
 	Intv e = {0, 0, 0};
 	PackedReader rd;
 	// wave-uniform: the free lanes, the 64 slots drawn last and which of them still wait, and the lanes the next placement needs
@@ -235,12 +268,15 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 			if (fresh) {
 				const uint32_t gl = csls::rank_in(gmask, lane);
 				BTask bt = bq[t];
-				r = bt.r; kind = bt.mi_kind >> 14; min_intv = bt.mi_kind & 0x3fffu; ret = bt.ret; xp = bt.x;
+				const int xp = bt.x, ret = bt.ret;
+				r = bt.r; kind = (uint32_t)(bt.mi_kind >> 14) | (gl ? WIN_TAIL : 0u); min_intv = bt.mi_kind & 0x3fffu; retx = (uint32_t)ret | (uint32_t)xp << 16;
 				const uint64_t rb = A.off[r];
-				f = 0x7fffffff;
 				rd.start(A.seqp, rb, r, xp);
-				if (gl < (uint32_t)WIN_LANES) valid = win_lane_init(A, rd, gl, xp, ret, min_intv, e, pend, s, my_q, my_hits, W);
-				else { // (the set has exactly 18 + n members: every rank from 18 on has its LEP)
+				if (gl < (uint32_t)WIN_LANES) {
+					unsigned long long q0 = 0, h0 = 0;
+					valid = win_lane_init(A, rd, gl, xp, ret, min_intv, e, pend, s, q0, h0, W);
+					nq += (uint32_t)q0; nh += (uint32_t)h0;
+				} else { // (the set has exactly 18 + n members: every rank from 18 on has its LEP)
 					unpack_lep(A.lep[(size_t)t * A.lep_stride + ((int)gl - WIN_LANES)], e, pend); s = xp - 1; wc_add(W, EV_LEP);
 					valid = true;
 				}
@@ -251,24 +287,70 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 		}
 		place = false;
 		if (exhausted && avail_m == 0 && F == ~0ull) break; // wave-uniform exit
-		uint64_t push0 = FTASK_NONE, push1 = FTASK_NONE, aux0 = AUX_NONE;
 #ifdef CS_STEP_HIST
 		W.steps((uint32_t)__popcll(__ballot(gmask != 0 && walking && s == clk)));
 #endif
+#if CS_WIN_BOOK
+		// One clock per call: position clk is the read base every walking lane prepends in this iteration.  A lane joins when the clock
+		// reaches the base in front of its match (the window lanes start staggered, the LEPs at the pivot), so all lanes that walk hold
+		// matches with the SAME start, and the equal-size rule of bwt.c:337-340 applies to them as it stands: a match with as many
+		// occurrences as the next longer walking one has the same occurrences, shares its fate from here on and is never reported -- it
+		// stops.  In repeats that is most lanes.
+		// The kernel is bound by the VALU instructions of this loop, so its bookkeeping is kept out of the vector ALU where it can be: a
+		// lane that walks belongs to a call (walking implies gmask != 0), so the step needs no test of gmask -- free lanes carry a stale clk
+		// and take part in the ballots below with false --, "the lanes above me in this ballot" is made once per use, and the defaults of
+		// the pushes exist only in the iteration in which some call ends.
+		const bool step = walking && s == clk;
+		if (step) {
+			uint32_t b = s < 0 ? 4u : rd.at(s);
+			if (b > 3) walking = false;
+			else {
+				Intv y = bwd_extend(ix, l2p1, e, (int)b, W); ++nq;
+				if (y.x2 < min_intv) walking = false; else { e = y; --s; }
+			}
+		}
+		if ((clk & 3) == 0) { // (every fourth step is enough: a lane that could have stopped earlier only repeats a few extensions)
+			const bool surv = step && walking;
+			const uint64_t hi = lane_mask(surv) & gmask & csls::above(lane);
+			const uint32_t ax2 = __shfl(e.x2, hi ? (int)__builtin_ctzll(hi) : (int)lane);
+			if (surv && hi != 0 && ax2 == e.x2) { walking = false; valid = false; }
+		}
+		--clk;
+		const bool ending = gmask != 0 && (lane_mask(walking) & gmask) == 0; // all ends of this lane's call are settled
+		if (lane_mask(ending)) { // (a call ends once in ~20 iterations: the first-survivor rule and the dispenser stay off the common path)
+			uint64_t push0 = FTASK_NONE, push1 = FTASK_NONE, aux0 = AUX_NONE;
+			if (ending) {
+				const uint64_t hi = lane_mask(valid) & gmask & csls::above(lane);
+				const int fn = __shfl(s, hi ? (int)__builtin_ctzll(hi) : (int)lane);
+				if (valid && (hi == 0 || s < fn)) push0 = emit_smem(A, r, kind & 3u, e, s + 1, pend, aux0);
+				if (kind == TK_ROUND1) push1 = chain_round1(rd, r, (int)(A.off[r + 1] - A.off[r]), (int)(retx & 0xffffu), (int)(retx >> 16)); // (rank 0 only: no WIN_TAIL)
+				valid = false;
+			}
+			wave_push<32>(O, push0 != FTASK_NONE, push0, A, aux0);
+			wave_push<32>(O, push1 != FTASK_NONE, push1, A);
+		}
+		// lanes that go back to F: those of the calls that ended, and (CS_WIN_RELEASE) those that can no longer matter
+#if CS_WIN_RELEASE
+		const uint64_t gone = lane_mask(gmask != 0 && !valid && (ending || kind >= WIN_TAIL));
+#else
+		const uint64_t gone = lane_mask(ending);
+#endif
+		if (gone) {
+			F |= gone; place = true;
+			gmask = csls::has(gone, lane) ? 0ull : csls::release(gmask, gone);
+		}
+#else
+		uint64_t push0 = FTASK_NONE, push1 = FTASK_NONE, aux0 = AUX_NONE;
 		bool ended = false;
 		if (gmask != 0) {
-			// One clock per call: position clk is the read base every walking lane prepends in this iteration.  A lane joins
-			// when the clock reaches the base in front of its match (the window lanes start staggered, the LEPs at the pivot),
-			// so all lanes that walk hold matches with the SAME start, and the equal-size rule of bwt.c:337-340 applies to
-			// them as it stands: a match with as many occurrences as the next longer walking one has the same occurrences,
-			// shares its fate from here on and is never reported -- it stops.  In repeats that is most lanes.
+			// (the loop as it was before CS_WIN_BOOK: every lane predicate through a 0/1 register, defaults of the pushes set up every iteration)
 			const bool step = walking && s == clk;
 			if (step) {
 				uint32_t b = s < 0 ? 4u : rd.at(s);
-				if (b > 3) { f = s; walking = false; }
+				if (b > 3) walking = false;
 				else {
-					Intv y = extend1<true>(ix, e, (int)b, W); ++my_q;
-					if (y.x2 < min_intv) { f = s; walking = false; } else { e = y; --s; }
+					Intv y = bwd_extend(ix, l2p1, e, (int)b, W); ++nq;
+					if (y.x2 < min_intv) walking = false; else { e = y; --s; }
 				}
 			}
 			if ((clk & 3) == 0) { // (every fourth step is enough: a lane that could have stopped earlier only repeats a few extensions)
@@ -280,15 +362,15 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 			--clk;
 			if ((__ballot(walking) & gmask) == 0) { // all ends of this call are settled: apply the first-survivor rule
 				const uint64_t vm = __ballot(valid) & gmask, higher = vm & csls::above(lane);
-				const int fn = __shfl(f, (int)csls::next_member(vm, lane));
-				if (valid && (higher == 0 || f < fn)) push0 = emit_smem(A, r, kind, e, f + 1, pend, aux0);
-				if (kind == TK_ROUND1 && csls::rank_in(gmask, lane) == 0) push1 = chain_round1(rd, r, (int)(A.off[r + 1] - A.off[r]), ret, xp);
+				const int fn = __shfl(s, (int)csls::next_member(vm, lane));
+				if (valid && (higher == 0 || s < fn)) push0 = emit_smem(A, r, kind & 3u, e, s + 1, pend, aux0);
+				if (kind == TK_ROUND1) push1 = chain_round1(rd, r, (int)(A.off[r + 1] - A.off[r]), (int)(retx & 0xffffu), (int)(retx >> 16));
 				ended = true; valid = false;
 			}
 		}
 		// lanes that go back to F: those of the calls that ended, and (CS_WIN_RELEASE) those that can no longer matter
 #if CS_WIN_RELEASE
-		const uint64_t gone = __ballot(ended || (gmask != 0 && !valid && csls::rank_in(gmask, lane) != 0));
+		const uint64_t gone = __ballot(ended || (gmask != 0 && !valid && kind >= WIN_TAIL));
 #else
 		const uint64_t gone = __ballot(ended);
 #endif
@@ -300,7 +382,9 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 			wave_push<32>(O, push0 != FTASK_NONE, push0, A, aux0);
 			wave_push<32>(O, push1 != FTASK_NONE, push1, A);
 		}
+#endif
 	}
+	my_q += nq; my_hits += nh;
 }
 
 // Calls with more than 64 LEPs (tandem arrays, very long reads): one WAVE per call, the list stays in HBM and every step
@@ -309,7 +393,7 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 // carried from chunk to chunk.
 template <class WC>
 __device__ __forceinline__ void bwd_wide_run(const SplitArgs &A, const BTask *bq, uint64_t n_tasks, unsigned long long *ctr, WaveOut &O,
-                                             unsigned long long &my_q, WC &W)
+                                             unsigned long long &my_q, const uint64_t *l2p1, WC &W)
 {
 	const DevIndex &ix = A.ix;
 	const uint32_t lane = threadIdx.x & 63u;
@@ -342,7 +426,7 @@ __device__ __forceinline__ void bwd_wide_run(const SplitArgs &A, const BTask *bq
 			for (int i = (int)bt.x - 1; i >= -1; --i) {
 				const uint32_t b = i < 0 ? 4u : rd.at(i);
 				Intv y = p;
-				if (live && b <= 3) { y = extend1<true>(ix, p, (int)b, W); ++my_q; }
+				if (live && b <= 3) { y = bwd_extend(ix, l2p1, p, (int)b, W); ++my_q; }
 				const bool cand = live && b <= 3 && y.x2 >= min_intv;
 				const uint64_t live_m = __ballot(live), cand_m = __ballot(cand);
 				const int first = __ffsll((long long)live_m) - 1;
@@ -370,7 +454,7 @@ __device__ __forceinline__ void bwd_wide_run(const SplitArgs &A, const BTask *bq
 				Intv p = {0, 0, 0}; uint32_t pend = 0;
 				if (valid) { unpack_lep(lep[j], p, pend); wc_add(W, EV_LEP); }
 				Intv y = p;
-				if (valid && b <= 3) { y = extend1<true>(ix, p, (int)b, W); ++my_q; }
+				if (valid && b <= 3) { y = bwd_extend(ix, l2p1, p, (int)b, W); ++my_q; }
 				bool cand = valid && b <= 3 && y.x2 >= min_intv;
 				uint64_t cand_m = __ballot(cand);
 				if (!first_done) { // lane 0 of the first chunk holds the longest live match (bwt.c:328-336)
@@ -407,7 +491,7 @@ __device__ __forceinline__ void bwd_wide_run(const SplitArgs &A, const BTask *bq
 					uint32_t b = s < 0 ? 4u : rd.at(s);
 					if (b > 3) { f = s; walking = false; }
 					else {
-						Intv y = extend1<true>(ix, e, (int)b, W); ++my_q;
+						Intv y = bwd_extend(ix, l2p1, e, (int)b, W); ++my_q;
 						if (y.x2 < min_intv) { f = s; walking = false; } else { e = y; --s; }
 					}
 				}
@@ -437,21 +521,23 @@ __global__ __launch_bounds__(BLOCK, 5) void bwd_all_kernel(const SplitArgs A, co
 	WaveOut O = {0, 0};
 	unsigned long long my_q = 0, my_hits = 0;
 	__shared__ uint4 sst[SST_ENTRIES];
+	__shared__ uint64_t l2p1[4];
 	sst_clear(sst);
+	bwd_l2_table(A.ix, l2p1);
 	WaveCtrT<COUNT> W;
 	const uint32_t role = blockIdx.x & 7u; // 5/8 of the workgroups start on the <=16 class, 2/8 on <=32, 1/8 on <=64
 	if (role < 5) {
-		bwd_groups_run<16>(A, bq, n_tasks, ctrs + 0, O, my_q, my_hits, sst, W);
-		bwd_groups_run<32>(A, bq, n_tasks, ctrs + 1, O, my_q, my_hits, sst, W);
-		bwd_groups_run<64>(A, bq, n_tasks, ctrs + 2, O, my_q, my_hits, sst, W);
+		bwd_groups_run<16>(A, bq, n_tasks, ctrs + 0, O, my_q, my_hits, sst, l2p1, W);
+		bwd_groups_run<32>(A, bq, n_tasks, ctrs + 1, O, my_q, my_hits, sst, l2p1, W);
+		bwd_groups_run<64>(A, bq, n_tasks, ctrs + 2, O, my_q, my_hits, sst, l2p1, W);
 	} else if (role < 7) {
-		bwd_groups_run<32>(A, bq, n_tasks, ctrs + 1, O, my_q, my_hits, sst, W);
-		bwd_groups_run<64>(A, bq, n_tasks, ctrs + 2, O, my_q, my_hits, sst, W);
-		bwd_groups_run<16>(A, bq, n_tasks, ctrs + 0, O, my_q, my_hits, sst, W);
+		bwd_groups_run<32>(A, bq, n_tasks, ctrs + 1, O, my_q, my_hits, sst, l2p1, W);
+		bwd_groups_run<64>(A, bq, n_tasks, ctrs + 2, O, my_q, my_hits, sst, l2p1, W);
+		bwd_groups_run<16>(A, bq, n_tasks, ctrs + 0, O, my_q, my_hits, sst, l2p1, W);
 	} else {
-		bwd_groups_run<64>(A, bq, n_tasks, ctrs + 2, O, my_q, my_hits, sst, W);
-		bwd_groups_run<16>(A, bq, n_tasks, ctrs + 0, O, my_q, my_hits, sst, W);
-		bwd_groups_run<32>(A, bq, n_tasks, ctrs + 1, O, my_q, my_hits, sst, W);
+		bwd_groups_run<64>(A, bq, n_tasks, ctrs + 2, O, my_q, my_hits, sst, l2p1, W);
+		bwd_groups_run<16>(A, bq, n_tasks, ctrs + 0, O, my_q, my_hits, sst, l2p1, W);
+		bwd_groups_run<32>(A, bq, n_tasks, ctrs + 1, O, my_q, my_hits, sst, l2p1, W);
 	}
 	wave_push_finish(O, A);
 	atomicAdd(A.n_queries, my_q);
@@ -620,10 +706,12 @@ __global__ __launch_bounds__(BLOCK, CS_WIN_WAVES) void bwd_win_kernel(const Spli
 {
 	if (*A.n_btasks == 0) return;
 	__shared__ uint8_t slot_w[BLOCK / 64][64]; // per wave: the lanes each of the 64 slots drawn last needs
+	__shared__ uint64_t l2p1[4];
 	WaveOut O = {0, 0};
 	WaveCtrT<COUNT> W;
 	unsigned long long my_q = 0, my_hits = 0;
-	bwd_win_run(A, bq, n_tasks, ctrs, O, my_q, my_hits, slot_w[threadIdx.x >> 6], W);
+	bwd_l2_table(A.ix, l2p1);
+	bwd_win_run(A, bq, n_tasks, ctrs, O, my_q, my_hits, slot_w[threadIdx.x >> 6], l2p1, W);
 	wave_push_finish(O, A);
 	atomicAdd(A.n_queries, my_q);
 	if (my_hits) atomicAdd(A.n_sst_hits, my_hits);
@@ -641,7 +729,9 @@ __global__ __launch_bounds__(256, CS_WIDE_BLOCKS) void bwd_wide_kernel(const Spl
 	WaveOut O = {0, 0};
 	WaveCtrT<COUNT> W;
 	unsigned long long my_q = 0;
-	bwd_wide_run(A, bq, n_tasks, ctr, O, my_q, W);
+	__shared__ uint64_t l2p1[4];
+	bwd_l2_table(A.ix, l2p1);
+	bwd_wide_run(A, bq, n_tasks, ctr, O, my_q, l2p1, W);
 	wave_push_finish(O, A);
 	atomicAdd(A.n_queries, my_q);
 	wc_flush(W, A.evc, KID_BWD_WIDE);
