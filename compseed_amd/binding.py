@@ -22,7 +22,8 @@ SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", 
            "cs_device_download", "cs_device_sync", "cs_packed_seed_rbeg", "cs_engine_check_index",
            "cs_ext_params_default", "cs_extender_create", "cs_extender_destroy", "cs_extend_batch", "cs_extend_batch_device", "cs_extender_stats",
            "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_extend_chains_device", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats",
-           "cs_regions_cigar", "cs_cigar_stats", "cs_mark_params_default", "cs_regions_mark", "cs_mark_stats"]
+           "cs_regions_cigar", "cs_cigar_stats", "cs_mark_params_default", "cs_regions_mark", "cs_mark_stats",
+           "cs_regions_sam", "cs_sam_header", "cs_sam_stats"]
 
 
 class CSError(RuntimeError):
@@ -231,6 +232,22 @@ class CMarkResult(C.Structure):
 
 class MarkStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("reads", "regions", "lines", "xa_members", "cigar_regions", "light_reads", "wave_reads", "hbm_reads", "launches")] + [("kernel_ms", C.c_double)]
+
+
+# cs_regions_sam: the SAM text
+SAM_SOFTCLIP, SAM_WAVE_ONLY = 1, 0x100
+
+
+class SamParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("rg_id", C.c_char_p)]
+
+
+class CSamResult(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("n_lines", C.c_uint64), ("n_bytes", C.c_uint64), ("text_off", C.c_void_p), ("text", C.c_void_p)]
+
+
+class SamStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "lines", "unmapped", "bytes", "xa_entries", "sa_entries", "launches")] + [("kernel_ms", C.c_double)]
 
 
 class IndexCheck(C.Structure):
@@ -444,6 +461,9 @@ def load_library():
     L.cs_mark_params_default.restype = None
     L.cs_regions_mark.argtypes = [vp, C.POINTER(MarkParams), C.POINTER(CAlnResult), vp, C.c_int64, C.c_uint32, C.POINTER(CMarkResult)]
     L.cs_mark_stats.argtypes = [vp, C.POINTER(MarkStats)]
+    L.cs_regions_sam.argtypes = [vp, C.POINTER(SamParams), C.POINTER(CMarkResult), vp, C.POINTER(CCigarResult), vp, vp, vp, vp, vp, vp, vp, C.POINTER(CSamResult)]
+    L.cs_sam_header.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.cs_sam_stats.argtypes = [vp, C.POINTER(SamStats)]
     _lib = L
     return L
 
@@ -1120,6 +1140,53 @@ class Aligner:
         st = MarkStats()
         _check(self.L.cs_mark_stats(self.h, C.byref(st)))
         return {n: (float(getattr(st, n)) if n == "kernel_ms" else int(getattr(st, n))) for n, _ in MarkStats._fields_}
+
+    def regions_sam(self, marks, alns, bases, read_offsets, names, quals=None, comments=None, softclip=False, rg_id=None, flags=0, reg_off=None):
+        """cs_regions_sam (mem_aln2sam, the string part of mem_gen_alt, the unmapped record): `marks` regions_mark's dict, `alns` regions_cigar's
+        dict over marks' cigar_regs, `reg_off` the reg_off regions_mark was given (or marks["reg_off"]), `names` / `comments` pairs
+        (bytes as uint8, uint64 CSR offsets) or lists of bytes, `quals` uint8 at the bases' offsets -> (text_off, text): read r's records are
+        text[text_off[r]:text_off[r + 1]], text as a whole the body of the reference's output.  softclip: -Y; rg_id: the ID of -R's line"""
+        def pair(x):
+            if isinstance(x, (list, tuple)) and (len(x) != 2 or isinstance(x[0], (bytes, str))):
+                x = [y.encode() if isinstance(y, str) else y for y in x]
+                off = np.zeros(len(x) + 1, np.uint64)
+                off[1:] = np.cumsum([len(y) for y in x])
+                x = (np.frombuffer(b"".join(x), np.uint8), off)
+            b = np.ascontiguousarray(x[0], dtype=np.uint8)
+            return (b if b.size else np.zeros(1, np.uint8)), np.ascontiguousarray(x[1], dtype=np.uint64)
+        reg_off = np.ascontiguousarray(marks["reg_off"] if reg_off is None else reg_off, dtype=np.uint64)
+        m = np.ascontiguousarray(marks["marks"], dtype=MARK_DT); lo = np.ascontiguousarray(marks["line_off"], dtype=np.uint64)
+        co = np.ascontiguousarray(marks["cigar_reg_off"], dtype=np.uint64); cr = np.ascontiguousarray(marks["cigar_regs"], dtype=ALNREG_DT); cs = np.ascontiguousarray(marks["cigar_src"], dtype=np.uint32)
+        a = np.ascontiguousarray(alns["alns"], dtype=ALN_DT); cg = np.ascontiguousarray(alns["cigar"], dtype=np.uint32); md = np.ascontiguousarray(alns["md"], dtype=np.uint8)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8); ro = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+        q = None if quals is None else np.ascontiguousarray(quals, dtype=np.uint8)
+        nm, no = pair(names)
+        cm, cmo = pair(comments) if comments is not None else (None, None)
+        ptr = lambda x: x.ctypes.data if x is not None and x.size else None
+        n = lo.size - 1
+        cmark = CMarkResult(n, m.size, int(lo[n]) if lo.size else 0, ptr(m), ptr(lo), CAlnResult(co.size - 1, cr.size, ptr(co), ptr(cr)), ptr(cs))
+        ccig = CCigarResult(a.size, cg.size, md.size, ptr(a), ptr(cg), ptr(md))
+        par = SamParams(int(flags) | (SAM_SOFTCLIP if softclip else 0), rg_id.encode() if isinstance(rg_id, str) else rg_id)
+        out = CSamResult()
+        _check(self.L.cs_regions_sam(self.h, C.byref(par), C.byref(cmark), ptr(reg_off), C.byref(ccig), ptr(bases), ptr(ro), ptr(q), nm.ctypes.data, ptr(no),
+                                     cm.ctypes.data if cm is not None else None, ptr(cmo), C.byref(out)))
+        return _view(out.text_off, "<u8", int(out.n_reads) + 1, True), (C.string_at(out.text, int(out.n_bytes)) if out.n_bytes else b"")
+
+    def sam_header(self, rg_line=None):
+        """cs_sam_header: the @SQ lines and, where given, the @RG line (as -R takes it: tabs written as a backslash and a t); host only"""
+        rg = rg_line.encode() if isinstance(rg_line, str) else rg_line
+        need = C.c_size_t()
+        rc = self.L.cs_sam_header(self.h, rg, None, 0, C.byref(need))
+        if rc != 0 and need.value == 0:
+            _check(rc)
+        buf = C.create_string_buffer(max(1, need.value))
+        _check(self.L.cs_sam_header(self.h, rg, buf, need.value, C.byref(need)))
+        return buf.raw[:need.value]
+
+    def sam_stats(self):
+        st = SamStats()
+        _check(self.L.cs_sam_stats(self.h, C.byref(st)))
+        return {n: (float(getattr(st, n)) if n == "kernel_ms" else int(getattr(st, n))) for n, _ in SamStats._fields_}
 
     def stats(self):
         st = AlnStats()

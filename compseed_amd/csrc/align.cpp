@@ -24,6 +24,8 @@ struct cs_aligner {
 	cs_aln_stats_t st{};
 	cs_cigar_gpu *cig = nullptr;          // the device side of cs_regions_cigar (cigar_gpu.hip), with its result
 	cs_mark_gpu *mrk = nullptr;           // the device side of cs_regions_mark (mark_gpu.hip), with its result
+	cs_sam_gpu *sam = nullptr;            // the device side of cs_regions_sam (sam_gpu.hip), with its result
+	std::vector<std::string> ctg_names;   // the contigs' names from <prefix>.ann: the SAM stage's RNAME and cs_sam_header's SN
 };
 
 
@@ -33,6 +35,23 @@ extern "C" void cs_aln_params_default(cs_aln_params_t *p)
 	// mem_opt_init (comp_seed.cpp:26-58)
 	p->a = 1; p->b = 4; p->o_del = p->o_ins = 6; p->e_del = p->e_ins = 1; p->pen_clip5 = p->pen_clip3 = 5; p->w = 100; p->zdrop = 100;
 	p->threads = 16; p->flags = 0;
+}
+
+// the names of <prefix>.ann's contigs (cs_load_contigs_ reads the same lines for the offsets: "gi name [comment]", then "offset len n_ambs")
+static int cs_load_contig_names_(const char *prefix, size_t n_seqs, std::vector<std::string> &names)
+{
+	FILE *fp = fopen((std::string(prefix) + ".ann").c_str(), "r");
+	if (!fp) return cs_fail_(CS_EIO, std::string("cannot read ") + prefix + ".ann");
+	std::vector<char> line(1 << 16), name(8192);
+	bool ok = fgets(line.data(), (int)line.size(), fp) != nullptr;
+	names.clear();
+	for (size_t i = 0; ok && i < n_seqs; ++i) {
+		unsigned gi = 0;
+		ok = fscanf(fp, "%u%8191s", &gi, name.data()) == 2 && fgets(line.data(), (int)line.size(), fp) != nullptr;   // the comment up to the end of the line
+		if (ok) { names.push_back(name.data()); ok = fgets(line.data(), (int)line.size(), fp) != nullptr; }
+	}
+	fclose(fp);
+	return ok ? CS_OK : cs_fail_(CS_EIO, std::string(prefix) + ".ann is malformed");
 }
 
 extern "C" int cs_aligner_create(const char *prefix, int device, const cs_aln_params_t *par, cs_aligner_t **out)
@@ -46,6 +65,8 @@ extern "C" int cs_aligner_create(const char *prefix, int device, const cs_aln_pa
 	int rc = cs_load_contigs_(prefix, A->ref);
 	if (rc != CS_OK) { delete A; return rc; }
 	rc = cs_load_pac_(prefix, A->ref.l_pac, A->pac);
+	if (rc != CS_OK) { delete A; return rc; }
+	rc = cs_load_contig_names_(prefix, A->ref.offset.size(), A->ctg_names);
 	if (rc != CS_OK) { delete A; return rc; }
 	cs_ext_params_t xp;
 	for (int i = 0, k = 0; i < 5; ++i) for (int j = 0; j < 5; ++j) xp.mat[k++] = (int8_t)(i == 4 || j == 4 ? -1 : i == j ? o.a : -o.b); // bwa_fill_scmat (bwalib/bwa.c:17-29)
@@ -69,6 +90,7 @@ extern "C" void cs_aligner_destroy(cs_aligner_t *A)
 	if (A->gpu) cs_aligner_gpu_release_(A->gpu);
 	if (A->cig) cs_cigar_gpu_release_(A->cig);
 	if (A->mrk) cs_mark_gpu_release_(A->mrk);
+	if (A->sam) cs_sam_gpu_release_(A->sam);
 	if (A->ext) cs_extender_destroy(A->ext);
 	delete A;
 }
@@ -160,6 +182,55 @@ extern "C" int cs_mark_stats(const cs_aligner_t *A, cs_mark_stats_t *st)
 {
 	if (!A || !st) return cs_fail_(CS_EINVAL, "null argument");
 	return cs_mark_gpu_stats_(A->mrk, st);
+}
+
+// the SAM text (sam_gpu.hip): only what the host can know is checked here, the arrays by a kernel
+extern "C" int cs_regions_sam(cs_aligner_t *A, const cs_sam_params_t *par, const cs_mark_result_t *marks, const uint64_t *reg_off, const cs_cigar_result_t *alns,
+                              const uint8_t *bases, const uint64_t *read_offsets, const uint8_t *quals, const char *names, const uint64_t *name_off,
+                              const char *comments, const uint64_t *comment_off, cs_sam_result_t *out)
+{
+	if (!A || !par || !marks || !alns || !out) return cs_fail_(CS_EINVAL, "cs_regions_sam: null argument");
+	if (par->flags & ~(CS_SAM_SOFTCLIP | CS_SAM_WAVE_ONLY)) return cs_fail_(CS_EINVAL, "cs_regions_sam: unknown flags");
+	if (par->rg_id && strlen(par->rg_id) > 255) return cs_fail_(CS_EINVAL, "cs_regions_sam: an RG id of more than 255 characters");
+	const int64_t n = marks->n_reads;
+	const uint64_t n_ents = marks->cigar_regs.n_regs;
+	if (n < 0 || marks->cigar_regs.n_reads != n || (n > 0 && (!reg_off || !marks->line_off || !marks->cigar_regs.reg_off || !read_offsets || !name_off)) || (marks->n_regs > 0 && !marks->marks) ||
+	    (n_ents > 0 && (!marks->cigar_src || !marks->cigar_regs.regs)) || (alns->n_regs > 0 && !alns->alns) || (alns->n_cigar > 0 && !alns->cigar) || (alns->md_bytes > 0 && !alns->md) ||
+	    (n > 0 && ((read_offsets[n] > 0 && !bases) || (name_off[n] > 0 && !names))))
+		return cs_fail_(CS_EINVAL, "cs_regions_sam: bad argument");
+	if (alns->n_regs != n_ents) return cs_fail_(CS_EINVAL, "cs_regions_sam: alns is not cs_regions_cigar's result over marks->cigar_regs (one entry per entry)");
+	if (!comments != !comment_off) return cs_fail_(CS_EINVAL, "cs_regions_sam: comments and comment_off come together or not at all");
+	if (A->device < 0) return cs_fail_(CS_EDEVICE, "cs_regions_sam: this aligner was created without a device (device -1): the text is made on the GPU only");
+	if (n >= 0xffffffffll || marks->n_regs >= 0xffffffffull || marks->n_lines >= 0xffffffffull) return cs_fail_(CS_ERANGE, "cs_regions_sam: 2^32 reads, regions or lines or more in one call");
+	return cs_regions_sam_gpu_(&A->sam, A->device, A->ref, A->ctg_names, par->flags, par->rg_id, marks, reg_off, alns, bases, read_offsets, quals, names, name_off, comments, comment_off, out);
+}
+extern "C" int cs_sam_stats(const cs_aligner_t *A, cs_sam_stats_t *st)
+{
+	if (!A || !st) return cs_fail_(CS_EINVAL, "null argument");
+	return cs_sam_gpu_stats_(A->sam, st);
+}
+// bwa_print_sam_hdr (bwalib/bwa.c:406-427) for the aligner's contigs, behind it the read-group line unescaped as bwa_set_rg / bwa_escape do (:429-476)
+extern "C" int cs_sam_header(const cs_aligner_t *A, const char *rg_line, char *buf, size_t cap, size_t *need)
+{
+	if (!A || !need || (!buf && cap)) return cs_fail_(CS_EINVAL, "cs_sam_header: null argument");
+	std::string h;
+	for (size_t i = 0; i < A->ctg_names.size(); ++i) h += "@SQ\tSN:" + A->ctg_names[i] + "\tLN:" + std::to_string(A->ref.len[i]) + (A->ref.is_alt[i] ? "\tAH:*\n" : "\n");
+	if (rg_line) {
+		if (strncmp(rg_line, "@RG", 3) != 0 || strchr(rg_line, '\t')) return cs_fail_(CS_EINVAL, "cs_sam_header: the read group line starts with @RG and holds no literal tab (write \\t)");
+		std::string rg;
+		for (const char *p = rg_line; *p; ++p) {
+			if (*p != '\\') { rg += *p; continue; }
+			++p;
+			if (*p == 't') rg += '\t'; else if (*p == 'n') rg += '\n'; else if (*p == 'r') rg += '\r'; else if (*p == '\\') rg += '\\';
+			if (!*p) break;
+		}
+		if (rg.find("\tID:") == std::string::npos) return cs_fail_(CS_EINVAL, "cs_sam_header: no ID in the read group line");
+		h += rg + "\n";
+	}
+	*need = h.size();
+	if (h.size() > cap) return cs_fail_(CS_ERANGE, "cs_sam_header: the buffer is too small");
+	if (!h.empty()) memcpy(buf, h.data(), h.size());
+	return CS_OK;
 }
 
 extern "C" int cs_aligner_stats(const cs_aligner_t *A, cs_aln_stats_t *st)

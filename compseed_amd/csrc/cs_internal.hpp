@@ -85,6 +85,13 @@ void cs_mark_gpu_release_(cs_mark_gpu *g);
 int cs_mark_gpu_stats_(const cs_mark_gpu *g, cs_mark_stats_t *st);
 int cs_regions_mark_gpu_(cs_mark_gpu **gp, int device, const cs_refseq_view &R, const cs_aln_params_t &o, const cs_mark_params_t &par, const cs_aln_result_t *regs,
                          const uint64_t *read_offsets, int64_t id_base, uint32_t flags, cs_mark_result_t *out);
+// ... and of cs_regions_sam (sam_gpu.hip): the SAM text from marks and alignments; ctg: the contigs' names
+struct cs_sam_gpu;
+void cs_sam_gpu_release_(cs_sam_gpu *g);
+int cs_sam_gpu_stats_(const cs_sam_gpu *g, cs_sam_stats_t *st);
+int cs_regions_sam_gpu_(cs_sam_gpu **gp, int device, const cs_refseq_view &R, const std::vector<std::string> &ctg, uint32_t flags, const char *rg_id, const cs_mark_result_t *marks,
+                        const uint64_t *reg_off, const cs_cigar_result_t *alns, const uint8_t *bases, const uint64_t *read_offsets, const uint8_t *quals, const char *names,
+                        const uint64_t *name_off, const char *comments, const uint64_t *comment_off, cs_sam_result_t *out);
 
 // ---- the host passes' work sharing: fn(k) for k in [0, n_chunks) on T threads, chunks of reads handed out by a counter.  (A read inside a
 // repeat costs a hundred times the average in the quadratic passes -- chain filter, dedup --; equal shares left fifteen threads waiting for

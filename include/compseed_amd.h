@@ -502,7 +502,7 @@ int  cs_dedup_regions(cs_aligner_t *a, const cs_dedup_params_t *par, const cs_al
                       cs_aln_result_t *out, const int32_t **n_comp);
 int  cs_aligner_stats(const cs_aligner_t *a, cs_aln_stats_t *st);
 /* From regions to alignments on the GPU: what the reference does with every region it reports (mem_reg2aln, comp_seed.cpp:811-880, without
- * primary marking and MAPQ, which are cs_regions_mark's below, and SAM text, which stays the caller's) -- the band inferred from the region, the banded global alignment with
+ * primary marking and MAPQ, which are cs_regions_mark's below, and SAM text, which is cs_regions_sam's) -- the band inferred from the region, the banded global alignment with
  * backtrack (bwa_gen_cigar2 / ksw_global2) up to three times with a doubled band, NM and MD, a leading or else a trailing deletion
  * squeezed out, the soft clips, and the position in contig coordinates.  Host arrays in (`regs`: cs_extend_chains' or cs_dedup_regions'
  * result, or the caller's regions in that form; `bases` / `read_offsets`: the reads); host arrays owned by the aligner out, valid until
@@ -536,8 +536,8 @@ int  cs_cigar_stats(const cs_aligner_t *a, cs_cigar_stats_t *st);
  * `line` the index of the region's SAM line within the read or -1, `flag` that line's 0x10 | 0x100 | 0x800 bits, `mapq` its MAPQ (0 for
  * a secondary), `xs` its XS (-1: none); without CS_MARK_ALL `xa_of` is the rank of the primary whose XA list the region joins, or -1.
  * `line_off`: a read's lines; a read with none gets the caller's unmapped record.  `cigar_regs` / `cigar_src`: the regions with
- * line >= 0 or xa_of >= 0 in rank order -- the input of cs_regions_cigar as it is -- and each one's index into marks.  Still the
- * caller's: SAM text, the -5 reordering (mem_reorder_primary5), paired-end, and the MAPQ formula of mapq_coef_len <= 0.  Errors, in this
+ * line >= 0 or xa_of >= 0 in rank order -- the input of cs_regions_cigar as it is -- and each one's index into marks.  The SAM text is
+ * cs_regions_sam's, below.  Still the caller's: the -5 reordering (mem_reorder_primary5), paired-end, XR (-V), and the MAPQ formula of mapq_coef_len <= 0.  Errors, in this
  * order: a NULL `a`, `par`, `regs` or `out`, or unknown flag bits CS_EINVAL; NULL arrays where the counts say there are entries
  * CS_EINVAL; mapq_coef_len <= 0 or other bad parameters CS_EINVAL; an aligner created with device -1 CS_EDEVICE; 2^32 regions or reads
  * or more, or mapq_coef_len above 131,072, CS_ERANGE; a read with 65,536 regions or more, or a region spanning more than 131,072 bases,
@@ -561,6 +561,41 @@ typedef struct { uint64_t reads, regions, lines, xa_members, cigar_regions, ligh
 void cs_mark_params_default(cs_mark_params_t *p);
 int  cs_regions_mark(cs_aligner_t *a, const cs_mark_params_t *par, const cs_aln_result_t *regs, const uint64_t *read_offsets, int64_t id_base, uint32_t flags, cs_mark_result_t *out);
 int  cs_mark_stats(const cs_aligner_t *a, cs_mark_stats_t *st);
+/* Behind marking and the CIGAR stage, on the GPU: the SAM text itself -- mem_aln2sam (comp_seed.cpp:904-1024), the string part of
+ * mem_gen_alt (:1056-1067) and the unmapped record of mem_reg2sam (:1107-1117), single-end as the reference runs them.  `marks`:
+ * cs_regions_mark's result; `reg_off`: the reg_off that call was given (the marks' CSR); `alns`: cs_regions_cigar's result over
+ * marks->cigar_regs, one entry per entry of cigar_regs; `bases` / `read_offsets`: the reads (ASCII or codes); `quals`: their qualities at the
+ * same offsets, or NULL ('*'); `names` / `name_off` and `comments` / `comment_off` (-C; both NULL: none): CSR byte arrays of n_reads + 1
+ * offsets.  Host arrays in; host arrays owned by the aligner out, valid until its next cs_regions_sam: text[text_off[r], text_off[r + 1])
+ * holds the record or records of read r, each ending in '\n', in the reference's order, so that the text as a whole is the body of the
+ * reference's output.  Contig names are the aligner's <prefix>.ann's.  -a / -M / -q are in the marks already; -Y is CS_SAM_SOFTCLIP.  What
+ * is reproduced: FLAG is the mark's (plus 0x4 on the unmapped record); a clip is written H on a line that is not the read's first unless
+ * -Y is given or the region is ALT, and SEQ / QUAL are cut there (the leading clip cuts the read's end on the reverse strand); a real
+ * secondary (secondary >= 0; NOT a -M supplementary, which only prints 0x100) gets "*\t*" and neither SA nor pa; NM and MD, AS, XS when
+ * xs >= 0, RG; SA:Z over the read's other lines that are not real secondaries (the CIGAR as cs_regions_cigar gave it, the capped MAPQ);
+ * pa:f:%.3f with glibc's digits; XA:Z over the regions whose xa_of names the line's rank; the comment; a read without lines gets the
+ * unmapped record.  A region whose xa_of names a rank without a line is listed nowhere, as in the reference.  Still the caller's: the -5
+ * reordering (mem_reorder_primary5), paired-end, XR (-V), and the MAPQ formula of mapq_coef_len <= 0.  Errors, in this order: a NULL `a`,
+ * `par`, `marks`, `alns` or `out`, or unknown flag bits CS_EINVAL; NULL arrays where the counts say there are entries CS_EINVAL;
+ * alns->n_regs != marks->cigar_regs.n_regs CS_EINVAL; one of comments / comment_off without the other CS_EINVAL; an aligner created with
+ * device -1 CS_EDEVICE; 2^32 reads, regions or lines or more CS_ERANGE; inconsistent input -- offsets that are not CSR arrays from 0 to
+ * their counts, a read of 65,536 bases or more, lines that are not numbered 0, 1, 2 ... in rank order, an xa_of outside the read,
+ * cigar_src that does not name exactly the marks with a line or an XA membership, an alignment without contig, position or CIGAR, with a
+ * CIGAR or MD outside the arrays, op codes above 4 or clips longer than the read -- CS_EINVAL, found by a checking kernel before any
+ * kernel follows an offset.  After any error the aligner is usable for the next call.
+ * cs_sam_header: the @SQ lines (AH:* on ALT contigs) and, where `rg_line` is given as -R takes it ("@RG\tID:x", the tab written as a
+ * backslash and a t, unescaped as bwa_set_rg does), that line; host only, legal on an aligner of device -1.  Writes at most `cap` bytes to
+ * `buf` (no NUL) and the full length to `*need`; CS_ERANGE when cap is too small (buf may be NULL with cap 0 to ask for the length). */
+typedef struct { uint32_t flags; const char *rg_id; /* the ID of -R's line (bwa_rg_id); NULL or "": no RG tag */ } cs_sam_params_t;
+#define CS_SAM_SOFTCLIP 1u       /* -Y: clips stay S on every line */
+#define CS_SAM_WAVE_ONLY 0x100u  /* accepted, changes nothing: the lane-per-read path it switched off lost its measurement and is gone; every record is a wave's */
+typedef struct { int64_t n_reads; uint64_t n_lines, n_bytes; const uint64_t *text_off /* n_reads + 1 */; const char *text; } cs_sam_result_t;
+typedef struct { uint64_t reads, lines, unmapped, bytes, xa_entries, sa_entries, launches; double kernel_ms; } cs_sam_stats_t;
+int  cs_regions_sam(cs_aligner_t *a, const cs_sam_params_t *par, const cs_mark_result_t *marks, const uint64_t *reg_off, const cs_cigar_result_t *alns,
+                    const uint8_t *bases, const uint64_t *read_offsets, const uint8_t *quals, const char *names, const uint64_t *name_off,
+                    const char *comments, const uint64_t *comment_off, cs_sam_result_t *out);
+int  cs_sam_header(const cs_aligner_t *a, const char *rg_line /* may be NULL */, char *buf, size_t cap, size_t *need);
+int  cs_sam_stats(const cs_aligner_t *a, cs_sam_stats_t *st);
 
 /* ---- the result of the LAST device-variant call, without moving it: an order-sensitive 64-bit digest per array
  *      (sum over the array's 64-bit words w[i] of splitmix64(w[i] + i * 0x9E3779B97F4A7C15), mod 2^64), so that two runs over

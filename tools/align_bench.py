@@ -10,7 +10,9 @@ Behind dedup_regions: "regions -> CIGAR", cs_regions_cigar over the de-duplicate
 reads, with the device span and the job counts of cs_cigar_stats; nothing in the reference is timed separately to compare it with.
 Behind that: "regions -> marks", cs_regions_mark over the de-duplicated regions in default mode and under CS_MARK_ALL, and cs_regions_cigar
 three ways -- over the marks' cigar_regs in either mode, and over all regions as a caller without marks has to -- each as the median, the
-minimum and the maximum of seven calls after a warm-up one, ms per million reads.
+minimum and the maximum of seven calls after a warm-up one, ms per million reads.  Behind that, per mode: "marks + CIGAR -> SAM text",
+cs_regions_sam over those marks and their alignments, timed the same way, with the device span, the bytes per read and the counts of
+cs_sam_stats.
 usage: align_bench.py [reads] [--synth-mbp M]"""
 import gzip, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -115,6 +117,9 @@ def run(n=200000, synth_mbp=0.0):
             ta = time.perf_counter(); r = fn(); ts.append((time.perf_counter() - ta) * 1e3 * 1e6 / n)
         return r, {"runs": MARK_RUNS, "median_ms_per_million_reads": float(np.median(ts)), "min": min(ts), "max": max(ts)}
     d_off, d_regs = np.array(d["reg_off"]), np.array(d["regs"])
+    name_list = [b"%d" % (k + 1) for k in range(n)]
+    name_off = np.zeros(n + 1, np.uint64); name_off[1:] = np.cumsum([len(x) for x in name_list])
+    names = (np.frombuffer(b"".join(name_list), np.uint8), name_off)
     for label, mflags in (("default", 0), ("CS_MARK_ALL", ca.MARK_ALL)):
         ms0 = al.mark_stats(); mk, tm = timed(lambda: al.regions_mark(d_off, d_regs, off, flags=mflags)); ms1 = al.mark_stats()
         _, tcg = timed(lambda: al.regions_cigar(mk["cigar_reg_off"], mk["cigar_regs"], bases, off))
@@ -123,6 +128,13 @@ def run(n=200000, synth_mbp=0.0):
                                                     cigar_regions=int(mk["cigar_regs"].size), light_reads=int(md["light_reads"]), wave_reads=int(md["wave_reads"]), hbm_reads=int(md["hbm_reads"]),
                                                     launches=int(md["launches"]), note="host arrays in and out, the binding's copies of the result included")
         out["marked regions -> CIGAR (%s)" % label] = dict(tcg, regions=int(mk["cigar_regs"].size))
+        # the SAM text of the batch (cs_regions_sam) from these marks and their alignments: names are the reads' numbers, no qualities
+        cgm = al.regions_cigar(mk["cigar_reg_off"], mk["cigar_regs"], bases, off)
+        ss0 = al.sam_stats(); (_, text), tsam = timed(lambda: al.regions_sam(mk, cgm, bases, off, names, reg_off=d_off)); ss1 = al.sam_stats()
+        sd = {k: (ss1[k] - ss0[k]) / (MARK_RUNS + 1) for k in ss1}
+        out["marks + CIGAR -> SAM text (%s)" % label] = dict(tsam, device_span_ms=sd["kernel_ms"], bytes=len(text), bytes_per_read=len(text) / n, lines=int(sd["lines"]), unmapped=int(sd["unmapped"]),
+                                                             xa_entries=int(sd["xa_entries"]), sa_entries=int(sd["sa_entries"]), launches=int(sd["launches"]),
+                                                             note="host arrays in and out, the binding's copy of the text included")
     _, tca = timed(lambda: al.regions_cigar(d_off, d_regs, bases, off))
     out["all regions -> CIGAR"] = dict(tca, regions=int(d_regs.size), note="what a caller without cs_regions_mark has to do")
     for name, a, b in (("seed (host call)", t0, t1), ("chain", t1, t2), ("chain_filter", t2, t3), ("extend_chains", t3, t4), ("dedup_regions", t4, t5)):
