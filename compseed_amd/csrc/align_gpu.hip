@@ -13,7 +13,11 @@
 //   apply_kernel        a side's results into the regions: clipped or to the end of the read, truesc, the band used; retry list
 //   seedcov_kernel, purge_kernel   comp_seed.cpp:1758-1766 and :2141-2232 (one thread per read walks its regions in extension order)
 // Same results as the host driver it replaces, field by field (tests/test_gpu_align.py against the reference's own regions).
+// The bodies are align_scan.hpp's, which tests/cpp/align_scan_check.cpp runs in this order on the CPU, one lane and 8 / 64 lanes in
+// lockstep; a kernel here is a grid-stride, wave-stride or block-stride loop around a body and does the atomics and the list appends for
+// what the body returns.  purge_big_kernel alone keeps its walk here (eight waves around a workgroup barrier: not run on the CPU).
 #include "dev_stage.hpp"
+#include "align_scan.hpp"
 #include "compact.hpp"
 
 #include <algorithm>
@@ -26,150 +30,26 @@
 #include <hip/hip_runtime.h>
 
 namespace csa {
-constexpr int32_t UNSET = -99;            // the reference's H0_ (mapping/macro.h:44): a coordinate that has not been set yet
-
-// The counter words: pairs on the left / right list, pairs sent back for the wider band, chains whose first seed lies outside the reference,
-// purged regions, chains on the list of region_big_kernel, reads on the list of purge_big_kernel and that kernel's ticket.  Two words serve
-// twice in cs_extend_chains_device: its checks count into the first two before the core clears the block, and the long chains' count has
-// served when the compaction writes the number of live regions in its place.
-enum { C_LEFT, C_RIGHT, C_RETRY, C_BAD_CHAIN, C_PURGED, C_BIG_CHAINS, C_BIG_READS, C_TICKET, C_COUNT,
-       C_REFUSED = C_LEFT, C_N_BASES = C_RIGHT, C_LIVE = C_BIG_CHAINS };
-
-struct Args {
-	const uint64_t *chain_off, *cseed_off, *read_off; const cs_chain_t *chains; const cs_seed_t *cseeds; const int32_t *score; const uint8_t *bases;
-	int64_t n_reads, n_chains, n_seeds, l_pac; uint64_t n_bases;
-	const uint8_t *pac; const int64_t *ctg_off; const int32_t *ctg_len; int32_t n_ctg;
-	cs_aln_params_t o;
-	uint32_t *chain_read; int64_t *w0; uint64_t *wlen2, *tb0;   // per chain: window start, 2 x length (scanned into tb0)
-	uint8_t *qbuf, *tbuf; uint32_t *ord; cs_alnreg_t *regs; uint32_t *reg_ci;
-	cs_ext_pair_t *lp, *rp;
-	int32_t small_chain, light_max, purge_cap;   // SMALL_CHAIN / 64 / PURGE_CAP unless cs_aln_params_t.flags says otherwise (A/B tests)
-	uint32_t *big, *big_reads;             // chains of more than SMALL_CHAIN seeds / reads of more than 64 regions: lists for the *_big kernels
-	unsigned long long *ctr;               // the C_* words
-};
-
-__device__ __forceinline__ int affordable_gap(const cs_aln_params_t &o, int qlen) // cal_max_gap (comp_seed.cpp:415-421)
-{
-	const int l_del = (int)((double)(qlen * o.a - o.o_del) / o.e_del + 1.), l_ins = (int)((double)(qlen * o.a - o.o_ins) / o.e_ins + 1.);
-	int l = l_del > l_ins ? l_del : l_ins;
-	l = l > 1 ? l : 1;
-	return l < (o.w << 1) ? l : (o.w << 1);
-}
+using csdd::wexcl_sum; using csdd::wbcast64;
 
 __global__ void chain_read_kernel(const Args A)
 {
-	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < A.n_reads; r += (int64_t)gridDim.x * blockDim.x)
-		for (uint64_t ci = A.chain_off[r]; ci < A.chain_off[r + 1]; ++ci) A.chain_read[ci] = (uint32_t)r;
+	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < A.n_reads; r += (int64_t)gridDim.x * blockDim.x) chain_read(A, r);
 }
 __global__ void query_kernel(const Args A)
 {
-	for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < A.n_bases; b += (uint64_t)gridDim.x * blockDim.x) {
-		// the read of base b: binary search in the offsets
-		int64_t lo = 0, hi = A.n_reads;
-		while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (A.read_off[mid] <= b) lo = mid; else hi = mid; }
-		const uint64_t b0 = A.read_off[lo], len = A.read_off[lo + 1] - b0, j = b - b0;
-		const uint8_t c = cs_base_code_(A.bases[b]);
-		A.qbuf[b] = c; A.qbuf[A.n_bases + b0 + (len - 1 - j)] = c;
-	}
+	for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < A.n_bases; b += (uint64_t)gridDim.x * blockDim.x) query_codes(A, b);
 }
 __global__ void window_kernel(const Args A)
 {
-	const cs_aln_params_t &o = A.o;
-	for (int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ci < A.n_chains; ci += (int64_t)gridDim.x * blockDim.x) {
-		const cs_seed_t *sd = A.cseeds + A.cseed_off[ci];
-		const int ns = (int)(A.cseed_off[ci + 1] - A.cseed_off[ci]);
-		A.w0[ci] = 0; A.wlen2[ci] = 0;
-		if (ns <= 0) continue;
-		const uint32_t r = A.chain_read[ci];
-		const int l_query = (int)(A.read_off[r + 1] - A.read_off[r]);
-		const int64_t l_pac = A.l_pac;
-		int64_t w0 = l_pac << 1, w1 = 0;
-		for (int i = 0; i < ns; ++i) {
-			const cs_seed_t s = sd[i];
-			const int64_t b = s.rbeg - (s.qbeg + affordable_gap(o, s.qbeg));
-			const int tail = l_query - s.qbeg - s.len;
-			const int64_t e = s.rbeg + s.len + (tail + affordable_gap(o, tail));
-			w0 = w0 < b ? w0 : b; w1 = w1 > e ? w1 : e;
-		}
-		w0 = w0 > 0 ? w0 : 0; w1 = w1 < (l_pac << 1) ? w1 : (l_pac << 1);
-		const int64_t mid = sd[0].rbeg;
-		if (w0 < l_pac && l_pac < w1) { if (mid < l_pac) w1 = l_pac; else w0 = l_pac; } // never across the strands
-		// clip to the contig of the first seed (bns_fetch_seq, bntseq.c:426-451)
-		const bool rev = mid >= l_pac;
-		const int64_t mid_f = rev ? (l_pac << 1) - 1 - mid : mid;
-		int lo = 0, hi = A.n_ctg;                                         // last contig whose offset is <= mid_f
-		while (hi - lo > 1) { const int m = (lo + hi) >> 1; if (A.ctg_off[m] <= mid_f) lo = m; else hi = m; }
-		if (mid_f < 0 || mid_f >= l_pac || !(w0 <= mid && mid < w1)) { atomicAdd(A.ctr + C_BAD_CHAIN, 1ull); continue; }
-		int64_t far_b = A.ctg_off[lo], far_e = far_b + A.ctg_len[lo];
-		if (rev) { const int64_t x = far_b; far_b = (l_pac << 1) - far_e; far_e = (l_pac << 1) - x; }
-		w0 = w0 > far_b ? w0 : far_b; w1 = w1 < far_e ? w1 : far_e;
-		A.w0[ci] = w0; A.wlen2[ci] = w1 > w0 ? (uint64_t)(w1 - w0) * 2 : 0;
-	}
+	for (int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ci < A.n_chains; ci += (int64_t)gridDim.x * blockDim.x)
+		if (!chain_window(A, ci)) atomicAdd(A.ctr + C_BAD_CHAIN, 1ull);
 }
-// one wave per chain: the window's bases, forward strand as stored, reverse strand complemented from the mirror position; then reversed
-__global__ void fill_kernel(const Args A)
+__global__ void fill_kernel(const Args A) // one wave per chain
 {
 	const int lane = threadIdx.x & 63;
 	const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-	for (int64_t ci = wave; ci < A.n_chains; ci += n_waves) {
-		const int64_t L = (int64_t)(A.wlen2[ci] >> 1), w0 = A.w0[ci];
-		uint8_t *t = A.tbuf + A.tb0[ci];
-		for (int64_t k = lane; k < L; k += 64) {
-			const int64_t p = w0 + k;
-			const uint8_t b = (uint8_t)(p < A.l_pac ? cs_pac_base_(A.pac, p) : 3 - cs_pac_base_(A.pac, (A.l_pac << 1) - 1 - p));
-			t[k] = b; t[L + (L - 1 - k)] = b;
-		}
-	}
-}
-// ---- regions.  A chain's seeds are extended in the order of their scores, highest first, later ones first among equals (comp_seed.cpp:1406-1411);
-// that order is total, so a seed's place is the number of seeds that rank before it and every seed can be placed on its own.
-constexpr int SMALL_CHAIN = 8;
-__device__ __forceinline__ int seed_rank(const cs_seed_t *sd, const int32_t *sc, int ns, int i)
-{
-	const int si = sc ? sc[i] : sd[i].len;
-	int rk = 0;
-	for (int y = 0; y < ns; ++y) { const int sy = sc ? sc[y] : sd[y].len; rk += (sy > si || (sy == si && y > i)) ? 1 : 0; }
-	return rk;
-}
-struct ChainCtx { int64_t ci, w0, L, tb0; uint64_t s0, rb0; int32_t l_query, rid, chain; float frac_rep; };
-__device__ __forceinline__ ChainCtx chain_ctx(const Args &A, int64_t ci)
-{
-	ChainCtx X;
-	const cs_chain_t c = A.chains[ci];
-	const uint32_t r = A.chain_read[ci];
-	X.ci = ci; X.s0 = A.cseed_off[ci]; X.rb0 = A.read_off[r]; X.l_query = (int32_t)(A.read_off[r + 1] - X.rb0);
-	X.w0 = A.w0[ci]; X.L = (int64_t)(A.wlen2[ci] >> 1); X.tb0 = (int64_t)A.tb0[ci];
-	X.rid = c.rid; X.frac_rep = c.frac_rep; X.chain = (int32_t)(ci - (int64_t)A.chain_off[r]);
-	return X;
-}
-// seed i of the chain, k-th in the order of extension: its region and its (at most two) pairs, at the slots the caller reserved
-__device__ __forceinline__ void emit_region(const Args &A, const ChainCtx &X, const cs_seed_t &s, int i, int k, bool left, bool right, uint64_t lslot, uint64_t rslot)
-{
-	const cs_aln_params_t &o = A.o;
-	const uint64_t g = X.s0 + (uint64_t)k;
-	cs_alnreg_t a; memset(&a, 0, sizeof a);
-	a.w = o.w; a.score = a.truesc = -1; a.rid = X.rid; a.frac_rep = X.frac_rep; a.seedlen0 = s.len; a.chain = X.chain;
-	a.rb = a.re = UNSET; a.qb = a.qe = UNSET;
-	if (left) { // reversed read prefix against the reversed window in front of the seed
-		const int64_t tl = s.rbeg - X.w0;
-		const cs_ext_pair_t p = {(uint64_t)(A.n_bases + X.rb0 + (uint64_t)(X.l_query - s.qbeg)), (uint64_t)(X.tb0 + X.L + (X.L - tl)), s.qbeg, (int32_t)tl, s.len * o.a, (int32_t)g};
-		A.lp[lslot] = p;
-		a.qb = s.qbeg; a.rb = s.rbeg;
-	} else { a.score = a.truesc = s.len * o.a; a.qb = 0; a.rb = s.rbeg; }
-	if (right) { // the rest of the read against the window behind the seed
-		const int qe = s.qbeg + s.len; const int64_t re = s.rbeg + s.len - X.w0;
-		const cs_ext_pair_t p = {(uint64_t)(X.rb0 + (uint64_t)qe), (uint64_t)(X.tb0 + re), X.l_query - qe, (int32_t)(X.L - re), 0, (int32_t)g};
-		A.rp[rslot] = p;
-		a.qe = qe; a.re = X.w0 + re;
-	} else { a.qe = X.l_query; a.re = s.rbeg + s.len; }
-	A.regs[g] = a; A.reg_ci[g] = (uint32_t)X.ci; A.ord[g] = (uint32_t)i;
-}
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, int lane, uint32_t &total)
-{
-	uint32_t x = v;
-	for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d); if (lane >= d) x += y; }
-	total = __shfl(x, 63);
-	return x - v;
+	for (int64_t ci = wave; ci < A.n_chains; ci += n_waves) fill_window<64>(A, ci, lane);
 }
 // a chain per lane for the chains of up to SMALL_CHAIN seeds (nearly all); the pair slots of a wave's 64 chains come from one atomic per
 // side (one per pair made the two counters the kernel's clock); longer chains go on a list for region_big_kernel
@@ -185,56 +65,27 @@ __global__ void region_kernel(const Args A)
 			const uint64_t s0 = A.cseed_off[ci];
 			ns = (int)(A.cseed_off[ci + 1] - s0);
 			if (ns > A.small_chain) A.big[atomicAdd(A.ctr + C_BIG_CHAINS, 1ull)] = (uint32_t)ci;
-			else if (ns > 0) {
-				mine = true; X = chain_ctx(A, ci); sd = A.cseeds + s0;
-				for (int i = 0; i < ns; ++i) { const cs_seed_t s = sd[i]; nl += s.qbeg != 0; nr += s.qbeg + s.len != X.l_query; }
-			}
+			else if (ns > 0) { mine = true; X = chain_ctx(A, ci); sd = A.cseeds + s0; count_pairs(X, sd, ns, nl, nr); }
 		}
 		uint32_t tl, tr;
-		const uint32_t el = wave_excl_scan(nl, lane, tl), er = wave_excl_scan(nr, lane, tr);
+		const uint32_t el = wexcl_sum<64>(nl, lane, tl), er = wexcl_sum<64>(nr, lane, tr);
 		unsigned long long bl = 0, br = 0;
 		if (lane == 0) { if (tl) bl = atomicAdd(A.ctr + C_LEFT, (unsigned long long)tl); if (tr) br = atomicAdd(A.ctr + C_RIGHT, (unsigned long long)tr); }
-		bl = __shfl(bl, 0); br = __shfl(br, 0);
-		if (mine) {
-			uint64_t ls = bl + el, rs = br + er;
-			const int32_t *sc = A.score ? A.score + X.s0 : nullptr;
-			for (int i = 0; i < ns; ++i) {
-				const cs_seed_t s = sd[i];
-				const bool left = s.qbeg != 0, right = s.qbeg + s.len != X.l_query;
-				emit_region(A, X, s, i, seed_rank(sd, sc, ns, i), left, right, ls, rs);
-				ls += left; rs += right;
-			}
-		}
+		bl = wbcast64<64>(bl, 0); br = wbcast64<64>(br, 0);
+		if (mine) emit_chain(A, X, sd, ns, bl + el, br + er);
 	}
 }
-// one wave per long chain (a repeat's hundreds of seeds on one diagonal band): a seed per lane, 64 at a time
-__global__ void region_big_kernel(const Args A)
+__global__ void region_big_kernel(const Args A) // one wave per long chain
 {
 	const int lane = threadIdx.x & 63;
-	const uint64_t lt = (1ull << lane) - 1ull;
 	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
 	const uint64_t n_big = A.ctr[C_BIG_CHAINS];
-	for (uint64_t e = wave; e < n_big; e += n_waves) {
-		const int64_t ci = (int64_t)A.big[e];
-		const ChainCtx X = chain_ctx(A, ci);
-		const cs_seed_t *sd = A.cseeds + X.s0;
-		const int32_t *sc = A.score ? A.score + X.s0 : nullptr;
-		const int ns = (int)(A.cseed_off[ci + 1] - X.s0);
-		for (int i0 = 0; i0 < ns; i0 += 64) {
-			const int i = i0 + lane;
-			cs_seed_t s = {0, 0, 0}; int k = 0; bool left = false, right = false;
-			if (i < ns) { s = sd[i]; k = seed_rank(sd, sc, ns, i); left = s.qbeg != 0; right = s.qbeg + s.len != X.l_query; }
-			const uint64_t ml = __ballot(left), mr = __ballot(right);
-			unsigned long long bl = 0, br = 0;
-			if (lane == 0) { if (ml) bl = atomicAdd(A.ctr + C_LEFT, (unsigned long long)__popcll(ml)); if (mr) br = atomicAdd(A.ctr + C_RIGHT, (unsigned long long)__popcll(mr)); }
-			bl = __shfl(bl, 0); br = __shfl(br, 0);
-			if (i < ns) emit_region(A, X, s, i, k, left, right, bl + (uint64_t)__popcll(ml & lt), br + (uint64_t)__popcll(mr & lt));
-		}
-	}
+	for (uint64_t e = wave; e < n_big; e += n_waves)
+		chain_regions<64>(A, (int64_t)A.big[e], lane, [&](int c, unsigned n) { return atomicAdd(A.ctr + c, (unsigned long long)n); });
 }
-__global__ void right_h0_kernel(cs_ext_pair_t *rp, uint64_t n, const cs_alnreg_t *regs) // the right side starts from what the left side reached (comp_seed.cpp:1917-1922)
+__global__ void right_h0_kernel(cs_ext_pair_t *rp, uint64_t n, const cs_alnreg_t *regs)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) rp[i].h0 = regs[(uint32_t)rp[i].reserved].score;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) right_h0(rp[i], regs);
 }
 // a side's results into the regions; pairs whose alignment may have been cut by the band go to `retry` (same pair, next try)
 __global__ void apply_kernel(const Args A, const cs_ext_pair_t *pairs, const cs_ext_result_t *res, uint64_t n, int w, int attempt, int is_left, int pen_clip, cs_ext_pair_t *retry)
@@ -244,72 +95,17 @@ __global__ void apply_kernel(const Args A, const cs_ext_pair_t *pairs, const cs_
 		const uint32_t g = (uint32_t)pr.reserved;
 		cs_alnreg_t a = A.regs[g];
 		const cs_ext_result_t x = res[i];
-		const int prev = a.score;
-		a.score = x.score;
-		// settled unless the band may have cut the alignment: same score as before, the path stayed within 3/4 of the band, or no try left
-		if (a.score == prev || x.max_off < (w >> 1) + (w >> 2) || attempt == 1) {
-			const bool local = x.gscore <= 0 || x.gscore <= a.score - pen_clip;   // clipping beats reaching the end of the read
-			if (is_left) {
-				if (local) { a.qb -= x.qle; a.rb -= x.tle; a.truesc = a.score; }
-				else { a.qb = 0; a.rb -= x.gtle; a.truesc = x.gscore; }
-			} else {
-				if (local) { a.qe += x.qle; a.re += x.tle; a.truesc += a.score - pr.h0; }
-				else { const uint32_t r = A.chain_read[A.reg_ci[g]]; a.qe = (int32_t)(A.read_off[r + 1] - A.read_off[r]); a.re += x.gtle; a.truesc += x.gscore - pr.h0; }
-			}
-			a.w = a.w > w ? a.w : w;
-		} else retry[atomicAdd(A.ctr + C_RETRY, 1ull)] = pr;
+		if (apply_result(A, a, pr, x, w, attempt, is_left, pen_clip)) retry[atomicAdd(A.ctr + C_RETRY, 1ull)] = pr;
 		A.regs[g] = a;
 	}
 }
-__global__ void seedcov_kernel(const Args A) // the chain's seeds that lie inside the final region on both axes (comp_seed.cpp:1758-1766)
+__global__ void seedcov_kernel(const Args A)
 {
-	for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < A.n_seeds; g += (int64_t)gridDim.x * blockDim.x) {
-		const uint32_t ci = A.reg_ci[g];
-		const cs_seed_t *sd = A.cseeds + A.cseed_off[ci];
-		const int ns = (int)(A.cseed_off[ci + 1] - A.cseed_off[ci]);
-		cs_alnreg_t a = A.regs[g];
-		int cov = 0;
-		for (int i = 0; i < ns; ++i) { const cs_seed_t t = sd[i]; if (t.qbeg >= a.qb && t.qbeg + t.len <= a.qe && t.rbeg >= a.rb && t.rbeg + t.len <= a.re) cov += t.len; }
-		A.regs[g].seedcov = cov;
-	}
+	for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < A.n_seeds; g += (int64_t)gridDim.x * blockDim.x) seed_coverage(A, g);
 }
-// comp_seed.cpp:2141-2232: walking a read's seeds in the order they were extended, a seed that lies inside an earlier, surviving region of
-// the read, is not much longer than that region's seed and sits within the band of its diagonal at either end is redundant -- unless a
-// higher-ranked seed of its chain that is still in play overlaps it on another diagonal.  Its region is marked qb = qe = -1.
-// The walk over a read's regions is sequential (a region's fate decides about the later ones), but both tests are "is there one among
-// the earlier ...": the lanes of a wave hold the earlier regions / the higher-ranked seeds and a ballot answers.
-struct PReg { int64_t rb, re; int32_t qb, qe, seedlen0, w; };
-template <class GapF> // gap_of(x) = affordable_gap(o, x); x is a distance inside the read here, 0 .. l_query
-__device__ __forceinline__ bool purge_around(const cs_seed_t &s, const PReg &p, int l_query, GapF gap_of)
-{
-	if (s.rbeg < p.rb || s.rbeg + s.len > p.re || s.qbeg < p.qb || s.qbeg + s.len > p.qe) return false;
-	if (s.len - p.seedlen0 > .1 * l_query) return false;
-	int qd = s.qbeg - p.qb; int64_t rd = s.rbeg - p.rb;
-	int gap = gap_of((int)(qd < rd ? qd : rd)), w = gap < p.w ? gap : p.w;
-	if (qd - rd < w && rd - qd < w) return true;
-	qd = p.qe - (s.qbeg + s.len); rd = p.re - (s.rbeg + s.len);
-	gap = gap_of((int)(qd < rd ? qd : rd)); w = gap < p.w ? gap : p.w;
-	return qd - rd < w && rd - qd < w;
-}
-__device__ __forceinline__ bool purge_rival(const cs_seed_t &s, const cs_seed_t &t) // t: a seed ranked above s in its chain
-{
-	if (t.len < s.len * .95) return false;
-	if (s.qbeg <= t.qbeg && s.qbeg + s.len - t.qbeg >= s.len >> 2 && t.qbeg - s.qbeg != t.rbeg - s.rbeg) return true;
-	return t.qbeg <= s.qbeg && t.qbeg + t.len - s.qbeg >= s.len >> 2 && s.qbeg - t.qbeg != s.rbeg - t.rbeg;
-}
-__device__ __forceinline__ void purge_load(const Args &A, uint64_t g0, uint64_t g, PReg &p, cs_seed_t &s, int &first)
-{
-	const uint64_t s0 = A.cseed_off[A.reg_ci[g]];
-	first = (int)(s0 - g0);                                         // the read's regions [first, g) are the higher-ranked seeds of g's chain
-	s = A.cseeds[s0 + A.ord[g]];
-	const cs_alnreg_t a = A.regs[g];
-	p.rb = a.rb; p.re = a.re; p.qb = a.qb; p.qe = a.qe; p.seedlen0 = a.seedlen0; p.w = a.w;
-}
-// reads of up to 64 regions (all but a few in a thousand): a wave per read, a region per lane, everything in registers -- the seed in
-// question comes from its lane by a shuffle, which regions are still there is a mask.  Longer reads go on a list for purge_big_kernel.
+// reads of up to 64 regions: a wave per read.  Longer reads go on a list for purge_big_kernel.
 __global__ void purge_kernel(const Args A)
 {
-	const cs_aln_params_t &o = A.o;
 	const int lane = threadIdx.x & 63;
 	const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
 	unsigned long long my = 0;
@@ -317,67 +113,16 @@ __global__ void purge_kernel(const Args A)
 		const uint64_t g0 = A.cseed_off[A.chain_off[r]], g1 = A.cseed_off[A.chain_off[r + 1]];
 		if (g1 - g0 < 2) continue;                                  // (a read's first region has nothing in front of it)
 		if (g1 - g0 > (uint64_t)A.light_max) { if (lane == 0) A.big_reads[atomicAdd(A.ctr + C_BIG_READS, 1ull)] = (uint32_t)r; continue; }
-		const int G = (int)(g1 - g0), l_query = (int)(A.read_off[r + 1] - A.read_off[r]);
-		PReg p = {0, 0, 0, 0, 0, 0}; cs_seed_t s = {0, 0, 0}; int first = 0;
-		if (lane < G) purge_load(A, g0, g0 + (uint64_t)lane, p, s, first);
-		const uint64_t all = G == 64 ? ~0ull : (1ull << G) - 1ull;
-		uint64_t alive = all;
-		for (int g = 1; g < G; ++g) {
-			cs_seed_t sg; sg.rbeg = (int64_t)__shfl((long long)s.rbeg, g); sg.qbeg = __shfl(s.qbeg, g); sg.len = __shfl(s.len, g);
-			const int fg = __shfl(first, g);
-			const bool before = lane < g && ((alive >> lane) & 1ull);
-			if (__ballot(before && purge_around(sg, p, l_query, [&](int x) { return affordable_gap(o, x); })) == 0) continue;
-			if (__ballot(before && lane >= fg && purge_rival(sg, s)) != 0) continue;
-			alive &= ~(1ull << g);
-		}
-		const uint64_t gone = all & ~alive;
-		if ((gone >> lane) & 1ull) { A.regs[g0 + (uint64_t)lane].qb = -1; A.regs[g0 + (uint64_t)lane].qe = -1; }
-		if (lane == 0) my += (unsigned long long)__popcll(gone);
+		purge_read_regs<64>(A, r, lane, my);
 	}
 	if (lane == 0 && my) atomicAdd(A.ctr + C_PURGED, my);
-}
-// a read of any size straight from HBM (the fallback of purge_big_kernel): which regions are purged so far is a byte array that is read
-// around the L1 (volatile) -- lane 0 writes, the whole wave reads in the next step.  Every step is a chain of HBM round trips.
-__device__ void purge_read_global(const Args &A, int64_t r, uint8_t *pflag, int lane, unsigned long long &my)
-{
-	const cs_aln_params_t &o = A.o;
-	volatile uint8_t *pf = pflag;
-	const int l_query = (int)(A.read_off[r + 1] - A.read_off[r]);
-	const uint64_t g0 = A.cseed_off[A.chain_off[r]];
-	uint64_t g = g0;
-	for (uint64_t ci = A.chain_off[r]; ci < A.chain_off[r + 1]; ++ci) {
-		const uint64_t s0 = A.cseed_off[ci];
-		const cs_seed_t *sd = A.cseeds + s0;
-		const uint32_t *ord = A.ord + s0;
-		const int ns = (int)(A.cseed_off[ci + 1] - s0);
-		for (int k = 0; k < ns; ++k, ++g) {
-			const cs_seed_t s = sd[ord[k]];
-			bool around = false;
-			for (uint64_t base = g0; base < g && !around; base += 64) {
-				const uint64_t i = base + (uint64_t)lane;
-				bool hit = false;
-				if (i < g && !pf[i]) { const cs_alnreg_t a = A.regs[i]; const PReg p = {a.rb, a.re, a.qb, a.qe, a.seedlen0, a.w}; hit = purge_around(s, p, l_query, [&](int x) { return affordable_gap(o, x); }); }
-				around = __ballot(hit) != 0;
-			}
-			if (!around) continue;
-			bool rival = false;
-			for (int base = 0; base < k && !rival; base += 64) {
-				const int v = base + lane;
-				const bool hit = v < k && !pf[s0 + (uint64_t)v] && purge_rival(s, sd[ord[v]]);
-				rival = __ballot(hit) != 0;
-			}
-			if (rival) continue;
-			if (lane == 0) { pf[g] = 1; A.regs[g].qb = -1; A.regs[g].qe = -1; ++my; }
-			__threadfence();
-		}
-	}
 }
 // the reads with more than 64 regions (reads inside repeats: hundreds to thousands of regions, and the walk is quadratic): a workgroup of eight
 // waves per read, the read's regions and seeds staged in the LDS -- a step of the walk costs LDS round trips instead of HBM ones, 512 earlier
 // regions are looked at per round, the affordable gap (two divisions in double precision) comes from a table over the read's length, both
 // tests of a step are answered with ONE barrier (every wave casts its two votes, double-buffered), and the reads are handed out by a ticket
-// counter (a few reads of 2,000 regions are most of the work).  All 160 KB of a CU's LDS: one read per CU at a time.
-constexpr int PURGE_CAP = 3000, PURGE_GAPS = 1024;
+// counter (a few reads of 2,000 regions are most of the work).  All 160 KB of a CU's LDS: one read per CU at a time.  A read beyond
+// PURGE_CAP regions is the first wave's, from HBM (purge_read_mem).  This walk is the one the CPU program does not run (align_scan.hpp).
 #ifndef CS_PURGE_THREADS
 #define CS_PURGE_THREADS 512
 #endif
@@ -404,7 +149,7 @@ __global__ __launch_bounds__(PB) void purge_big_kernel(const Args A, uint8_t *pf
 		if (e >= n_big) break;
 		const int64_t r = (int64_t)A.big_reads[e];
 		const uint64_t g0 = A.cseed_off[A.chain_off[r]], g1 = A.cseed_off[A.chain_off[r + 1]];
-		if (g1 - g0 > (uint64_t)A.purge_cap) { if (tid < 64) purge_read_global(A, r, pflag, lane, my); continue; }
+		if (g1 - g0 > (uint64_t)A.purge_cap) { if (tid < 64) purge_read_mem<64>(A, r, pflag, lane, my); continue; }
 		const int G = (int)(g1 - g0), l_query = (int)(A.read_off[r + 1] - A.read_off[r]);
 		auto gap_of = [&](int x) { return (unsigned)x < (unsigned)PURGE_GAPS ? l_gap[x] : affordable_gap(o, x); };
 		for (int i = tid; i < G; i += PB) { PReg p; cs_seed_t s; int first; purge_load(A, g0, g0 + (uint64_t)i, p, s, first); l_reg[i] = p; l_seed[i] = s; l_first[i] = first; l_alive[i] = 1; }
@@ -428,27 +173,15 @@ __global__ __launch_bounds__(PB) void purge_big_kernel(const Args A, uint8_t *pf
 	if (lane == 0 && my) atomicAdd(A.ctr + C_PURGED, my);
 }
 
-// ---- cs_extend_chains_device.  The caller's arrays are device memory that no host loop has seen, so what cs_extend_chains' host loops
-// refuse is counted by two kernels that follow no offset themselves -- a lane reads its own two entries of an offset array and compares
-// them with each other and with the host counts --, the host waits for the counter, and only then do reg_off_kernel and the kernels above
-// index one array by another (the way chain_filter_gpu.hip goes about it).  Beyond the host's conditions: read_off starts at 0 and does
-// not decrease (query_kernel's search and read lengths rest on it), a read with chains is shorter than MAX_READ_LEN, and both offset arrays
-// run from 0 to their count -- a chain no read owns has no chain_read entry, a seed no chain owns no region, and the kernels above read both.
-constexpr uint64_t MAX_READ_LEN = 65536;
-struct DevIn { const uint64_t *chain_off, *cseed_off, *read_off; const cs_chain_t *chains; int64_t n_reads; uint64_t n_chains, n_seeds; };
+// ---- cs_extend_chains_device: the host waits for the checks' counter, and only then do reg_off_kernel and the kernels above index one
+// array by another (the way chain_filter_gpu.hip goes about it)
 __global__ void check_reads_kernel(const DevIn D, unsigned long long *bad)
 {
-	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < D.n_reads; r += (int64_t)gridDim.x * blockDim.x) {
-		const uint64_t c0 = D.chain_off[r], c1 = D.chain_off[r + 1], b0 = D.read_off[r], b1 = D.read_off[r + 1];
-		if (c1 < c0 || c1 > D.n_chains || b1 < b0 || (r == 0 && (b0 != 0 || c0 != 0)) || (r == D.n_reads - 1 && c1 != D.n_chains) || (c1 > c0 && b1 - b0 >= MAX_READ_LEN)) atomicAdd(bad, 1ull);
-	}
+	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < D.n_reads; r += (int64_t)gridDim.x * blockDim.x) if (check_read(D, r)) atomicAdd(bad, 1ull);
 }
 __global__ void check_chains_kernel(const DevIn D, unsigned long long *bad)
 {
-	for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < D.n_chains; c += (uint64_t)gridDim.x * blockDim.x) {
-		const uint64_t s0 = D.cseed_off[c], s1 = D.cseed_off[c + 1];
-		if (s1 < s0 || s1 > D.n_seeds || (int64_t)(s1 - s0) != (int64_t)D.chains[c].n_seeds || (c == 0 && s0 != 0) || (c == D.n_chains - 1 && s1 != D.n_seeds)) atomicAdd(bad, 1ull);
-	}
+	for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < D.n_chains; c += (uint64_t)gridDim.x * blockDim.x) if (check_chain(D, c)) atomicAdd(bad, 1ull);
 }
 __global__ void reg_off_kernel(const DevIn D, uint64_t *reg_off) // a read's regions start where its first chain's seeds start; entry n_reads: the total
 {

@@ -5,8 +5,8 @@
 // on first use, its deletion and its statistics, the host's check of a batch without regions, and the download of a chain result.
 // Header-only.  A stage derives its state from cs_dev_stage and declares its device buffers as DevBuf<T> members of the type its kernels
 // read; it grows them with DevBuf::ensure, which frees before it allocates.  This is the HOST half only: what the kernels of
-// chain_filter_gpu.hip, cigar_gpu.hip and mark_gpu.hip loop over are the bodies of chain_filter_scan.hpp, cigar_scan.hpp and mark_scan.hpp,
-// on the lanes of wave_lanes.hpp and the alignment of band_align.hpp, which plain C++ programs run on the CPU (tests/cpp/).
+// chain_filter_gpu.hip, align_gpu.hip, cigar_gpu.hip and mark_gpu.hip loop over are the bodies of chain_filter_scan.hpp, align_scan.hpp,
+// cigar_scan.hpp and mark_scan.hpp, on the lanes of wave_lanes.hpp and the alignment of band_align.hpp, which plain C++ programs run on the CPU (tests/cpp/).
 #pragma once
 #include "cs_internal.hpp"
 

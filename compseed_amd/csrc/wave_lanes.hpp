@@ -1,5 +1,5 @@
-// wave_lanes.hpp -- the W lanes (1 or 64) that the per-read and per-job bodies of chain_filter_scan.hpp, dedup_scan.hpp, cigar_scan.hpp
-// and mark_scan.hpp are written for: shuffles and ballots of a wave, or nothing at all.  A plain C++ program may define the CSD_ macros before it includes
+// wave_lanes.hpp -- the W lanes (1 or 64) that the per-read and per-job bodies of chain_filter_scan.hpp, dedup_scan.hpp, cigar_scan.hpp,
+// mark_scan.hpp and align_scan.hpp are written for: shuffles and ballots of a wave, or nothing at all.  A plain C++ program may define the CSD_ macros before it includes
 // this header and run the W > 1 instantiations on lanes of its own (tests/cpp/lockstep.hpp: threads in lockstep); in device code they are
 // the wave's own, for a block of one wave.  With W = 1 every primitive is the identity, so a body written once for W lanes is the
 // sequential routine when one lane runs it.  The namespace stays csdd, where these primitives began (dedup_scan.hpp), so that no caller
@@ -39,12 +39,45 @@ template <int W> CS_HD inline int wbcast(int v, int src)
 	(void)src;
 	return v;
 }
+template <int W> CS_HD inline unsigned long long wbcast64(unsigned long long v, int src)
+{
+#ifdef CSD_SYNC
+	if constexpr (W > 1) return CSD_SHFL(v, src, W);
+#endif
+	(void)src;
+	return v;
+}
+// what lane 0 wrote to memory before it is what the other lanes read after it: a fence on the device, where the wave runs on by itself;
+// the emulation's lanes meet at CSD_SYNC's barrier (no macro of its own: a program's lane macros stay the five above)
+template <int W> CS_HD inline void wfence()
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	if constexpr (W > 1) __threadfence();
+#elif defined(CSD_SYNC)
+	if constexpr (W > 1) CSD_SYNC();
+#endif
+}
 template <int W, class T> CS_HD inline T wsum(T v)
 {
 #ifdef CSD_SYNC
 	if constexpr (W > 1) for (int d = W >> 1; d > 0; d >>= 1) v += CSD_SHFL_XOR(v, d, W);
 #endif
 	return v;
+}
+// the sum of v over the lanes below this one; total: over all W
+template <int W> CS_HD inline uint32_t wexcl_sum(uint32_t v, int lane, uint32_t &total)
+{
+	uint32_t x = v;
+#ifdef CSD_SYNC
+	if constexpr (W > 1) {
+		for (int d = 1; d < W; d <<= 1) { const uint32_t y = CSD_SHFL_UP(x, d, W); if (lane >= d) x += y; }
+		total = CSD_SHFL(x, W - 1, W);
+		return x - v;
+	}
+#endif
+	(void)lane;
+	total = x;
+	return x - v;
 }
 // the maximum of g over the lanes below this one and `carry` (the strips before); carry takes the whole strip in
 template <int W> CS_HD inline int64_t wprefix_max(int64_t g, int lane, int64_t &carry)

@@ -1,5 +1,5 @@
 // lockstep.hpp -- what the CPU programs over the W-lane bodies share (chain_filter_scan_check.cpp, dedup_scan_check.cpp,
-// dedup_pass_check.cpp, cigar_scan_check.cpp): include it BEFORE the header under test.
+// dedup_pass_check.cpp, cigar_scan_check.cpp, align_scan_check.cpp): include it BEFORE the header under test.
 // Built with -DCS_EMU_W=N (a power of two up to 64; -pthread) the CSD_ macros of compseed_amd/csrc/wave_lanes.hpp are defined over N
 // threads in lockstep: a ballot or a shuffle is an exchange through a shared array between two barriers, so lanes that reach different
 // collectives, or a different number of them, never finish (the tests' time limits) or differ in what they return.  Without it LANES
