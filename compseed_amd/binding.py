@@ -23,7 +23,8 @@ SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", 
            "cs_ext_params_default", "cs_extender_create", "cs_extender_destroy", "cs_extend_batch", "cs_extend_batch_device", "cs_extender_stats",
            "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_extend_chains_device", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats",
            "cs_regions_cigar", "cs_cigar_stats", "cs_mark_params_default", "cs_regions_mark", "cs_mark_stats",
-           "cs_regions_sam", "cs_sam_header", "cs_sam_stats"]
+           "cs_regions_sam", "cs_sam_header", "cs_sam_stats", "cs_reader_next_chunk",
+           "cs_map_params_default", "cs_map_params_split", "cs_mapper_create", "cs_mapper_destroy", "cs_map_batch", "cs_mapper_header", "cs_mapper_stats", "cs_mapper_engine_stats"]
 
 
 class CSError(RuntimeError):
@@ -250,6 +251,40 @@ class SamStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("reads", "lines", "unmapped", "bytes", "xa_entries", "sa_entries", "launches")] + [("kernel_ms", C.c_double)]
 
 
+# cs_mapper_t: reads to SAM text in one call
+MAP_ALL, MAP_NO_MULTI, MAP_KEEP_SUPP_MAPQ, MAP_SOFTCLIP = 1, 2, 4, 8
+MAP_STAGES = ("upload", "seed", "chain", "filter", "extend", "download", "dedup", "mark", "cigar", "sam", "total")   # CS_MAP_T_*
+
+
+class MapParams(C.Structure):
+    """cs_map_params_t: mem_opt_t as the command line fills it; defaults = cs_map_params_default (mem_opt_init, mapping/comp_seed.cpp:26-58).
+    T is the caller's to scale by -A; rg_id: str or bytes, None for no RG tag"""
+    _fields_ = [(n, C.c_int32) for n in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "pen_clip5", "pen_clip3", "w", "zdrop", "T", "min_seed_len")] + \
+               [("split_factor", C.c_float), ("split_width", C.c_int32), ("max_occ", C.c_int32), ("max_mem_intv", C.c_uint64)] + \
+               [(n, C.c_int32) for n in ("max_chain_gap", "max_chain_extend", "min_chain_weight")] + \
+               [(n, C.c_float) for n in ("mask_level", "drop_ratio", "xa_drop_ratio", "mask_level_redun")] + \
+               [(n, C.c_int32) for n in ("mapq_coef_len", "max_xa_hits", "max_xa_hits_alt")] + \
+               [("flags", C.c_uint32), ("threads", C.c_int32), ("rg_id", C.c_char_p), ("reserved", C.c_uint32 * 4)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        load_library().cs_map_params_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("no such field: " + k)
+            setattr(self, k, v.encode() if k == "rg_id" and isinstance(v, str) else v)
+
+
+class MapStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("reads", "bases", "regions", "lines", "unmapped", "bytes", "batches")] + [("stage_ms", C.c_double * len(MAP_STAGES))]
+
+
+class CReadChunk(C.Structure):
+    """cs_read_chunk_t"""
+    _fields_ = [("n_reads", C.c_int64), ("first_id", C.c_uint64), ("bases", C.c_void_p), ("offsets", C.c_void_p), ("quals", C.c_void_p), ("names", C.c_void_p), ("name_off", C.c_void_p),
+                ("comments", C.c_void_p), ("comment_off", C.c_void_p)]
+
+
 class IndexCheck(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rows_checked", "order_violations", "isa_violations", "bwt_violations", "sampled_sa_violations", "undecided_rows",
                                           "text_violations")] + [("text_checked", C.c_int32), ("reserved", C.c_int32)]
@@ -464,6 +499,18 @@ def load_library():
     L.cs_regions_sam.argtypes = [vp, C.POINTER(SamParams), C.POINTER(CMarkResult), vp, C.POINTER(CCigarResult), vp, vp, vp, vp, vp, vp, vp, C.POINTER(CSamResult)]
     L.cs_sam_header.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cs_sam_stats.argtypes = [vp, C.POINTER(SamStats)]
+    L.cs_reader_next_chunk.argtypes = [vp, C.POINTER(CReadChunk)]
+    L.cs_map_params_default.argtypes = [C.POINTER(MapParams)]
+    L.cs_map_params_default.restype = None
+    L.cs_map_params_split.argtypes = [C.POINTER(MapParams), C.POINTER(Params), C.POINTER(ChainParams), C.POINTER(FltParams), C.POINTER(AlnParams), C.POINTER(DedupParams), C.POINTER(MarkParams),
+                                      C.POINTER(C.c_uint32), C.POINTER(SamParams)]
+    L.cs_mapper_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(EngineOptions), C.POINTER(MapParams), C.POINTER(vp)]
+    L.cs_mapper_destroy.argtypes = [vp]
+    L.cs_mapper_destroy.restype = None
+    L.cs_map_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(CSamResult)]
+    L.cs_mapper_header.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.cs_mapper_stats.argtypes = [vp, C.POINTER(MapStats)]
+    L.cs_mapper_engine_stats.argtypes = [vp, C.POINTER(Stats)]
     _lib = L
     return L
 
@@ -590,6 +637,21 @@ class Reader:
             raise StopIteration
         off = _view(o.value, "<u8", n.value + 1, False)
         return _view(b.value, np.uint8, int(off[-1]), False), off
+
+    def next_chunk(self, copy=False):
+        """cs_reader_next_chunk: the next chunk with what a SAM record needs, as a dict -- n_reads, first_id (the reads before it: map_batch's
+        id_base), bases, offsets, quals (None for reordered reads), names / comments as (bytes as uint8, uint64 CSR offsets) pairs (comments
+        None where the input has none) -- or None at the end of the input.  copy=False: views of the reader's two alternating buffers, valid
+        until the chunk after the next is read.  A reader is driven either by this call or by iteration"""
+        c = CReadChunk()
+        _check(load_library().cs_reader_next_chunk(self._h, C.byref(c)))
+        n = int(c.n_reads)
+        if n == 0:
+            return None
+        off = _view(c.offsets, "<u8", n + 1, copy)
+        csr = lambda b, o: None if not o else (lambda oo: (_view(b, np.uint8, int(oo[-1]), copy), oo))(_view(o, "<u8", n + 1, copy))
+        return dict(n_reads=n, first_id=int(c.first_id), bases=_view(c.bases, np.uint8, int(off[-1]), copy), offsets=off,
+                    quals=_view(c.quals, np.uint8, int(off[-1]), copy) if c.quals else None, names=csr(c.names, c.name_off), comments=csr(c.comments, c.comment_off))
 
     def close(self):
         if self._h:
@@ -1196,6 +1258,83 @@ class Aligner:
     def close(self):
         if self.h:
             self.L.cs_aligner_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def map_params_split(params=None):
+    """cs_map_params_split: a MapParams (None: the defaults) as the stages take it -> dict(seed=Params, chain=ChainParams, flt=FltParams, aln=AlnParams,
+    dedup=DedupParams, mark=MarkParams, mark_flags=int, sam=SamParams)"""
+    params = params if params is not None else MapParams()
+    out = dict(seed=Params(), chain=ChainParams(), flt=FltParams(), aln=AlnParams(), dedup=DedupParams(), mark=MarkParams(), sam=SamParams())
+    mf = C.c_uint32()
+    _check(load_library().cs_map_params_split(C.byref(params), C.byref(out["seed"]), C.byref(out["chain"]), C.byref(out["flt"]), C.byref(out["aln"]), C.byref(out["dedup"]),
+                                              C.byref(out["mark"]), C.byref(mf), C.byref(out["sam"])))
+    out["mark_flags"] = int(mf.value)
+    return out
+
+
+class Mapper:
+    """cs_mapper_t: reads to SAM text in one call -- one engine, one device chainer and one aligner on `device`, the index loaded from `prefix`"""
+
+    def __init__(self, prefix, device=0, engine_options=None, params=None):
+        self.L = load_library()
+        self.h = C.c_void_p()
+        _check(self.L.cs_mapper_create(os.fsencode(prefix), int(device), C.byref(engine_options) if engine_options is not None else None,
+                                       C.byref(params) if params is not None else None, C.byref(self.h)))
+
+    def map_batch(self, bases, read_offsets, names, quals=None, comments=None, id_base=0):
+        """cs_map_batch: `names` / `comments` pairs (bytes as uint8, uint64 CSR offsets) or lists of bytes, `quals` uint8 at the bases' offsets,
+        `id_base` the number of reads before this batch -> (text_off, text) as Aligner.regions_sam returns them"""
+        def pair(x):
+            if isinstance(x, (list, tuple)) and (len(x) != 2 or isinstance(x[0], (bytes, str))):
+                x = [y.encode() if isinstance(y, str) else y for y in x]
+                off = np.zeros(len(x) + 1, np.uint64)
+                off[1:] = np.cumsum([len(y) for y in x])
+                x = (np.frombuffer(b"".join(x), np.uint8), off)
+            b = np.ascontiguousarray(x[0], dtype=np.uint8)
+            return (b if b.size else np.zeros(1, np.uint8)), np.ascontiguousarray(x[1], dtype=np.uint64)
+        bases = np.ascontiguousarray(bases, dtype=np.uint8); ro = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+        q = None if quals is None else np.ascontiguousarray(quals, dtype=np.uint8)
+        nm, no = pair(names)
+        cm, cmo = pair(comments) if comments is not None else (None, None)
+        ptr = lambda x: x.ctypes.data if x is not None and x.size else None
+        out = CSamResult()
+        _check(self.L.cs_map_batch(self.h, ro.size - 1, ptr(bases), ptr(ro), ptr(q), nm.ctypes.data, ptr(no), cm.ctypes.data if cm is not None else None, ptr(cmo), int(id_base), C.byref(out)))
+        return _view(out.text_off, "<u8", int(out.n_reads) + 1, True), (C.string_at(out.text, int(out.n_bytes)) if out.n_bytes else b"")
+
+    def header(self, rg_line=None):
+        """cs_mapper_header: the @SQ lines and, where given, the @RG line (as -R takes it: tabs written as a backslash and a t)"""
+        rg = rg_line.encode() if isinstance(rg_line, str) else rg_line
+        need = C.c_size_t()
+        rc = self.L.cs_mapper_header(self.h, rg, None, 0, C.byref(need))
+        if rc != 0 and need.value == 0:
+            _check(rc)
+        buf = C.create_string_buffer(max(1, need.value))
+        _check(self.L.cs_mapper_header(self.h, rg, buf, need.value, C.byref(need)))
+        return buf.raw[:need.value]
+
+    def stats(self):
+        """cs_mapper_stats: the counters, and stage_ms as a dict by step name (MAP_STAGES)"""
+        st = MapStats()
+        _check(self.L.cs_mapper_stats(self.h, C.byref(st)))
+        out = {n: int(getattr(st, n)) for n, _ in MapStats._fields_ if n != "stage_ms"}
+        out["stage_ms"] = {n: float(st.stage_ms[k]) for k, n in enumerate(MAP_STAGES)}
+        return out
+
+    def engine_stats(self):
+        st = Stats()
+        _check(self.L.cs_mapper_engine_stats(self.h, C.byref(st)))
+        return st.asdict()
+
+    def close(self):
+        if self.h:
+            self.L.cs_mapper_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

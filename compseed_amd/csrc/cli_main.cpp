@@ -1,17 +1,31 @@
-// cli_main.cpp -- `compseed_amd_cli`: the CompSeed command line for the seeding path, on MI355X.
+// cli_main.cpp -- `compseed_amd_cli`: the CompSeed command line on MI355X, in two modes.
 //
-//   compseed_amd_cli [options] <FM-index prefix> <reordered reads>
+//   compseed_amd_cli [options] <FM-index prefix> <reordered reads>                 the seeding mode
+//   compseed_amd_cli --sam FILE [options] <FM-index prefix> <reordered reads>      reads to SAM (FILE '-': standard output)
 //
-// Same positional arguments and the same seeding flags as `CompSeed` / `bwamem` (main.cpp:146-200, 233-330):
-// -t -k -r -y -c -s -K.  Everything downstream of seeding (chaining, banded SW, SAM) is out of scope, so instead of SAM
-// the program writes the seeds (--dump-seeds FILE) and prints the reference's exit counters (display_profile,
-// main.cpp:203-214).  Flags of the stages that are not here are accepted and ignored so existing command lines run.
-// Input: one read per line (input_reorder_reads, main.cpp:36-58) or FASTQ when the first byte is '@' (main.cpp:399-406).
-// Chunking follows main.cpp:54,437: a chunk ends at the first even read count that reaches -K bases
-// (default 10,000,000 x n_threads).  Chunks are split into contiguous read ranges, one per GPU (--gpus N, default all).
+// Same positional arguments as `CompSeed` / `bwamem` (main.cpp:146-200, 233-330).  Input: one read per line (input_reorder_reads,
+// main.cpp:36-58) or FASTQ when the first byte is '@' (main.cpp:399-406).  Chunking follows main.cpp:54,437: a chunk ends at the first even
+// read count that reaches -K bases (default 10,000,000 x n_threads).  Chunks are split into contiguous read ranges, one per GPU
+// (--gpus N, default all; --devices LIST).
+// The seeding mode (no --sam) is what the program was before the library could write SAM, and it stays as it was for the command lines
+// that use it: the seeding flags -t -k -r -y -c -s -K are honoured, the flags of the other stages are accepted and ignored, the seeds
+// are written (--dump-seeds FILE) and the reference's exit counters printed (display_profile, main.cpp:203-214).
+// With --sam the flags are parsed as main.cpp:233-330 parses them and update_a (main.cpp:130-143) is applied; one cs_mapper_t per GPU
+// maps each chunk's shard while the next chunk is read, and FILE receives the header (bwa_print_sam_hdr, with -R's line) and every chunk's
+// text in read order: the file the reference's program writes.  Honoured: -k -r -y -c -s -K -t, -w -d -D -W -N -G -X -T -A -B,
+// -O / -E / -L / -h a[,b], -Q -a -M -q -Y -C -R -v; -o / -f / -1 are accepted and ignored (as in the seeding mode: making -o an alias of
+// --sam would change what existing command lines do).  Refused with exit status 1 before the GPU is touched, because the library's stages
+// do not have them: -5 (mem_reorder_primary5), -V (XR), -Q <= 0 (the other MAPQ formula), -L a,b with a != b (one extender, one end
+// bonus), -x presets, -H, -j, the paired-end options -p -I -S -P -U -m and a second reads file (the reference's own program refuses
+// that one, main.cpp:331-335), and --dump-seeds / --no-sal together with --sam.  --show-params prints the resolved cs_map_params_t as
+// key=value lines and exits without touching the index or the GPU.
 #include "../../include/compseed_amd.h"
 
+#include <cctype>
+#include <chrono>
 #include <cstdio>
+#include <functional>
+#include <thread>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -41,9 +55,9 @@ static void usage()
 	        "belong to stages behind seeding; they are accepted and ignored.\n");
 }
 
-int main(int argc, char **argv)
+// the seeding mode: everything the program did before it wrote SAM, unchanged
+static int seed_main(int argc, char **argv)
 {
-	setenv("GPU_MAX_HW_QUEUES", "8", 0); // before the HIP runtime starts: one engine per GPU, each with streams of its own (INTEGRATION.md)
 	cs_params_t par; cs_params_default(&par);
 	int n_threads = 1, n_gpus = -1, verbose = 0; long fixed_chunk = 0; const char *dump = nullptr;
 	std::vector<int> devices; // --devices: the device ordinal of every shard (an ordinal may repeat: several engines on one GPU)
@@ -169,4 +183,270 @@ int main(int argc, char **argv)
 	fprintf(stderr, "Wall time:   BWT %.2f SAL %.2f seconds on %d GPU(s); %lu reads, %lu mems, %lu seeds\n", tot.seed_kernel_ms / 1e3,
 	        tot.sal_kernel_ms / 1e3, n_gpus, (unsigned long)tot.reads, (unsigned long)tot.mems, (unsigned long)tot.seeds);
 	return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- --sam: reads to SAM
+static void usage_sam()
+{
+	fprintf(stderr,
+	        "Usage: compseed_amd_cli --sam FILE [options] <FM-index> <Reordered Reads | FASTQ>      (FILE '-': standard output)\n\n"
+	        "Options with the meaning they have in CompSeed / bwamem:\n"
+	        "       seeding      -k INT  -r FLOAT  -y INT  -c INT  -s INT\n"
+	        "       chaining     -w INT  -G INT  -N INT  -W INT  -D FLOAT  -X FLOAT\n"
+	        "       extension    -A INT  -B INT  -O INT[,INT]  -E INT[,INT]  -L INT  -d INT\n"
+	        "       output       -T INT  -h INT[,INT]  -Q INT  -a  -M  -q  -Y  -C  -R STR  -v INT\n"
+	        "       input        -t INT  -K INT          (-o / -f / -1 are accepted and ignored)\n"
+	        "       --gpus INT | --devices LIST   one mapper per entry; a chunk's reads are split into contiguous ranges\n"
+	        "       --show-params                 print the resolved parameters as key=value lines and exit\n"
+	        "Refused: -5, -V, -Q <= 0, -L with two different values, -p -x -H -I -j -S -P -U -m, a second reads file (paired-end),\n"
+	        "         --dump-seeds and --no-sal together with --sam.\n");
+}
+
+namespace {
+struct SamOpts {
+	cs_map_params_t p; bool given_b = false, given_T = false, given_o_del = false, given_e_del = false, given_o_ins = false, given_e_ins = false, given_zdrop = false,
+	                        given_clip5 = false, given_clip3 = false, given_a = false;   // opt0 of main.cpp:232-330
+	int n_threads = 1, n_gpus = -1, verbose = 0; long fixed_chunk = 0; bool copy_comment = false, show = false;
+	const char *sam = nullptr; std::string rg_line, rg_id; std::vector<int> devices; std::vector<const char *> pos;
+};
+int refuse(const char *opt, const char *why) { fprintf(stderr, "[E::main] %s: %s\n", opt, why); return 1; }
+// "INT[,INT]" as main.cpp:268-292 reads it: the second value behind one punctuation character
+void two_ints(const char *v, int32_t *x, int32_t *y)
+{
+	char *q = nullptr;
+	*x = *y = (int32_t)strtol(v, &q, 10);
+	if (*q != 0 && ispunct((unsigned char)*q) && isdigit((unsigned char)q[1])) *y = (int32_t)strtol(q + 1, &q, 10);
+}
+// -R's line: "@RG" first, tabs written as a backslash and a t, an ID field (bwa_set_rg / bwa_rg_id, bwalib/bwa.c:429-476); the ID into `id`
+bool rg_id_of(const std::string &line, std::string &id)
+{
+	if (line.compare(0, 3, "@RG") != 0 || line.find('\t') != std::string::npos) return false;
+	std::string u;
+	for (size_t k = 0; k < line.size(); ++k) {
+		if (line[k] != '\\') { u += line[k]; continue; }
+		if (++k == line.size()) break;
+		u += line[k] == 't' ? '\t' : line[k] == 'n' ? '\n' : line[k] == 'r' ? '\r' : line[k] == '\\' ? '\\' : '\0';
+		if (u.back() == '\0') u.pop_back();
+	}
+	const size_t at = u.find("\tID:");
+	if (at == std::string::npos) return false;
+	size_t e = at + 4;
+	while (e < u.size() && u[e] != '\t' && u[e] != '\n') ++e;
+	id = u.substr(at + 4, e - at - 4);
+	return !id.empty() && id.size() <= 255;
+}
+
+// the command line as main.cpp:233-335 reads it (getopt: clustered switches, a value attached or in the next argument); 0, or the exit status
+int parse_sam(int argc, char **argv, SamOpts &o)
+{
+	cs_map_params_default(&o.p);
+	cs_map_params_t &p = o.p;
+	const std::string switches = "51qpaMCSPVYj", valued = "kcvsrtRABOEUwLdTQDmINofWxGhyKXH";
+	bool dump = false, no_sal = false;
+	for (int i = 1; i < argc; ++i) {
+		const std::string a = argv[i];
+		auto next = [&](const char *opt) -> const char * { if (i + 1 >= argc) { fprintf(stderr, "[E::main] option %s needs a value\n", opt); usage_sam(); exit(1); } return argv[++i]; };
+		if (a == "--sam") { o.sam = next("--sam"); continue; }
+		if (a == "--show-params") { o.show = true; continue; }
+		if (a == "--gpus") { o.n_gpus = atoi(next("--gpus")); continue; }
+		if (a == "--devices") { for (const char *q = next("--devices"); *q;) { o.devices.push_back((int)strtol(q, (char **)&q, 10)); if (*q == ',') ++q; else if (*q) { usage_sam(); return 1; } } continue; }
+		if (a == "--dump-seeds") { (void)next("--dump-seeds"); dump = true; continue; }
+		if (a == "--no-sal") { no_sal = true; continue; }
+		if (a.size() < 2 || a[0] != '-' || a == "-") { o.pos.push_back(argv[i]); continue; }
+		if (a[1] == '-') { fprintf(stderr, "[E::main] unknown option %s\n", a.c_str()); usage_sam(); return 1; }
+		for (size_t j = 1; j < a.size(); ++j) {
+			const char c = a[j];
+			const std::string name = std::string("-") + c;
+			if (switches.find(c) != std::string::npos) {
+				if (c == 'a') p.flags |= CS_MAP_ALL;
+				else if (c == 'M') p.flags |= CS_MAP_NO_MULTI;
+				else if (c == 'q') p.flags |= CS_MAP_KEEP_SUPP_MAPQ;
+				else if (c == 'Y') p.flags |= CS_MAP_SOFTCLIP;
+				else if (c == 'C') o.copy_comment = true;
+				else if (c == '1') {}                                          // (no_mt_io: this program's reader has one thread anyway)
+				else if (c == '5') return refuse("-5", "the reordering of split alignments (mem_reorder_primary5) is not implemented");
+				else if (c == 'V') return refuse("-V", "the XR tag is not implemented");
+				else if (c == 'j') return refuse("-j", "ignoring the .alt file is not implemented");
+				else return refuse(name.c_str(), "paired-end options are not implemented (the reference's program refuses a second reads file too)");   // -p -S -P
+				continue;
+			}
+			if (valued.find(c) == std::string::npos) { fprintf(stderr, "[E::main] unknown option %s\n", name.c_str()); usage_sam(); return 1; }
+			const std::string own = a.substr(j + 1);
+			const char *v = own.empty() ? next(name.c_str()) : own.c_str();
+			if (c == 'k') p.min_seed_len = atoi(v);
+			else if (c == 'r') p.split_factor = (float)atof(v);
+			else if (c == 'y') p.max_mem_intv = (uint64_t)atol(v);
+			else if (c == 'c') p.max_occ = atoi(v);
+			else if (c == 's') p.split_width = atoi(v);
+			else if (c == 't') { o.n_threads = atoi(v); if (o.n_threads < 1) o.n_threads = 1; }
+			else if (c == 'K') o.fixed_chunk = atol(v);
+			else if (c == 'v') o.verbose = atoi(v) >= 4 ? 1 : 0;
+			else if (c == 'w') p.w = atoi(v);
+			else if (c == 'd') { p.zdrop = atoi(v); o.given_zdrop = true; }
+			else if (c == 'D') p.drop_ratio = (float)atof(v);
+			else if (c == 'W') p.min_chain_weight = atoi(v);
+			else if (c == 'N') p.max_chain_extend = atoi(v);
+			else if (c == 'G') p.max_chain_gap = atoi(v);
+			else if (c == 'X') p.mask_level = (float)atof(v);
+			else if (c == 'T') { p.T = atoi(v); o.given_T = true; }
+			else if (c == 'A') { p.a = atoi(v); o.given_a = true; }
+			else if (c == 'B') { p.b = atoi(v); o.given_b = true; }
+			else if (c == 'O') { two_ints(v, &p.o_del, &p.o_ins); o.given_o_del = o.given_o_ins = true; }
+			else if (c == 'E') { two_ints(v, &p.e_del, &p.e_ins); o.given_e_del = o.given_e_ins = true; }
+			else if (c == 'L') { two_ints(v, &p.pen_clip5, &p.pen_clip3); o.given_clip5 = o.given_clip3 = true; if (p.pen_clip5 != p.pen_clip3) return refuse("-L", "two different clipping penalties are not implemented (one extender, one end bonus)"); }
+			else if (c == 'h') two_ints(v, &p.max_xa_hits, &p.max_xa_hits_alt);
+			else if (c == 'Q') { p.mapq_coef_len = atoi(v); if (p.mapq_coef_len <= 0) return refuse("-Q", "the MAPQ formula of a value <= 0 is not implemented"); }
+			else if (c == 'R') { o.rg_line = v; if (!rg_id_of(o.rg_line, o.rg_id)) return refuse("-R", "the read group line starts with @RG, writes its tabs as \\t and has an ID of at most 255 characters"); }
+			else if (c == 'o' || c == 'f') {}                                  // accepted and ignored in both modes: the output is --sam's
+			else if (c == 'x') return refuse("-x", "read-type presets are not implemented");
+			else if (c == 'H') return refuse("-H", "extra header lines are not implemented");
+			else return refuse(name.c_str(), "paired-end options are not implemented (the reference's program refuses a second reads file too)");       // -I -U -m
+			break;
+		}
+	}
+	if (o.sam && dump) return refuse("--dump-seeds", "not together with --sam");
+	if (o.sam && no_sal) return refuse("--no-sal", "not together with --sam");
+	if (o.pos.size() >= 3) return refuse(o.pos[2], "a second reads file: paired-end is not implemented (the reference's program refuses it too)");
+	if (o.given_a) {   // update_a, main.cpp:130-143
+		if (!o.given_b) p.b *= p.a;
+		if (!o.given_T) p.T *= p.a;
+		if (!o.given_o_del) p.o_del *= p.a;
+		if (!o.given_e_del) p.e_del *= p.a;
+		if (!o.given_o_ins) p.o_ins *= p.a;
+		if (!o.given_e_ins) p.e_ins *= p.a;
+		if (!o.given_zdrop) p.zdrop *= p.a;
+		if (!o.given_clip5) p.pen_clip5 *= p.a;
+		if (!o.given_clip3) p.pen_clip3 *= p.a;
+	}
+	p.rg_id = o.rg_id.empty() ? nullptr : o.rg_id.c_str();
+	return 0;
+}
+
+void show_params(const SamOpts &o)
+{
+	const cs_map_params_t &p = o.p;
+	printf("a=%d\nb=%d\no_del=%d\ne_del=%d\no_ins=%d\ne_ins=%d\npen_clip5=%d\npen_clip3=%d\nw=%d\nzdrop=%d\nT=%d\n", p.a, p.b, p.o_del, p.e_del, p.o_ins, p.e_ins, p.pen_clip5, p.pen_clip3, p.w, p.zdrop, p.T);
+	printf("min_seed_len=%d\nsplit_factor=%g\nsplit_width=%d\nmax_occ=%d\nmax_mem_intv=%lu\n", p.min_seed_len, (double)p.split_factor, p.split_width, p.max_occ, (unsigned long)p.max_mem_intv);
+	printf("max_chain_gap=%d\nmax_chain_extend=%d\nmin_chain_weight=%d\n", p.max_chain_gap, p.max_chain_extend, p.min_chain_weight);
+	printf("mask_level=%g\ndrop_ratio=%g\nxa_drop_ratio=%g\nmask_level_redun=%g\n", (double)p.mask_level, (double)p.drop_ratio, (double)p.xa_drop_ratio, (double)p.mask_level_redun);
+	printf("mapq_coef_len=%d\nmax_xa_hits=%d\nmax_xa_hits_alt=%d\nflags=%u\nthreads=%d\nrg_id=%s\n", p.mapq_coef_len, p.max_xa_hits, p.max_xa_hits_alt, p.flags, p.threads, p.rg_id ? p.rg_id : "");
+	printf("copy_comment=%d\nchunk_bases=%ld\n", o.copy_comment ? 1 : 0, o.fixed_chunk > 0 ? o.fixed_chunk : 10000000L * o.n_threads);
+}
+
+// a shard of a chunk: a contiguous read range with its offset arrays rebased to 0 (they live until the shard's text has been written)
+struct Shard { int64_t r0 = 0, n = 0; std::vector<uint64_t> off, name_off, comment_off; cs_sam_result_t res{}; int rc = 0; std::string err; };
+} // namespace
+
+static int sam_main(int argc, char **argv)
+{
+	SamOpts o;
+	if (int rc = parse_sam(argc, argv, o)) return rc;
+	if (o.show) { show_params(o); return 0; }
+	if (!o.sam || o.pos.size() != 2) { usage_sam(); return 1; }
+
+	int ndev = 0;
+	if (cs_device_count(&ndev) || ndev < 1) { fprintf(stderr, "[E::main] no MI355X visible: %s\n", cs_last_error()); return 1; }
+	int n_gpus = o.n_gpus;
+	std::vector<int> devices = o.devices;
+	if (!devices.empty()) n_gpus = (int)devices.size();
+	else { if (n_gpus < 1 || n_gpus > ndev) n_gpus = ndev; for (int g = 0; g < n_gpus; ++g) devices.push_back(g); }
+	for (int d : devices) if (d < 0 || d >= ndev) { fprintf(stderr, "[E::main] --devices: no device %d (%d visible)\n", d, ndev); return 1; }
+	cs_engine_options_t eopt; cs_engine_options_default(&eopt);
+	eopt.count_sal_merged = 1; // "SA Lookup: ... calls, % merged" as CompSeed prints it (main.cpp:209-210)
+	eopt.verbose = o.verbose;
+	std::vector<cs_mapper_t *> mp((size_t)n_gpus, nullptr);
+	for (int g = 0; g < n_gpus; ++g)
+		if (cs_mapper_create(o.pos[0], devices[(size_t)g], &eopt, &o.p, &mp[(size_t)g])) { fprintf(stderr, "[E::main] GPU %d: %s\n", g, cs_last_error()); return 1; }
+
+	const bool to_stdout = strcmp(o.sam, "-") == 0;
+	FILE *fo = to_stdout ? stdout : fopen(o.sam, "wb");
+	if (!fo) { fprintf(stderr, "[E::main] cannot write %s\n", o.sam); return 1; }
+	{   // bwa_print_sam_hdr (main.cpp:436): the @SQ lines and -R's line
+		size_t need = 0;
+		const char *rg = o.rg_line.empty() ? nullptr : o.rg_line.c_str();
+		(void)cs_mapper_header(mp[0], rg, nullptr, 0, &need);
+		std::vector<char> hdr(need + 1);
+		if (cs_mapper_header(mp[0], rg, hdr.data(), need, &need)) { fprintf(stderr, "[E::main] %s\n", cs_last_error()); return 1; }
+		fwrite(hdr.data(), 1, need, fo);
+	}
+	const long chunk_bases = o.fixed_chunk > 0 ? o.fixed_chunk : 10000000L * o.n_threads; // main.cpp:437
+	cs_reader_t *rd = nullptr;
+	if (cs_reader_open(o.pos[1], chunk_bases, &rd)) { fprintf(stderr, "[E::main] %s\n", cs_last_error()); return 1; }
+
+	// The reference's three-step pipeline (main.cpp:438): chunk n+1 is read while chunk n is mapped -- every mapper on a thread of its own
+	// over a contiguous read range of the chunk -- and the texts are written in shard order, chunk by chunk.
+	auto read_chunk = [&](cs_read_chunk_t &c) -> bool {
+		if (cs_reader_next_chunk(rd, &c)) { fprintf(stderr, "[E::process] %s\n", cs_last_error()); exit(1); }
+		return c.n_reads > 0;
+	};
+	auto map_shard = [&](const cs_read_chunk_t &c, int g, Shard &s) {
+		s.r0 = c.n_reads * g / n_gpus; s.n = c.n_reads * (g + 1) / n_gpus - s.r0;
+		const bool cm = o.copy_comment && c.comment_off;                   // -C (main.cpp:77-81)
+		s.off.resize((size_t)s.n + 1); s.name_off.resize((size_t)s.n + 1); s.comment_off.resize(cm ? (size_t)s.n + 1 : 0);
+		for (int64_t r = 0; r <= s.n; ++r) {
+			s.off[(size_t)r] = c.offsets[s.r0 + r] - c.offsets[s.r0]; s.name_off[(size_t)r] = c.name_off[s.r0 + r] - c.name_off[s.r0];
+			if (cm) s.comment_off[(size_t)r] = c.comment_off[s.r0 + r] - c.comment_off[s.r0];
+		}
+		s.rc = cs_map_batch(mp[(size_t)g], s.n, c.bases + c.offsets[s.r0], s.off.data(), c.quals ? c.quals + c.offsets[s.r0] : nullptr, c.names + c.name_off[s.r0], s.name_off.data(),
+		                    cm ? c.comments + c.comment_off[s.r0] : nullptr, cm ? s.comment_off.data() : nullptr, (int64_t)c.first_id + s.r0, &s.res);
+		if (s.rc) s.err = cs_last_error();                                 // (the message is the calling thread's)
+	};
+	cs_read_chunk_t ch[2];
+	std::vector<Shard> shards((size_t)n_gpus);
+	uint64_t n_reads = 0;
+	const auto t0 = std::chrono::steady_clock::now();
+	int cur = 0;
+	bool have = read_chunk(ch[0]);
+	while (have) {
+		const cs_read_chunk_t &c = ch[cur];
+		std::vector<std::thread> th;
+		for (int g = 1; g < n_gpus; ++g) th.emplace_back(map_shard, std::cref(c), g, std::ref(shards[(size_t)g]));
+		std::thread first(map_shard, std::cref(c), 0, std::ref(shards[0]));
+		have = read_chunk(ch[cur ^ 1]);
+		first.join();
+		for (std::thread &t : th) t.join();
+		for (int g = 0; g < n_gpus; ++g) {
+			const Shard &s = shards[(size_t)g];
+			if (s.rc) { fprintf(stderr, "[E::main] GPU %d: %s\n", g, s.err.c_str()); return 1; }
+			if (s.res.n_bytes && fwrite(s.res.text, 1, (size_t)s.res.n_bytes, fo) != (size_t)s.res.n_bytes) { fprintf(stderr, "[E::main] cannot write %s\n", o.sam); return 1; }
+		}
+		n_reads += (uint64_t)c.n_reads;
+		cur ^= 1;
+	}
+	const double wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+	cs_reader_close(rd);
+	if (to_stdout ? fflush(fo) : fclose(fo)) { fprintf(stderr, "[E::main] cannot write %s\n", o.sam); return 1; }
+
+	cs_stats_t tot; memset(&tot, 0, sizeof tot);
+	cs_map_stats_t mt; memset(&mt, 0, sizeof mt);
+	for (int g = 0; g < n_gpus; ++g) {
+		cs_stats_t st; cs_mapper_engine_stats(mp[(size_t)g], &st);
+		tot.reads += st.reads; tot.bwt_queries += st.bwt_queries; tot.bwt_calls += st.bwt_calls; tot.sal_queries += st.sal_queries;
+		tot.sal_calls += st.sal_calls; tot.mems += st.mems; tot.seeds += st.seeds;
+		tot.seed_kernel_ms = st.seed_kernel_ms > tot.seed_kernel_ms ? st.seed_kernel_ms : tot.seed_kernel_ms;
+		tot.sal_kernel_ms = st.sal_kernel_ms > tot.sal_kernel_ms ? st.sal_kernel_ms : tot.sal_kernel_ms;
+		cs_map_stats_t ms; cs_mapper_stats(mp[(size_t)g], &ms);
+		mt.reads += ms.reads; mt.lines += ms.lines; mt.unmapped += ms.unmapped; mt.bytes += ms.bytes;
+		for (int k = 0; k < CS_MAP_N_STAGES; ++k) mt.stage_ms[k] = ms.stage_ms[k] > mt.stage_ms[k] ? ms.stage_ms[k] : mt.stage_ms[k];   // (the mappers run side by side)
+		cs_mapper_destroy(mp[(size_t)g]);
+	}
+	// display_profile, main.cpp:203-214
+	fprintf(stderr, "BWT-extend:  %lu queries, %lu calls, %.2f %% hit in SST\n", (unsigned long)tot.bwt_queries, (unsigned long)tot.bwt_calls,
+	        tot.bwt_queries ? 100.0 * (double)(tot.bwt_queries - tot.bwt_calls) / (double)tot.bwt_queries : 0.0);
+	fprintf(stderr, "SA Lookup:   %lu queries, %lu calls, %.2f %% merged\n", (unsigned long)tot.sal_queries, (unsigned long)tot.sal_calls,
+	        tot.sal_queries ? 100.0 * (double)(tot.sal_queries - tot.sal_calls) / (double)tot.sal_queries : 0.0);
+	fprintf(stderr, "Wall time:   BWT %.2f SAL %.2f seconds on %d GPU(s); %lu reads, %lu mems, %lu seeds\n", tot.seed_kernel_ms / 1e3,
+	        tot.sal_kernel_ms / 1e3, n_gpus, (unsigned long)tot.reads, (unsigned long)tot.mems, (unsigned long)tot.seeds);
+	static const char *const stage[CS_MAP_N_STAGES] = {"upload", "seed", "chain", "filter", "extend", "download", "dedup", "mark", "cigar", "sam", "total"};
+	for (int k = 0; k < CS_MAP_N_STAGES; ++k) fprintf(stderr, "Mapper %-9s %.2f ms\n", stage[k], mt.stage_ms[k]);
+	fprintf(stderr, "SAM:         %lu reads, %lu lines, %lu unmapped, %.0f reads/s over %.3f seconds of mapping\n", (unsigned long)n_reads, (unsigned long)(mt.lines + mt.unmapped), (unsigned long)mt.unmapped,
+	        wall_s > 0 ? (double)n_reads / wall_s : 0.0, wall_s);
+	return 0;
+}
+
+int main(int argc, char **argv)
+{
+	setenv("GPU_MAX_HW_QUEUES", "8", 0); // before the HIP runtime starts: one engine per GPU, each with streams of its own (INTEGRATION.md)
+	for (int i = 1; i < argc; ++i) if (!strcmp(argv[i], "--sam") || !strcmp(argv[i], "--show-params")) return sam_main(argc, argv);
+	return seed_main(argc, argv);
 }

@@ -323,6 +323,19 @@ typedef struct cs_reader cs_reader_t;
 int  cs_reader_open(const char *path, int64_t chunk_bases, cs_reader_t **out);
 int  cs_reader_next(cs_reader_t *r, const uint8_t **bases, const uint64_t **offsets, int64_t *n_reads);
 void cs_reader_close(cs_reader_t *r);
+/* The same chunks with everything a SAM record needs.  cs_reader_next_chunk cuts exactly where cs_reader_next cuts and uses the same two
+ * alternating buffers (a chunk stays intact while the next one is read); a reader is driven by ONE of the two calls (CS_EINVAL for the
+ * other).  Reordered reads: the name is the decimal of the 1-based running line number (main.cpp:47; has_input starts at 1), there are no
+ * qualities and no comments.  FASTQ, as kseq and bseq_read do it (bwalib/bwa.c:53-60, 78-110): the name runs to the first white-space
+ * byte, the comment is the rest of the header line after that one byte (empty where there is none), a trailing "/" + digit is trimmed
+ * from a name longer than two bytes, the quality line is the qualities (at the bases' offsets; a length other than the sequence's gives
+ * CS_EIO).  `first_id`: the number of reads before this chunk, cs_map_batch's id_base.  names / comments are CSR byte arrays of
+ * n_reads + 1 offsets.  n_reads == 0: end of input. */
+typedef struct { int64_t n_reads; uint64_t first_id; const uint8_t *bases; const uint64_t *offsets;
+                 const uint8_t *quals;                              /* NULL for reordered-reads input */
+                 const char *names; const uint64_t *name_off;
+                 const char *comments; const uint64_t *comment_off; /* both NULL: the input has none */ } cs_read_chunk_t;
+int  cs_reader_next_chunk(cs_reader_t *r, cs_read_chunk_t *out);
 
 /* ---- seed -> chain hand-off: mem_chain of the reference (mapping/comp_seed.cpp:241-285) over the seeds of a whole batch, host code.
  *      A chain is a run of co-linear seeds on one reference sequence (test_and_merge, comp_seed.cpp:182-203); chains come out per read in
@@ -596,6 +609,60 @@ int  cs_regions_sam(cs_aligner_t *a, const cs_sam_params_t *par, const cs_mark_r
                     const char *comments, const uint64_t *comment_off, cs_sam_result_t *out);
 int  cs_sam_header(const cs_aligner_t *a, const char *rg_line /* may be NULL */, char *buf, size_t cap, size_t *need);
 int  cs_sam_stats(const cs_aligner_t *a, cs_sam_stats_t *st);
+
+/* ---- reads to SAM text in one call: the mapper owns one engine, one device chainer and one aligner on one GPU, the device copy of the
+ *      reads, the order of the stage calls above and their errors -- seed_and_extend behind mem_process_seqs (comp_seed.cpp:2239-2420)
+ *      single-end, as the reference's program runs it.  It adds no kernel: every stage is the documented call above, with its limits.
+ *      cs_map_params_t is mem_opt_t as the command line fills it; cs_map_params_split is the ONE place where a field several stages
+ *      read (min_seed_len, max_occ, max_chain_gap, mask_level, drop_ratio, the scoring) is copied to each of them; the seeding struct's
+ *      engine-side knobs (sst_mode, disable, result_flags) stay at their defaults.  Host only.
+ *      cs_mapper_create loads the index files of `prefix`.  Errors, in this order: a NULL `prefix` or `out` or device < 0 CS_EINVAL;
+ *      non-zero `reserved` or unknown flag bits CS_EINVAL; pen_clip5 != pen_clip3, mapq_coef_len <= 0 or a parameter one of the stages'
+ *      own checks refuses CS_EINVAL; index files missing CS_EIO; no GPU CS_EDEVICE.  On any error everything made so far is released and
+ *      *out is NULL.
+ *      cs_map_batch: host arrays in, with cs_regions_sam's conventions for quals, names and comments; `id_base`: the number of reads
+ *      before this batch (comp_seed.cpp:2410); `out`: as from cs_regions_sam, owned by the mapper and valid until its next cs_map_batch.
+ *      Per call: the reads are uploaded once into buffers the mapper owns and grows; cs_engine_seed_batch_device; cs_chain_batch_device;
+ *      cs_chain_filter_device; cs_extend_chains_device with CS_ALN_DEV_COMPACT; reg_off and the live regions come to the host;
+ *      cs_dedup_regions; cs_regions_mark; cs_regions_cigar over cigar_regs; cs_regions_sam (the three tail stages upload their own copy of
+ *      the reads).  n_reads == 0 gives an empty result; a batch in which no read has a seed, a chain or a region gives every read its
+ *      unmapped record.  Errors: NULL arguments, n_reads < 0, id_base < 0, read_offsets that do not start at 0 or decrease CS_EINVAL;
+ *      otherwise a stage's error is the call's error and cs_last_error names the stage.  After any error the mapper is usable for the
+ *      next call.  One thread at a time per mapper; mappers are independent.
+ *      cs_mapper_header is cs_sam_header on the mapper's aligner.  cs_mapper_stats: counters over the mapper's life and the host wall
+ *      time of each step of cs_map_batch, accumulated; cs_mapper_engine_stats passes cs_engine_stats through. */
+#define CS_MAP_ALL             1u   /* -a */
+#define CS_MAP_NO_MULTI        2u   /* -M */
+#define CS_MAP_KEEP_SUPP_MAPQ  4u   /* -q */
+#define CS_MAP_SOFTCLIP        8u   /* -Y */
+typedef struct {
+	int32_t a, b, o_del, e_del, o_ins, e_ins, pen_clip5, pen_clip3, w, zdrop;   /* -A -B -O -E -L -w -d */
+	int32_t T;                                                                   /* -T, already scaled by -A */
+	int32_t min_seed_len; float split_factor; int32_t split_width, max_occ; uint64_t max_mem_intv;  /* -k -r -s -c -y */
+	int32_t max_chain_gap, max_chain_extend, min_chain_weight;                   /* -G -N -W */
+	float   mask_level, drop_ratio, xa_drop_ratio, mask_level_redun;             /* -X -D, 0.80, 0.95 */
+	int32_t mapq_coef_len, max_xa_hits, max_xa_hits_alt;                         /* -Q -h */
+	uint32_t flags;          /* CS_MAP_ALL (-a) | CS_MAP_NO_MULTI (-M) | CS_MAP_KEEP_SUPP_MAPQ (-q) | CS_MAP_SOFTCLIP (-Y) */
+	int32_t threads;         /* host threads of cs_dedup_regions [16] */
+	const char *rg_id;       /* NULL or "": no RG tag */
+	uint32_t reserved[4];    /* must be 0 */
+} cs_map_params_t;
+enum { CS_MAP_T_UPLOAD, CS_MAP_T_SEED, CS_MAP_T_CHAIN, CS_MAP_T_FILTER, CS_MAP_T_EXTEND, CS_MAP_T_DOWNLOAD, CS_MAP_T_DEDUP, CS_MAP_T_MARK,
+       CS_MAP_T_CIGAR, CS_MAP_T_SAM, CS_MAP_T_TOTAL, CS_MAP_N_STAGES };
+typedef struct { uint64_t reads, bases, regions /* after de-duplication */, lines, unmapped, bytes, batches;
+                 double stage_ms[CS_MAP_N_STAGES]; } cs_map_stats_t;
+typedef struct cs_mapper cs_mapper_t;
+void cs_map_params_default(cs_map_params_t *p);               /* mem_opt_init, comp_seed.cpp:26-58 */
+int  cs_map_params_split(const cs_map_params_t *p, cs_params_t *seed, cs_chain_params_t *chain, cs_flt_params_t *flt, cs_aln_params_t *aln,
+                         cs_dedup_params_t *dedup, cs_mark_params_t *mark, uint32_t *mark_flags, cs_sam_params_t *sam);
+int  cs_mapper_create(const char *prefix, int device, const cs_engine_options_t *eopt /* NULL: defaults */, const cs_map_params_t *par /* NULL: defaults */,
+                      cs_mapper_t **out);
+void cs_mapper_destroy(cs_mapper_t *m);
+int  cs_map_batch(cs_mapper_t *m, int64_t n_reads, const uint8_t *bases, const uint64_t *read_offsets, const uint8_t *quals, const char *names,
+                  const uint64_t *name_off, const char *comments, const uint64_t *comment_off, int64_t id_base, cs_sam_result_t *out);
+int  cs_mapper_header(const cs_mapper_t *m, const char *rg_line /* may be NULL */, char *buf, size_t cap, size_t *need);
+int  cs_mapper_stats(const cs_mapper_t *m, cs_map_stats_t *st);
+int  cs_mapper_engine_stats(const cs_mapper_t *m, cs_stats_t *st);
 
 /* ---- the result of the LAST device-variant call, without moving it: an order-sensitive 64-bit digest per array
  *      (sum over the array's 64-bit words w[i] of splitmix64(w[i] + i * 0x9E3779B97F4A7C15), mod 2^64), so that two runs over

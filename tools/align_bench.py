@@ -12,7 +12,10 @@ Behind that: "regions -> marks", cs_regions_mark over the de-duplicated regions 
 three ways -- over the marks' cigar_regs in either mode, and over all regions as a caller without marks has to -- each as the median, the
 minimum and the maximum of seven calls after a warm-up one, ms per million reads.  Behind that, per mode: "marks + CIGAR -> SAM text",
 cs_regions_sam over those marks and their alignments, timed the same way, with the device span, the bytes per read and the counts of
-cs_sam_stats.
+cs_sam_stats.  Last: "reads -> SAM text (cs_map_batch)", the whole path as one call of a Mapper of its own on the same reads -- reads/s over the
+median of three calls after a warm-up one, the mapper's per-step host wall time per call, and beside them the sum of this run's separate rows of
+the same steps (device seeding, device chaining, device filter, compacting extension and its download, dedup_regions, marks, marked CIGAR and
+SAM text in default mode); the text is checked equal to the separate stages' text.
 usage: align_bench.py [reads] [--synth-mbp M]"""
 import gzip, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -89,7 +92,7 @@ def run(n=200000, synth_mbp=0.0):
         # the chain pass on the GPU: host arrays in and out (PCIe both ways), then from the engine's device result (seeded once more)
         t6 = time.perf_counter(); cg = chd.chain_gpu(res.mem_off, res.mems, res.seed_off, res.seeds, off, ca.ChainParams(), copy=False); t7 = time.perf_counter()
         assert same(cg, c), "cs_chain_batch_gpu differs from cs_chain_batch"
-        rd = eng.seed_batch_device(d_b, d_o, n, bases.size, ca.Params())
+        tsd0 = time.perf_counter(); rd = eng.seed_batch_device(d_b, d_o, n, bases.size, ca.Params()); tsd1 = time.perf_counter()
         sd0 = chd.stats(); t8 = time.perf_counter(); dd = chd.chain_device(rd, d_o, ca.ChainParams()); t9 = time.perf_counter(); sd1 = chd.stats()
         assert same(ca.download_chains(eng, dd), c), "cs_chain_batch_device differs from cs_chain_batch"
         # the chain filter on the GPU: from the device chain call's result, then host arrays in and out
@@ -132,6 +135,8 @@ def run(n=200000, synth_mbp=0.0):
         cgm = al.regions_cigar(mk["cigar_reg_off"], mk["cigar_regs"], bases, off)
         ss0 = al.sam_stats(); (_, text), tsam = timed(lambda: al.regions_sam(mk, cgm, bases, off, names, reg_off=d_off)); ss1 = al.sam_stats()
         sd = {k: (ss1[k] - ss0[k]) / (MARK_RUNS + 1) for k in ss1}
+        if mflags == 0:
+            text_default = text
         out["marks + CIGAR -> SAM text (%s)" % label] = dict(tsam, device_span_ms=sd["kernel_ms"], bytes=len(text), bytes_per_read=len(text) / n, lines=int(sd["lines"]), unmapped=int(sd["unmapped"]),
                                                              xa_entries=int(sd["xa_entries"]), sa_entries=int(sd["sa_entries"]), launches=int(sd["launches"]),
                                                              note="host arrays in and out, the binding's copy of the text included")
@@ -171,11 +176,32 @@ def run(n=200000, synth_mbp=0.0):
                                        "includes the copies and host waits between them; not part of behind_seeding_reads_per_s"}
     t_all = sum(out[k]["ms"] for k in ("chain", "chain_filter", "extend_chains", "dedup_regions"))
     out["behind_seeding_reads_per_s"] = n / (t_all * 1e-3)
-    if tmpdir:
-        shutil.rmtree(tmpdir, ignore_errors=True)
+    out["seed (device call)"] = {"ms": 1e3 * (tsd1 - tsd0), "reads_per_s": n / (tsd1 - tsd0)}
     eng.free(d_b); eng.free(d_o)
     for x in (al, ald, chd, ch, eng, ix):
         x.close()
+    # the whole path in one call: a mapper of its own (engine, device chainer, aligner) on the same reads, default parameters
+    MAP_RUNS = 3
+    mp = ca.Mapper(PREFIX, 0)
+    mp.map_batch(bases, off, names)
+    s0 = mp.stats(); walls = []
+    for _ in range(MAP_RUNS):
+        ta = time.perf_counter(); _, mtext = mp.map_batch(bases, off, names); walls.append(time.perf_counter() - ta)
+    s1 = mp.stats()
+    mp.close()
+    assert mtext == text_default, "cs_map_batch's text differs from the separate stages' text"
+    per_m = lambda row: out[row]["median_ms_per_million_reads"] * n / 1e6
+    separate = {"seed": out["seed (device call)"]["ms"], "chain": out["chain_device"]["ms"], "filter": out["chain_filter (device)"]["ms"], "extend": out["extend_chains (device, compact)"]["ms"],
+                "download": out["extend_chains (device, compact)"]["download_regions_ms"], "dedup": out["dedup_regions"]["ms"], "mark": per_m("regions -> marks (default)"),
+                "cigar": per_m("marked regions -> CIGAR (default)"), "sam": per_m("marks + CIGAR -> SAM text (default)")}
+    wall = float(np.median(walls))
+    out["reads -> SAM text (cs_map_batch)"] = {"runs": MAP_RUNS, "ms": 1e3 * wall, "min_ms": 1e3 * min(walls), "max_ms": 1e3 * max(walls), "reads_per_s": n / wall,
+                                               "stage_ms": {k: (s1["stage_ms"][k] - s0["stage_ms"][k]) / MAP_RUNS for k in s1["stage_ms"]}, "separate_rows_ms": separate,
+                                               "separate_rows_sum_ms": sum(separate.values()), "bytes": len(mtext), "lines": (s1["lines"] - s0["lines"]) // MAP_RUNS,
+                                               "unmapped": (s1["unmapped"] - s0["unmapped"]) // MAP_RUNS, "equal_to_separate_stages_text": True,
+                                               "note": "host arrays in, the binding's copy of the text included; the separate rows of the tail stages include the binding's copies of their results"}
+    if tmpdir:
+        shutil.rmtree(tmpdir, ignore_errors=True)
     return out
 
 
