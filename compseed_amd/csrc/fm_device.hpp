@@ -110,6 +110,16 @@ template <> struct WaveCtrT<true> {
 	__device__ __forceinline__ void rec(bool) {}
 	__device__ __forceinline__ void hist(uint32_t) {}
 	__device__ __forceinline__ void steps(uint32_t n) { if ((threadIdx.x & 63u) == 0) { v[n == 0 ? 0 : n == 1 ? 1 : n == 2 ? 2 : n <= 4 ? 3 : n <= 8 ? 4 : n <= 16 ? 5 : n <= 32 ? 6 : 7] += 1u; v[8] += n; } }
+#elif defined(CS_WIN_CENSUS) // experiment build (make variant DEFS=-DCS_WIN_CENSUS): what the 64 lanes of bwd_win_kernel's wave loop are, summed over its iterations: slot 0 = iterations, 1 = free, 2 = stepping, 3 = walking but not yet on the clock, 4 = stopped with valid == true (CS_WIN_SETTLE: waiting to report), 5 = an invalid rank 0 kept for the successor
+	__device__ __forceinline__ void add(int, uint32_t) {}
+	__device__ __forceinline__ void addn(int, uint32_t) {}
+	__device__ __forceinline__ void rec(bool) {}
+	__device__ __forceinline__ void hist(uint32_t) {}
+	__device__ __forceinline__ void steps(uint32_t) {}
+	__device__ __forceinline__ void census(uint64_t fr, uint64_t st, uint64_t wt, uint64_t sv, uint64_t r0)
+	{
+		if ((threadIdx.x & 63u) == 0) { v[0] += 1u; v[1] += (uint32_t)__popcll(fr); v[2] += (uint32_t)__popcll(st); v[3] += (uint32_t)__popcll(wt); v[4] += (uint32_t)__popcll(sv); v[5] += (uint32_t)__popcll(r0); }
+	}
 #elif defined(CS_X2_HIST) // experiment build (make variant DEFS=-DCS_X2_HIST): the ten event slots hold a histogram of the interval sizes extend1 is asked for
 	__device__ __forceinline__ void add(int, uint32_t) {}
 	__device__ __forceinline__ void addn(int, uint32_t) {}
@@ -138,6 +148,7 @@ template <> struct WaveCtrT<false> {
 	__device__ __forceinline__ void rec(bool) {}
 	__device__ __forceinline__ void hist(uint32_t) {}
 	__device__ __forceinline__ void steps(uint32_t) {}
+	__device__ __forceinline__ void census(uint64_t, uint64_t, uint64_t, uint64_t, uint64_t) {}
 	__device__ __forceinline__ void flush(unsigned long long *, int) const {}
 };
 using WaveCtr = WaveCtrT<true>;

@@ -45,4 +45,33 @@ CS_HD inline uint32_t next_member(uint64_t set, uint32_t lane)
 // a set after the lanes `gone` left it; the same AND serves every lane of the wave, whichever call it belongs to
 CS_HD inline uint64_t release(uint64_t set, uint64_t gone) { return set & ~gone; }
 
+// ---- settling an end at the moment it stops (bwd_win_run, CS_WIN_SETTLE).  The ends of a call stop from the top of its set downward,
+// ties within one iteration, so the first-survivor rule needs one value per lane: fup, the s of the nearest valid end above it that has
+// already left the set (FUP_NONE: there is none).  stopv is the wave's ballot of "stopped in this iteration with valid == true".
+constexpr int32_t FUP_NONE = 0x7fffffff;
+// the valid ends of `lane`'s set above it that stop in this iteration
+CS_HD inline uint64_t stops_above(uint64_t stopv, uint64_t gmask, uint32_t lane) { return stopv & gmask & above(lane); }
+// the lane whose s a lane reads in this iteration: the nearest of stops_above, or itself
+CS_HD inline uint32_t settle_src(uint64_t hi, uint32_t lane) { return hi ? (uint32_t)__builtin_ctzll(hi) : lane; }
+// the s of the nearest valid end above: the one read from settle_src, or the carried one
+CS_HD inline int32_t settle_fn(uint64_t hi, int32_t s_src, int32_t fup) { return hi ? s_src : fup; }
+// does an end that stops valid at s report [s + 1, pend)?  The first-survivor rule as it stands (no valid end above, or it stopped
+// strictly earlier: a larger s) and the length filter of emit_smem.
+CS_HD inline bool settle_reports(int32_t s, int32_t fn, uint32_t pend, int32_t min_seed_len) { return s < fn && (int32_t)pend - (s + 1) >= min_seed_len; }
+// what a lane carries on: the members of the set under a valid end that stopped take its s
+CS_HD inline int32_t settle_carry(bool stopped, uint64_t hi, int32_t fn, int32_t fup) { return !stopped && hi ? fn : fup; }
+// of the lanes that stopped in this iteration (`out`), those that go back to F at once: all but the ones that wait to report
+CS_HD inline uint64_t settle_freed(uint64_t out, uint64_t reporting) { return out & ~reporting; }
+// a lane's set after `out` left it: a lane that left holds no set, whether it is free or waits to report
+CS_HD inline uint64_t settle_set(uint64_t gmask, uint64_t out, uint32_t lane) { return has(out, lane) ? 0ull : release(gmask, out); }
+// Are the lanes P that wait to report flushed now?  When `thresh` of them have gathered; when the next placement (need lanes, 65: the
+// queue is used up) is short of free lanes and they would make up for it; and when nothing else keeps the wave from its exit.
+CS_HD inline bool settle_flush(uint64_t F, uint64_t P, uint32_t need, uint32_t thresh)
+{
+	if (P == 0) return false;
+	if (count(P) >= thresh) return true;
+	if (count(F) >= need) return false;
+	return need > 64 ? (F | P) == ~0ull : count(F) + count(P) >= need;
+}
+
 } // namespace csls

@@ -210,10 +210,24 @@ __device__ __forceinline__ bool win_lane_init(const SplitArgs &A, PackedReader &
 #ifndef CS_WIN_RELEASE
 #define CS_WIN_RELEASE 1
 #endif
-// CS_WIN_BOOK: the loop's bookkeeping kept in lane masks -- same ballots in the same places, same rules (0: the loop as it was, for A/B
-// builds: make variant DEFS=-DCS_WIN_BOOK=0).
-#ifndef CS_WIN_BOOK
-#define CS_WIN_BOOK 1
+// CS_WIN_SETTLE: every end is settled in the iteration in which it stops, and its lane goes back to F at once (lane_sets.hpp, "settling
+// an end").  The ends of a call stop from the top of its set downward -- all walking lanes of a call extend [clk, end) on one clock, a
+// longer end has at most the occurrences of a shorter one, window lanes join top-down and cannot die before the LEP lanes have joined
+// (their strings are substrings of every stored LEP until then), and a stopped lane's s never changes -- so when a lane stops, the
+// nearest valid end above it either stops in the same iteration or stopped earlier, and a lane needs to carry one value, fup, the s of
+// the nearest valid end above it that has left.  An end that reports stays as "pending" -- out of its call's set, so nothing consults it,
+// holding e, s, pend, r and kind -- until the wave flushes all pending lanes in one block (emit_smem + wave_push off the common
+// iteration): when CS_WIN_PEND of them have gathered, when a placement is short of the lanes they hold, and before the exit.  The call's
+// successor (chain_round1: a function of the task record alone) is pushed at placement by the top lane of the new set, so no lane has to
+// stay to a call's end and a call has no end event: it is over when its set is empty.  Lanes whose filter or jump lookup fails leave at
+// placement.  0: the loop as it was (rule applied at the call's end, rank 0 kept for the successor), for A/B builds
+// (make variant DEFS=-DCS_WIN_SETTLE=0); CS_WIN_RELEASE applies to that form only.  Both forms keep their bookkeeping in lane masks;
+// the older copy of the loop that went through 0/1 registers (CS_WIN_BOOK = 0) is gone.
+#ifndef CS_WIN_SETTLE
+#define CS_WIN_SETTLE 1
+#endif
+#ifndef CS_WIN_PEND
+#define CS_WIN_PEND 8
 #endif
 __device__ __forceinline__ uint64_t lane_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); } // __ballot without the trip through a 0/1 register
 template <class WC>
@@ -224,13 +238,20 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 	const uint32_t lane = threadIdx.x & 63u;
 	uint64_t gmask = 0;
 	bool walking = false, valid = false;
-	// Per-lane state is kept narrow (the kernel runs at the register limit of its six waves per SIMD): the call's pivot and forward end
-	// share a word (both 16 bits), the kind carries in bit 2 whether this lane is NOT its call's rank 0 (WIN_TAIL) -- early release never
-	// takes a call's rank 0, so that is the same lane from placement to the call's end, whatever left the set in between --, a lane that
-	// stops keeps its position in s (a stopped lane's s is the f of the scheme above: nothing moves it any more), and the extensions and
-	// jump-table credits are counted in 32 bits and added to the kernel's 64-bit counters once, at the end.
+	// Per-lane state is kept narrow (the kernel runs at the register limit of its six waves per SIMD): a lane that stops keeps its position
+	// in s (a stopped lane's s is the f of the scheme above: nothing moves it any more), and the extensions and jump-table credits are
+	// counted in 32 bits and added to the kernel's 64-bit counters once, at the end.
+#if CS_WIN_SETTLE
+	int fup = csls::FUP_NONE;  // the s of the nearest valid end above this lane that has left its set
+	uint64_t P = 0;            // wave-uniform: the lanes that wait to report
+	uint32_t r = 0, kind = 0, min_intv = 1, pend = 0, nq = 0, nh = 0;
+#else
+	// The call's pivot and forward end share a word (both 16 bits), and the kind carries in bit 2 whether this lane is NOT its call's rank 0
+	// (WIN_TAIL) -- early release never takes a call's rank 0, so that is the same lane from placement to the call's end, whatever left the
+	// set in between.
 	constexpr uint32_t WIN_TAIL = 4u;
 	uint32_t r = 0, kind = 0, min_intv = 1, pend = 0, retx = 0, nq = 0, nh = 0;
+#endif
 	int s = 0, clk = 0;
 	Intv e = {0, 0, 0};
 	PackedReader rd;
@@ -238,59 +259,93 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 	// (18 + n of the call at the head once known, 19 before -- no call takes fewer --, 65 when the queue is used up)
 	uint64_t F = ~0ull, batch_base = 0, avail_m = 0; bool exhausted = false, place = true; uint32_t need = WIN_LANES + 1;
 	for (;;) {
-		if (place && csls::count(F) >= need) {
-			bool fresh = false; uint64_t t = 0;
-			for (;;) {
-				if (avail_m == 0) {
-					if (exhausted) { need = 65; break; }
-					unsigned long long base = 0;
-					if (lane == 0) base = atomicAdd(ctr, 64ull);
-					base = (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)base) | (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32;
-					if (base >= n_tasks) { exhausted = true; need = 65; break; }
-					const uint64_t slot = base + lane;
-					uint32_t cls = 0xffffffffu, n = 0;
-					if (slot < n_tasks) { cls = bq[slot].cls; n = bq[slot].n; }
-					avail_m = __ballot(cls == 4u || cls == 5u);  // (n <= WIN_G64_LEPS: 18 + n <= 64)
-					batch_base = base;
-					__builtin_amdgcn_wave_barrier();             // (the previous draw's widths have all been read)
-					slot_w[lane] = (uint8_t)(WIN_LANES + n);
-					__builtin_amdgcn_wave_barrier();
-					continue;
+		while (place) { // wave-uniform; repeats only after lanes came back to F inside it (duds of a placement, a flush)
+			place = false;
+			if (csls::count(F) >= need) {
+				bool fresh = false; uint64_t t = 0;
+				for (;;) {
+					if (avail_m == 0) {
+						if (exhausted) { need = 65; break; }
+						unsigned long long base = 0;
+						if (lane == 0) base = atomicAdd(ctr, 64ull);
+						base = (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)base) | (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32;
+						if (base >= n_tasks) { exhausted = true; need = 65; break; }
+						const uint64_t slot = base + lane;
+						uint32_t cls = 0xffffffffu, n = 0;
+						if (slot < n_tasks) { cls = bq[slot].cls; n = bq[slot].n; }
+						avail_m = __ballot(cls == 4u || cls == 5u);  // (n <= WIN_G64_LEPS: 18 + n <= 64)
+						batch_base = base;
+						__builtin_amdgcn_wave_barrier();             // (the previous draw's widths have all been read)
+						slot_w[lane] = (uint8_t)(WIN_LANES + n);
+						__builtin_amdgcn_wave_barrier();
+						continue;
+					}
+					const int k = __ffsll((long long)avail_m) - 1;
+					const uint32_t w = __builtin_amdgcn_readfirstlane((uint32_t)slot_w[k]);
+					if (csls::count(F) < w) { need = w; break; } // the head of the queue waits for lanes; nothing overtakes it
+					const bool join = csls::takes(F, lane, w);
+					const uint64_t take = __ballot(join);
+					if (join) { gmask = take; t = batch_base + (uint64_t)k; fresh = true; }
+					F = csls::release(F, take); avail_m &= avail_m - 1; need = WIN_LANES + 1;
 				}
-				const int k = __ffsll((long long)avail_m) - 1;
-				const uint32_t w = __builtin_amdgcn_readfirstlane((uint32_t)slot_w[k]);
-				if (csls::count(F) < w) { need = w; break; } // the head of the queue waits for lanes; nothing overtakes it
-				const bool join = csls::takes(F, lane, w);
-				const uint64_t take = __ballot(join);
-				if (join) { gmask = take; t = batch_base + (uint64_t)k; fresh = true; }
-				F = csls::release(F, take); avail_m &= avail_m - 1; need = WIN_LANES + 1;
-			}
-			if (fresh) {
-				const uint32_t gl = csls::rank_in(gmask, lane);
-				BTask bt = bq[t];
-				const int xp = bt.x, ret = bt.ret;
-				r = bt.r; kind = (uint32_t)(bt.mi_kind >> 14) | (gl ? WIN_TAIL : 0u); min_intv = bt.mi_kind & 0x3fffu; retx = (uint32_t)ret | (uint32_t)xp << 16;
-				const uint64_t rb = A.off[r];
-				rd.start(A.seqp, rb, r, xp);
-				if (gl < (uint32_t)WIN_LANES) {
-					unsigned long long q0 = 0, h0 = 0;
-					valid = win_lane_init(A, rd, gl, xp, ret, min_intv, e, pend, s, q0, h0, W);
-					nq += (uint32_t)q0; nh += (uint32_t)h0;
-				} else { // (the set has exactly 18 + n members: every rank from 18 on has its LEP)
-					unpack_lep(A.lep[(size_t)t * A.lep_stride + ((int)gl - WIN_LANES)], e, pend); s = xp - 1; wc_add(W, EV_LEP);
-					valid = true;
+#if CS_WIN_SETTLE
+				uint64_t push1 = FTASK_NONE;
+#endif
+				if (fresh) {
+					const uint32_t gl = csls::rank_in(gmask, lane);
+					BTask bt = bq[t];
+					const int xp = bt.x, ret = bt.ret;
+					r = bt.r; min_intv = bt.mi_kind & 0x3fffu;
+					const uint64_t rb = A.off[r];
+#if CS_WIN_SETTLE
+					kind = (uint32_t)(bt.mi_kind >> 14); fup = csls::FUP_NONE;
+					if (kind == TK_ROUND1 && (gmask & csls::above(lane)) == 0) { // the set's top lane (always an LEP lane) pushes the call's successor
+						rd.start(A.seqp, rb, r, ret);
+						push1 = chain_round1(rd, r, (int)(A.off[r + 1] - rb), ret, xp);
+					}
+#else
+					kind = (uint32_t)(bt.mi_kind >> 14) | (gl ? WIN_TAIL : 0u); retx = (uint32_t)ret | (uint32_t)xp << 16;
+#endif
+					rd.start(A.seqp, rb, r, xp);
+					if (gl < (uint32_t)WIN_LANES) {
+						unsigned long long q0 = 0, h0 = 0;
+						valid = win_lane_init(A, rd, gl, xp, ret, min_intv, e, pend, s, q0, h0, W);
+						nq += (uint32_t)q0; nh += (uint32_t)h0;
+					} else { // (the set has exactly 18 + n members: every rank from 18 on has its LEP)
+						unpack_lep(A.lep[(size_t)t * A.lep_stride + ((int)gl - WIN_LANES)], e, pend); s = xp - 1; wc_add(W, EV_LEP);
+						valid = true;
+					}
+					walking = valid;
+					clk = xp + WIN_LANES - A.jump_k - 1; // the base in front of the last window lane, the first to join
+					if (clk < xp - 1) clk = xp - 1;        // (the LEP lanes join at the pivot)
 				}
-				walking = valid;
-				clk = xp + WIN_LANES - A.jump_k - 1; // the base in front of the last window lane, the first to join
-				if (clk < xp - 1) clk = xp - 1;        // (the LEP lanes join at the pivot)
+#if CS_WIN_SETTLE
+				wave_push<32>(O, push1 != FTASK_NONE, push1, A);
+				const uint64_t dud = lane_mask(fresh && !valid); // window lanes whose filter or jump lookup failed never walk: back to F
+				if (dud) { F |= dud; gmask = csls::settle_set(gmask, dud, lane); place = true; }
+#endif
 			}
+#if CS_WIN_SETTLE
+			if (csls::settle_flush(F, P, need, CS_WIN_PEND)) { // the lanes that wait to report, all at once
+				uint64_t push0 = FTASK_NONE, aux0 = AUX_NONE;
+				if (csls::has(P, lane)) push0 = emit_smem(A, r, kind, e, s + 1, pend, aux0);
+				wave_push<32>(O, push0 != FTASK_NONE, push0, A, aux0);
+				F |= P; P = 0; place = true;
+			}
+#endif
 		}
-		place = false;
 		if (exhausted && avail_m == 0 && F == ~0ull) break; // wave-uniform exit
 #ifdef CS_STEP_HIST
 		W.steps((uint32_t)__popcll(__ballot(gmask != 0 && walking && s == clk)));
 #endif
-#if CS_WIN_BOOK
+#ifdef CS_WIN_CENSUS
+#if CS_WIN_SETTLE
+		W.census(F, __ballot(walking && s == clk), __ballot(walking && s != clk), P, 0ull);
+#else
+		W.census(F, __ballot(gmask != 0 && walking && s == clk), __ballot(gmask != 0 && walking && s != clk), __ballot(gmask != 0 && !walking && valid),
+		         __ballot(gmask != 0 && !valid && kind < WIN_TAIL));
+#endif
+#endif
 		// One clock per call: position clk is the read base every walking lane prepends in this iteration.  A lane joins when the clock
 		// reaches the base in front of its match (the window lanes start staggered, the LEPs at the pivot), so all lanes that walk hold
 		// matches with the SAME start, and the equal-size rule of bwt.c:337-340 applies to them as it stands: a match with as many
@@ -309,6 +364,30 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 				if (y.x2 < min_intv) walking = false; else { e = y; --s; }
 			}
 		}
+#if CS_WIN_SETTLE
+		bool stopv = step && !walking; // stopped in this iteration with valid == true (a lane that walks is valid)
+		if ((clk & 3) == 0) { // (every fourth step is enough: a lane that could have stopped earlier only repeats a few extensions)
+			const bool surv = step && walking;
+			const uint64_t hi = lane_mask(surv) & gmask & csls::above(lane);
+			const uint32_t ax2 = __shfl(e.x2, hi ? (int)__builtin_ctzll(hi) : (int)lane);
+			if (surv && hi != 0 && ax2 == e.x2) walking = false; // (not valid any more: it leaves below without a word)
+		}
+		--clk;
+		const uint64_t out = lane_mask(step && !walking); // the lanes that stopped in this iteration: every one of them leaves its set now
+		if (out) { // (some lane of the wave stops in one iteration of a few: the rule and the masks stay off the common path)
+			const uint64_t stopm = lane_mask(stopv);
+			bool reports = false;
+			if (stopm) {
+				const uint64_t hi = csls::stops_above(stopm, gmask, lane);
+				const int fn = csls::settle_fn(hi, __shfl(s, (int)csls::settle_src(hi, lane)), fup);
+				reports = stopv && csls::settle_reports(s, fn, pend, A.min_seed_len);
+				fup = csls::settle_carry(stopv, hi, fn, fup);
+			}
+			const uint64_t pm = lane_mask(reports);
+			P |= pm; F |= csls::settle_freed(out, pm); place = true;
+			gmask = csls::settle_set(gmask, out, lane);
+		}
+#else
 		if ((clk & 3) == 0) { // (every fourth step is enough: a lane that could have stopped earlier only repeats a few extensions)
 			const bool surv = step && walking;
 			const uint64_t hi = lane_mask(surv) & gmask & csls::above(lane);
@@ -338,49 +417,6 @@ __device__ __forceinline__ void bwd_win_run(const SplitArgs &A, const BTask *bq,
 		if (gone) {
 			F |= gone; place = true;
 			gmask = csls::has(gone, lane) ? 0ull : csls::release(gmask, gone);
-		}
-#else
-		uint64_t push0 = FTASK_NONE, push1 = FTASK_NONE, aux0 = AUX_NONE;
-		bool ended = false;
-		if (gmask != 0) {
-			// (the loop as it was before CS_WIN_BOOK: every lane predicate through a 0/1 register, defaults of the pushes set up every iteration)
-			const bool step = walking && s == clk;
-			if (step) {
-				uint32_t b = s < 0 ? 4u : rd.at(s);
-				if (b > 3) walking = false;
-				else {
-					Intv y = bwd_extend(ix, l2p1, e, (int)b, W); ++nq;
-					if (y.x2 < min_intv) walking = false; else { e = y; --s; }
-				}
-			}
-			if ((clk & 3) == 0) { // (every fourth step is enough: a lane that could have stopped earlier only repeats a few extensions)
-				const bool surv = step && walking;
-				const uint64_t lm = __ballot(surv) & gmask;
-				const uint64_t ax2 = __shfl(e.x2, (int)csls::next_member(lm, lane));
-				if (surv && (lm & csls::above(lane)) && ax2 == e.x2) { walking = false; valid = false; }
-			}
-			--clk;
-			if ((__ballot(walking) & gmask) == 0) { // all ends of this call are settled: apply the first-survivor rule
-				const uint64_t vm = __ballot(valid) & gmask, higher = vm & csls::above(lane);
-				const int fn = __shfl(s, (int)csls::next_member(vm, lane));
-				if (valid && (higher == 0 || s < fn)) push0 = emit_smem(A, r, kind & 3u, e, s + 1, pend, aux0);
-				if (kind == TK_ROUND1) push1 = chain_round1(rd, r, (int)(A.off[r + 1] - A.off[r]), (int)(retx & 0xffffu), (int)(retx >> 16));
-				ended = true; valid = false;
-			}
-		}
-		// lanes that go back to F: those of the calls that ended, and (CS_WIN_RELEASE) those that can no longer matter
-#if CS_WIN_RELEASE
-		const uint64_t gone = __ballot(ended || (gmask != 0 && !valid && kind >= WIN_TAIL));
-#else
-		const uint64_t gone = __ballot(ended);
-#endif
-		if (gone) {
-			F |= gone; place = true;
-			gmask = csls::has(gone, lane) ? 0ull : csls::release(gmask, gone);
-		}
-		if (__ballot((push0 & push1) != FTASK_NONE)) { // (a call ends once in ~20 iterations: keep the dispenser code off the common path)
-			wave_push<32>(O, push0 != FTASK_NONE, push0, A, aux0);
-			wave_push<32>(O, push1 != FTASK_NONE, push1, A);
 		}
 #endif
 	}
