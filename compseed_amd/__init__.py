@@ -12,7 +12,7 @@ from .binding import (CSError, Engine, EngineOptions, Index, Params, Result, Sta
                       ChainStats, CHAIN_TREE_ONLY, download_chains, FltStats, FLT_WAVE_ONLY, ALN_DEV_COMPACT, EXT_VECTOR_ZDROP, download_regions,
                       MarkParams, MarkStats, MARK_DT, MARK_ALL, MARK_NO_MULTI, MARK_KEEP_SUPP_MAPQ, MARK_NO_LIGHT_PATH, MARK_FROM_HBM,
                       SamParams, SamStats, SAM_SOFTCLIP, SAM_WAVE_ONLY,
-                      Mapper, MapParams, MapStats, map_params_split, MAP_ALL, MAP_NO_MULTI, MAP_KEEP_SUPP_MAPQ, MAP_SOFTCLIP, MAP_STAGES)
+                      Mapper, MapParams, MapStats, map_params_split, MAP_ALL, MAP_NO_MULTI, MAP_KEEP_SUPP_MAPQ, MAP_SOFTCLIP, MAP_STAGES, MAP_MAX_IN_FLIGHT)
 
 __all__ = ["CSError", "Engine", "EngineOptions", "Index", "Params", "Result", "Stats", "lib_path", "load_library", "build_library",
            "disable_mask", "pinned_array", "pack_reads", "RefSeq", "Reader", "Chainer", "ChainParams", "FltParams", "DedupParams", "build_index_from_fasta", "unpack_mems16", "unpack_mems8", "unpack_mems", "RESULT_LEAN", "MEM_FULL32", "MEM_PACKED16", "MEM_LEAN8", "MEM8_DT", "INTV_DT", "SEED_DT", "MEM16_DT",
@@ -20,4 +20,4 @@ __all__ = ["CSError", "Engine", "EngineOptions", "Index", "Params", "Result", "S
            "ChainStats", "CHAIN_TREE_ONLY", "download_chains", "FltStats", "FLT_WAVE_ONLY", "ALN_DEV_COMPACT", "EXT_VECTOR_ZDROP", "download_regions",
            "MarkParams", "MarkStats", "MARK_DT", "MARK_ALL", "MARK_NO_MULTI", "MARK_KEEP_SUPP_MAPQ", "MARK_NO_LIGHT_PATH", "MARK_FROM_HBM",
            "SamParams", "SamStats", "SAM_SOFTCLIP", "SAM_WAVE_ONLY",
-           "Mapper", "MapParams", "MapStats", "map_params_split", "MAP_ALL", "MAP_NO_MULTI", "MAP_KEEP_SUPP_MAPQ", "MAP_SOFTCLIP", "MAP_STAGES"]
+           "Mapper", "MapParams", "MapStats", "map_params_split", "MAP_ALL", "MAP_NO_MULTI", "MAP_KEEP_SUPP_MAPQ", "MAP_SOFTCLIP", "MAP_STAGES", "MAP_MAX_IN_FLIGHT"]

@@ -24,7 +24,8 @@ SYMBOLS = ["cs_last_error", "cs_version", "cs_params_default", "cs_index_load", 
            "cs_extender_upload", "cs_extend_batch_resident", "cs_engine_memory", "cs_aln_params_default", "cs_aligner_create", "cs_aligner_destroy", "cs_extend_chains", "cs_extend_chains_device", "cs_dedup_params_default", "cs_dedup_regions", "cs_aligner_stats",
            "cs_regions_cigar", "cs_cigar_stats", "cs_mark_params_default", "cs_regions_mark", "cs_mark_stats",
            "cs_regions_sam", "cs_sam_header", "cs_sam_stats", "cs_reader_next_chunk",
-           "cs_map_params_default", "cs_map_params_split", "cs_mapper_create", "cs_mapper_destroy", "cs_map_batch", "cs_mapper_header", "cs_mapper_stats", "cs_mapper_engine_stats"]
+           "cs_map_params_default", "cs_map_params_split", "cs_mapper_create", "cs_mapper_destroy", "cs_map_batch", "cs_mapper_header", "cs_mapper_stats", "cs_mapper_engine_stats",
+           "cs_map_submit", "cs_map_collect", "cs_mapper_in_flight"]
 
 
 class CSError(RuntimeError):
@@ -253,6 +254,7 @@ class SamStats(C.Structure):
 
 # cs_mapper_t: reads to SAM text in one call
 MAP_ALL, MAP_NO_MULTI, MAP_KEEP_SUPP_MAPQ, MAP_SOFTCLIP = 1, 2, 4, 8
+MAP_MAX_IN_FLIGHT = 3                                                     # CS_MAP_MAX_IN_FLIGHT
 MAP_STAGES = ("upload", "seed", "chain", "filter", "extend", "download", "dedup", "mark", "cigar", "sam", "total")   # CS_MAP_T_*
 
 
@@ -508,6 +510,10 @@ def load_library():
     L.cs_mapper_destroy.argtypes = [vp]
     L.cs_mapper_destroy.restype = None
     L.cs_map_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(CSamResult)]
+    if hasattr(L, "cs_map_submit"):   # (an older build given through CS_LIB / bench.py --lib for an A/B run lacks the three; calling them there raises)
+        L.cs_map_submit.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i64]
+        L.cs_map_collect.argtypes = [vp, C.POINTER(CSamResult)]
+        L.cs_mapper_in_flight.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.cs_mapper_header.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cs_mapper_stats.argtypes = [vp, C.POINTER(MapStats)]
     L.cs_mapper_engine_stats.argtypes = [vp, C.POINTER(Stats)]
@@ -1285,12 +1291,13 @@ class Mapper:
     def __init__(self, prefix, device=0, engine_options=None, params=None):
         self.L = load_library()
         self.h = C.c_void_p()
+        self._flying = []                                                   # the arrays of the batches submitted and not yet collected
         _check(self.L.cs_mapper_create(os.fsencode(prefix), int(device), C.byref(engine_options) if engine_options is not None else None,
                                        C.byref(params) if params is not None else None, C.byref(self.h)))
 
-    def map_batch(self, bases, read_offsets, names, quals=None, comments=None, id_base=0):
-        """cs_map_batch: `names` / `comments` pairs (bytes as uint8, uint64 CSR offsets) or lists of bytes, `quals` uint8 at the bases' offsets,
-        `id_base` the number of reads before this batch -> (text_off, text) as Aligner.regions_sam returns them"""
+    @staticmethod
+    def _arrays(bases, read_offsets, names, quals, comments):
+        """the arrays of a batch as the library takes them, and its pointer arguments (n_reads .. comment_off)"""
         def pair(x):
             if isinstance(x, (list, tuple)) and (len(x) != 2 or isinstance(x[0], (bytes, str))):
                 x = [y.encode() if isinstance(y, str) else y for y in x]
@@ -1304,9 +1311,41 @@ class Mapper:
         nm, no = pair(names)
         cm, cmo = pair(comments) if comments is not None else (None, None)
         ptr = lambda x: x.ctypes.data if x is not None and x.size else None
+        return (bases, ro, q, nm, no, cm, cmo), (ro.size - 1, ptr(bases), ptr(ro), ptr(q), nm.ctypes.data, ptr(no), cm.ctypes.data if cm is not None else None, ptr(cmo))
+
+    def map_batch(self, bases, read_offsets, names, quals=None, comments=None, id_base=0):
+        """cs_map_batch: `names` / `comments` pairs (bytes as uint8, uint64 CSR offsets) or lists of bytes, `quals` uint8 at the bases' offsets,
+        `id_base` the number of reads before this batch -> (text_off, text) as Aligner.regions_sam returns them"""
+        _keep, args = self._arrays(bases, read_offsets, names, quals, comments)
         out = CSamResult()
-        _check(self.L.cs_map_batch(self.h, ro.size - 1, ptr(bases), ptr(ro), ptr(q), nm.ctypes.data, ptr(no), cm.ctypes.data if cm is not None else None, ptr(cmo), int(id_base), C.byref(out)))
+        _check(self.L.cs_map_batch(self.h, *args, int(id_base), C.byref(out)))
         return _view(out.text_off, "<u8", int(out.n_reads) + 1, True), (C.string_at(out.text, int(out.n_bytes)) if out.n_bytes else b"")
+
+    def submit(self, bases, read_offsets, names, quals=None, comments=None, id_base=0):
+        """cs_map_submit: map_batch's arguments; queues the batch and returns (at most MAP_MAX_IN_FLIGHT uncollected).  The mapper keeps
+        references to the batch's arrays until its collect."""
+        keep, args = self._arrays(bases, read_offsets, names, quals, comments)
+        _check(self.L.cs_map_submit(self.h, *args, int(id_base)))
+        self._flying.append(keep)
+
+    def collect(self, copy=True):
+        """cs_map_collect: blocks until the OLDEST submitted batch is complete -> (text_off, text) as map_batch returns them; with copy=False
+        text_off and text (uint8) are views of the mapper's arrays, valid until the next collect, map_batch or close.  A batch that failed
+        in a stage raises here, and is collected by that."""
+        out = CSamResult()
+        rc = self.L.cs_map_collect(self.h, C.byref(out))
+        if self._flying:
+            self._flying.pop(0)                                             # (a batch's error collects it too)
+        _check(rc)
+        if not copy:
+            return _view(out.text_off, "<u8", int(out.n_reads) + 1, False), _view(out.text, np.uint8, int(out.n_bytes), False)
+        return _view(out.text_off, "<u8", int(out.n_reads) + 1, True), (C.string_at(out.text, int(out.n_bytes)) if out.n_bytes else b"")
+
+    def in_flight(self):
+        """cs_mapper_in_flight -> (submitted and not yet collected, how many of those are complete)"""
+        s, f = C.c_int(), C.c_int()
+        _check(self.L.cs_mapper_in_flight(self.h, C.byref(s), C.byref(f)))
+        return int(s.value), int(f.value)
 
     def header(self, rg_line=None):
         """cs_mapper_header: the @SQ lines and, where given, the @RG line (as -R takes it: tabs written as a backslash and a t)"""
@@ -1334,8 +1373,9 @@ class Mapper:
 
     def close(self):
         if self.h:
-            self.L.cs_mapper_destroy(self.h)
+            self.L.cs_mapper_destroy(self.h)                                # (waits for the batches in flight)
             self.h = C.c_void_p()
+            self._flying = []
 
     def __del__(self):
         try:

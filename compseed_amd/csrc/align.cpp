@@ -209,6 +209,9 @@ extern "C" int cs_sam_stats(const cs_aligner_t *A, cs_sam_stats_t *st)
 	if (!A || !st) return cs_fail_(CS_EINVAL, "null argument");
 	return cs_sam_gpu_stats_(A->sam, st);
 }
+// the result arrays of the last cs_regions_sam / cs_dedup_regions against the caller's (cs_internal.hpp): the mapper's streamed batches
+void cs_aligner_sam_exchange_(cs_aligner_t *A, std::vector<uint64_t> &text_off, std::vector<char> &text) { cs_sam_gpu_exchange_(A->sam, text_off, text); }
+void cs_aligner_dedup_exchange_(cs_aligner_t *A, std::vector<uint64_t> &reg_off, std::vector<cs_alnreg_t> &regs) { A->dd_off.swap(reg_off); A->dd_regs.swap(regs); }
 // bwa_print_sam_hdr (bwalib/bwa.c:406-427) for the aligner's contigs, behind it the read-group line unescaped as bwa_set_rg / bwa_escape do (:429-476)
 extern "C" int cs_sam_header(const cs_aligner_t *A, const char *rg_line, char *buf, size_t cap, size_t *need)
 {

@@ -11,7 +11,7 @@
 // that use it: the seeding flags -t -k -r -y -c -s -K are honoured, the flags of the other stages are accepted and ignored, the seeds
 // are written (--dump-seeds FILE) and the reference's exit counters printed (display_profile, main.cpp:203-214).
 // With --sam the flags are parsed as main.cpp:233-330 parses them and update_a (main.cpp:130-143) is applied; one cs_mapper_t per GPU
-// maps each chunk's shard while the next chunk is read, and FILE receives the header (bwa_print_sam_hdr, with -R's line) and every chunk's
+// takes each chunk's shard as a submitted batch, up to CS_MAP_MAX_IN_FLIGHT chunks in flight while the next is read, and FILE receives the header (bwa_print_sam_hdr, with -R's line) and every chunk's
 // text in read order: the file the reference's program writes.  Honoured: -k -r -y -c -s -K -t, -w -d -D -W -N -G -X -T -A -B,
 // -O / -E / -L / -h a[,b], -Q -a -M -q -Y -C -R -v; -o / -f / -1 are accepted and ignored (as in the seeding mode: making -o an alias of
 // --sam would change what existing command lines do).  Refused with exit status 1 before the GPU is touched, because the library's stages
@@ -24,6 +24,7 @@
 #include <cctype>
 #include <chrono>
 #include <cstdio>
+#include <deque>
 #include <functional>
 #include <thread>
 #include <cstdlib>
@@ -334,7 +335,9 @@ void show_params(const SamOpts &o)
 }
 
 // a shard of a chunk: a contiguous read range with its offset arrays rebased to 0 (they live until the shard's text has been written)
-struct Shard { int64_t r0 = 0, n = 0; std::vector<uint64_t> off, name_off, comment_off; cs_sam_result_t res{}; int rc = 0; std::string err; };
+struct Shard { int64_t r0 = 0, n = 0; std::vector<uint64_t> off, name_off, comment_off; };
+// a chunk in flight: its bytes (copies: the reader's two buffer sets are fewer than the chunks in flight) and its shard per mapper
+struct Flying { int64_t n = 0; std::vector<uint8_t> bases, quals; std::vector<char> names, comments; std::vector<Shard> shards; };
 } // namespace
 
 static int sam_main(int argc, char **argv)
@@ -373,45 +376,51 @@ static int sam_main(int argc, char **argv)
 	cs_reader_t *rd = nullptr;
 	if (cs_reader_open(o.pos[1], chunk_bases, &rd)) { fprintf(stderr, "[E::main] %s\n", cs_last_error()); return 1; }
 
-	// The reference's three-step pipeline (main.cpp:438): chunk n+1 is read while chunk n is mapped -- every mapper on a thread of its own
-	// over a contiguous read range of the chunk -- and the texts are written in shard order, chunk by chunk.
-	auto read_chunk = [&](cs_read_chunk_t &c) -> bool {
-		if (cs_reader_next_chunk(rd, &c)) { fprintf(stderr, "[E::process] %s\n", cs_last_error()); exit(1); }
-		return c.n_reads > 0;
-	};
-	auto map_shard = [&](const cs_read_chunk_t &c, int g, Shard &s) {
-		s.r0 = c.n_reads * g / n_gpus; s.n = c.n_reads * (g + 1) / n_gpus - s.r0;
-		const bool cm = o.copy_comment && c.comment_off;                   // -C (main.cpp:77-81)
-		s.off.resize((size_t)s.n + 1); s.name_off.resize((size_t)s.n + 1); s.comment_off.resize(cm ? (size_t)s.n + 1 : 0);
-		for (int64_t r = 0; r <= s.n; ++r) {
-			s.off[(size_t)r] = c.offsets[s.r0 + r] - c.offsets[s.r0]; s.name_off[(size_t)r] = c.name_off[s.r0 + r] - c.name_off[s.r0];
-			if (cm) s.comment_off[(size_t)r] = c.comment_off[s.r0 + r] - c.comment_off[s.r0];
-		}
-		s.rc = cs_map_batch(mp[(size_t)g], s.n, c.bases + c.offsets[s.r0], s.off.data(), c.quals ? c.quals + c.offsets[s.r0] : nullptr, c.names + c.name_off[s.r0], s.name_off.data(),
-		                    cm ? c.comments + c.comment_off[s.r0] : nullptr, cm ? s.comment_off.data() : nullptr, (int64_t)c.first_id + s.r0, &s.res);
-		if (s.rc) s.err = cs_last_error();                                 // (the message is the calling thread's)
-	};
-	cs_read_chunk_t ch[2];
-	std::vector<Shard> shards((size_t)n_gpus);
+	// The reference's three-step pipeline (main.cpp:438) with the mappers' own threads behind it: every chunk is cut into one shard per
+	// mapper and SUBMITTED (cs_map_submit), up to CS_MAP_MAX_IN_FLIGHT chunks kept in flight; this thread reads the next chunk meanwhile,
+	// then collects the oldest chunk's shards in mapper order and writes their texts -- the file in read order, chunk by chunk.  The
+	// reader has two buffer sets and a chunk must stay untouched until it is collected, so a chunk in flight is a copy of its bytes.
+	auto bail = [&]() { for (cs_mapper_t *m : mp) cs_mapper_destroy(m); return 1; };   // (waits for what is in flight: no worker outlives main)
+	std::deque<Flying> fl;
 	uint64_t n_reads = 0;
 	const auto t0 = std::chrono::steady_clock::now();
-	int cur = 0;
-	bool have = read_chunk(ch[0]);
-	while (have) {
-		const cs_read_chunk_t &c = ch[cur];
-		std::vector<std::thread> th;
-		for (int g = 1; g < n_gpus; ++g) th.emplace_back(map_shard, std::cref(c), g, std::ref(shards[(size_t)g]));
-		std::thread first(map_shard, std::cref(c), 0, std::ref(shards[0]));
-		have = read_chunk(ch[cur ^ 1]);
-		first.join();
-		for (std::thread &t : th) t.join();
-		for (int g = 0; g < n_gpus; ++g) {
-			const Shard &s = shards[(size_t)g];
-			if (s.rc) { fprintf(stderr, "[E::main] GPU %d: %s\n", g, s.err.c_str()); return 1; }
-			if (s.res.n_bytes && fwrite(s.res.text, 1, (size_t)s.res.n_bytes, fo) != (size_t)s.res.n_bytes) { fprintf(stderr, "[E::main] cannot write %s\n", o.sam); return 1; }
+	for (bool have = true;;) {
+		while (have && fl.size() < (size_t)CS_MAP_MAX_IN_FLIGHT) {
+			cs_read_chunk_t c;
+			if (cs_reader_next_chunk(rd, &c)) { fprintf(stderr, "[E::process] %s\n", cs_last_error()); return bail(); }
+			if (!(have = c.n_reads > 0)) break;
+			fl.emplace_back();
+			Flying &f = fl.back();
+			const bool cm = o.copy_comment && c.comment_off;               // -C (main.cpp:77-81)
+			f.n = c.n_reads;
+			f.bases.assign(c.bases, c.bases + c.offsets[c.n_reads]);
+			if (c.quals) f.quals.assign(c.quals, c.quals + c.offsets[c.n_reads]);
+			f.names.assign(c.names, c.names + c.name_off[c.n_reads]);
+			if (cm) f.comments.assign(c.comments, c.comments + c.comment_off[c.n_reads]);
+			f.shards.resize((size_t)n_gpus);
+			for (int g = 0; g < n_gpus; ++g) {
+				Shard &s = f.shards[(size_t)g];
+				s.r0 = c.n_reads * g / n_gpus; s.n = c.n_reads * (g + 1) / n_gpus - s.r0;
+				s.off.resize((size_t)s.n + 1); s.name_off.resize((size_t)s.n + 1); s.comment_off.resize(cm ? (size_t)s.n + 1 : 0);
+				for (int64_t r = 0; r <= s.n; ++r) {
+					s.off[(size_t)r] = c.offsets[s.r0 + r] - c.offsets[s.r0]; s.name_off[(size_t)r] = c.name_off[s.r0 + r] - c.name_off[s.r0];
+					if (cm) s.comment_off[(size_t)r] = c.comment_off[s.r0 + r] - c.comment_off[s.r0];
+				}
+				if (cs_map_submit(mp[(size_t)g], s.n, f.bases.data() + c.offsets[s.r0], s.off.data(), c.quals ? f.quals.data() + c.offsets[s.r0] : nullptr, f.names.data() + c.name_off[s.r0],
+				                  s.name_off.data(), cm ? f.comments.data() + c.comment_off[s.r0] : nullptr, cm ? s.comment_off.data() : nullptr, (int64_t)c.first_id + s.r0)) {
+					fprintf(stderr, "[E::main] GPU %d: %s\n", g, cs_last_error());
+					return bail();
+				}
+			}
 		}
-		n_reads += (uint64_t)c.n_reads;
-		cur ^= 1;
+		if (fl.empty()) break;
+		for (int g = 0; g < n_gpus; ++g) {
+			cs_sam_result_t res;
+			if (cs_map_collect(mp[(size_t)g], &res)) { fprintf(stderr, "[E::main] GPU %d: %s\n", g, cs_last_error()); return bail(); }
+			if (res.n_bytes && fwrite(res.text, 1, (size_t)res.n_bytes, fo) != (size_t)res.n_bytes) { fprintf(stderr, "[E::main] cannot write %s\n", o.sam); return bail(); }
+		}
+		n_reads += (uint64_t)fl.front().n;
+		fl.pop_front();
 	}
 	const double wall_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 	cs_reader_close(rd);

@@ -92,6 +92,13 @@ int cs_sam_gpu_stats_(const cs_sam_gpu *g, cs_sam_stats_t *st);
 int cs_regions_sam_gpu_(cs_sam_gpu **gp, int device, const cs_refseq_view &R, const std::vector<std::string> &ctg, uint32_t flags, const char *rg_id, const cs_mark_result_t *marks,
                         const uint64_t *reg_off, const cs_cigar_result_t *alns, const uint8_t *bases, const uint64_t *read_offsets, const uint8_t *quals, const char *names,
                         const uint64_t *name_off, const char *comments, const uint64_t *comment_off, cs_sam_result_t *out);
+// The stage's host result arrays against the caller's vectors (host only, no copy): what was the stage's result is the caller's from then
+// on, and the stage writes its next result into what the caller gave.  A null stage (no call yet) exchanges nothing.
+void cs_sam_gpu_exchange_(cs_sam_gpu *g, std::vector<uint64_t> &text_off, std::vector<char> &text);
+// The same through an aligner, for the mapper's streamed batches (mapper.hip), and its counterpart for cs_dedup_regions' result: the arrays
+// of the last call leave the aligner, so that its next call does not overwrite a result that is still being read.
+void cs_aligner_sam_exchange_(cs_aligner_t *a, std::vector<uint64_t> &text_off, std::vector<char> &text);
+void cs_aligner_dedup_exchange_(cs_aligner_t *a, std::vector<uint64_t> &reg_off, std::vector<cs_alnreg_t> &regs);
 
 // ---- the host passes' work sharing: fn(k) for k in [0, n_chunks) on T threads, chunks of reads handed out by a counter.  (A read inside a
 // repeat costs a hundred times the average in the quadratic passes -- chain filter, dedup --; equal shares left fifteen threads waiting for

@@ -79,6 +79,7 @@ static_assert(cssm::C_COUNT < cs_sam_gpu::N_CTR, "the stage's pinned counter blo
 
 void cs_sam_gpu_release_(cs_sam_gpu *g) { cs_dev_stage_delete_(g); }
 int cs_sam_gpu_stats_(const cs_sam_gpu *g, cs_sam_stats_t *st) { return cs_dev_stage_stats_(g, st); }
+void cs_sam_gpu_exchange_(cs_sam_gpu *g, std::vector<uint64_t> &text_off, std::vector<char> &text) { if (g) { g->text_off.swap(text_off); g->text.swap(text); } }
 
 int cs_regions_sam_gpu_(cs_sam_gpu **gp, int device, const cs_refseq_view &R, const std::vector<std::string> &ctg, uint32_t flags, const char *rg_id, const cs_mark_result_t *marks,
                         const uint64_t *reg_off, const cs_cigar_result_t *alns, const uint8_t *bases, const uint64_t *read_offsets, const uint8_t *quals, const char *names,

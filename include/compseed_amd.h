@@ -610,8 +610,9 @@ int  cs_regions_sam(cs_aligner_t *a, const cs_sam_params_t *par, const cs_mark_r
 int  cs_sam_header(const cs_aligner_t *a, const char *rg_line /* may be NULL */, char *buf, size_t cap, size_t *need);
 int  cs_sam_stats(const cs_aligner_t *a, cs_sam_stats_t *st);
 
-/* ---- reads to SAM text in one call: the mapper owns one engine, one device chainer and one aligner on one GPU, the device copy of the
- *      reads, the order of the stage calls above and their errors -- seed_and_extend behind mem_process_seqs (comp_seed.cpp:2239-2420)
+/* ---- reads to SAM text in one call: the mapper owns one engine, one device chainer and its aligners on one GPU (one per part of a batch:
+ *      the extension's, a host-only one for cs_dedup_regions and the tail stages' -- the packed reference once more on host and device, not
+ *      the engine), the device copy of the reads, the order of the stage calls above and their errors -- seed_and_extend behind mem_process_seqs (comp_seed.cpp:2239-2420)
  *      single-end, as the reference's program runs it.  It adds no kernel: every stage is the documented call above, with its limits.
  *      cs_map_params_t is mem_opt_t as the command line fills it; cs_map_params_split is the ONE place where a field several stages
  *      read (min_seed_len, max_occ, max_chain_gap, mask_level, drop_ratio, the scoring) is copied to each of them; the seeding struct's
@@ -621,7 +622,8 @@ int  cs_sam_stats(const cs_aligner_t *a, cs_sam_stats_t *st);
  *      own checks refuses CS_EINVAL; index files missing CS_EIO; no GPU CS_EDEVICE.  On any error everything made so far is released and
  *      *out is NULL.
  *      cs_map_batch: host arrays in, with cs_regions_sam's conventions for quals, names and comments; `id_base`: the number of reads
- *      before this batch (comp_seed.cpp:2410); `out`: as from cs_regions_sam, owned by the mapper and valid until its next cs_map_batch.
+ *      before this batch (comp_seed.cpp:2410); `out`: as from cs_regions_sam, owned by the mapper and valid until its next cs_map_batch
+ *      or cs_map_submit.
  *      Per call: the reads are uploaded once into buffers the mapper owns and grows; cs_engine_seed_batch_device; cs_chain_batch_device;
  *      cs_chain_filter_device; cs_extend_chains_device with CS_ALN_DEV_COMPACT; reg_off and the live regions come to the host;
  *      cs_dedup_regions; cs_regions_mark; cs_regions_cigar over cigar_regs; cs_regions_sam (the three tail stages upload their own copy of
@@ -660,6 +662,33 @@ int  cs_mapper_create(const char *prefix, int device, const cs_engine_options_t 
 void cs_mapper_destroy(cs_mapper_t *m);
 int  cs_map_batch(cs_mapper_t *m, int64_t n_reads, const uint8_t *bases, const uint64_t *read_offsets, const uint8_t *quals, const char *names,
                   const uint64_t *name_off, const char *comments, const uint64_t *comment_off, int64_t id_base, cs_sam_result_t *out);
+/* The same as a stream of batches, up to CS_MAP_MAX_IN_FLIGHT in flight, the counterpart of cs_engine_submit / cs_engine_collect_packed one
+ * level up: cs_map_submit runs cs_map_batch's argument checks (CS_EINVAL: nothing is queued and the stream is as it was), queues the batch
+ * and returns at once; the caller's arrays must stay untouched until the batch is collected.  A submit with CS_MAP_MAX_IN_FLIGHT batches
+ * uncollected is CS_EINVAL and queues nothing.  cs_map_collect blocks until the OLDEST submitted batch is complete and hands out its result;
+ * results come back in submission order; with nothing in flight it returns CS_EINVAL.  A batch is three parts -- front (upload, seeding,
+ * chaining, filter, extension, download), cs_dedup_regions, tail (marking, CIGAR, SAM text) -- and the mapper owns one worker thread per
+ * part, started by the first submit: the parts of one batch run in cs_map_batch's order, each part runs one batch at a time in submission
+ * order, and the three run beside each other on different batches, so that the de-duplication of batch n (host threads) runs beside the
+ * front of batch n+1 and the tail of batch n-1 (both on the GPU).  The text is cs_map_batch's for the same reads, whatever travels
+ * beside them.  n_reads == 0 is a legal batch and gives the empty result in its turn.
+ * A collected result is owned by the mapper and stays valid until the next cs_map_collect, cs_map_batch or cs_mapper_destroy, whatever
+ * is submitted or finishes meanwhile.  The mapper keeps ONE set of the SAM stage's host result arrays more than it has batches in flight
+ * for this: a finished batch's text is exchanged out of the stage, and a collect exchanges it with that spare set and hands out the spare
+ * set's pointers -- pointers change hands, the text (225 bytes per read) is not copied.  A batch that fails in a stage fails at ITS collect:
+ * that stage's code, and cs_last_error (of the collecting thread) starts with "cs_map_collect: <stage>: ".  A collect that returns an error
+ * hands nothing out and does not shorten the life of an earlier result; the batches behind it are not affected, and the mapper stays
+ * usable.  While batches are in flight cs_map_batch returns CS_EINVAL; cs_mapper_destroy waits for them first.
+ * cs_mapper_stats: every step adds its wall time to stage_ms[k] as in cs_map_batch, measured in the thread that ran it; CS_MAP_T_TOTAL of a
+ * streamed batch is its time from submit to completion, so that with batches in flight the steps no longer sum to the total; the
+ * counters and times of a batch are added when it is collected.  cs_mapper_in_flight: batches submitted and not yet collected, and how
+ * many of those are complete (finished <= submitted <= CS_MAP_MAX_IN_FLIGHT); host only, never blocks.
+ * Threads: one submitting thread, one collecting thread, which may be the same; cs_mapper_in_flight from either. */
+#define CS_MAP_MAX_IN_FLIGHT 3
+int  cs_map_submit(cs_mapper_t *m, int64_t n_reads, const uint8_t *bases, const uint64_t *read_offsets, const uint8_t *quals, const char *names,
+                   const uint64_t *name_off, const char *comments, const uint64_t *comment_off, int64_t id_base);
+int  cs_map_collect(cs_mapper_t *m, cs_sam_result_t *out);
+int  cs_mapper_in_flight(const cs_mapper_t *m, int *submitted, int *finished);
 int  cs_mapper_header(const cs_mapper_t *m, const char *rg_line /* may be NULL */, char *buf, size_t cap, size_t *need);
 int  cs_mapper_stats(const cs_mapper_t *m, cs_map_stats_t *st);
 int  cs_mapper_engine_stats(const cs_mapper_t *m, cs_stats_t *st);

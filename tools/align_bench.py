@@ -15,7 +15,8 @@ cs_regions_sam over those marks and their alignments, timed the same way, with t
 cs_sam_stats.  Last: "reads -> SAM text (cs_map_batch)", the whole path as one call of a Mapper of its own on the same reads -- reads/s over the
 median of three calls after a warm-up one, the mapper's per-step host wall time per call, and beside them the sum of this run's separate rows of
 the same steps (device seeding, device chaining, device filter, compacting extension and its download, dedup_regions, marks, marked CIGAR and
-SAM text in default mode); the text is checked equal to the separate stages' text.
+SAM text in default mode); the text is checked equal to the separate stages' text.  Beside it: "reads -> SAM text (cs_map_submit / collect)", the
+same batch as a stream on the same mapper with 1, 2 and 3 batches kept in flight, ms per batch and the per-step times; every text checked equal to cs_map_batch's.
 usage: align_bench.py [reads] [--synth-mbp M]"""
 import gzip, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -188,6 +189,23 @@ def run(n=200000, synth_mbp=0.0):
     for _ in range(MAP_RUNS):
         ta = time.perf_counter(); _, mtext = mp.map_batch(bases, off, names); walls.append(time.perf_counter() - ta)
     s1 = mp.stats()
+    # the same batch as a stream on the same mapper: STREAM_BATCHES submits of it with 1, 2 and 3 kept in flight, wall per batch over the
+    # whole stream (its filling and draining included), every collected text checked equal to cs_map_batch's after the clock has stopped
+    STREAM_BATCHES = 6
+    stream = {}
+    for fl in range(1, ca.MAP_MAX_IN_FLIGHT + 1):
+        q0 = mp.stats(); texts = []; sent = 0
+        ta = time.perf_counter()
+        while len(texts) < STREAM_BATCHES:
+            while sent < STREAM_BATCHES and sent - len(texts) < fl:
+                mp.submit(bases, off, names, id_base=0); sent += 1
+            texts.append(mp.collect()[1])
+        tb = time.perf_counter()
+        q1 = mp.stats()
+        assert all(t == mtext for t in texts), "a streamed batch's text differs from cs_map_batch's (%d in flight)" % fl
+        del texts
+        stream[str(fl)] = {"batches": STREAM_BATCHES, "ms_per_batch": 1e3 * (tb - ta) / STREAM_BATCHES, "reads_per_s": n * STREAM_BATCHES / (tb - ta),
+                           "stage_ms": {k: (q1["stage_ms"][k] - q0["stage_ms"][k]) / STREAM_BATCHES for k in q1["stage_ms"]}}
     mp.close()
     assert mtext == text_default, "cs_map_batch's text differs from the separate stages' text"
     per_m = lambda row: out[row]["median_ms_per_million_reads"] * n / 1e6
@@ -200,6 +218,12 @@ def run(n=200000, synth_mbp=0.0):
                                                "separate_rows_sum_ms": sum(separate.values()), "bytes": len(mtext), "lines": (s1["lines"] - s0["lines"]) // MAP_RUNS,
                                                "unmapped": (s1["unmapped"] - s0["unmapped"]) // MAP_RUNS, "equal_to_separate_stages_text": True,
                                                "note": "host arrays in, the binding's copy of the text included; the separate rows of the tail stages include the binding's copies of their results"}
+    best = min(stream.values(), key=lambda v: v["ms_per_batch"])
+    out["reads -> SAM text (cs_map_submit / collect)"] = {"in_flight": stream, "ms": best["ms_per_batch"], "reads_per_s": best["reads_per_s"], "blocking_ms_same_run": 1e3 * wall,
+                                                          "equal_to_cs_map_batch_text": True,
+                                                          "note": "the batch of the cs_map_batch row submitted %d times on the same mapper with 1, 2 and 3 batches kept in flight; ms per batch over the whole stream, "
+                                                                  "the binding's copy of every text included; stage_ms per batch as cs_mapper_stats adds it up: each step in the thread that ran it, "
+                                                                  "total = submit to completion; ms / reads_per_s: the fastest of the three" % STREAM_BATCHES}
     if tmpdir:
         shutil.rmtree(tmpdir, ignore_errors=True)
     return out
